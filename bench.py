@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the KPFusion forward hot path on MI355X (driver contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs if --dump-outputs is given, and prints the
+result line; everything else it can measure (the fields marked [--full] below) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the timed path returned in its last step, as DIR/<name>.npy (float32, or float64 where
+the path returns float64), rank 0's shard: the backbones workloads `depth_result`, `depth_feature`, `rgb_result`, `rgb_feature`
+(img_result NCHW, img_feature NHWC per stream), the full-model eval workloads `results_<i>` / `sws_<i>` (model(...)'s two lists), the
+training workloads `loss` and `parameters` (every live parameter after the step, flattened and concatenated in model order).  An array
+of more than DUMP_MAX_ELEMS elements is written as a fixed sample (dump_sample_indices: the sorted distinct flat indices of DUMP_MAX_ELEMS
+draws from numpy's default_rng(crc32(name))), the same for every run of the same arguments.  Inputs and weights are seeded: identical arguments
+give identical inputs, so two builds can be compared output for output.
 
 N > 1: either launched once per rank by torch.distributed.run (the driver's form; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the
 environment) or plainly as `python bench.py --gpus N`, in which case this process starts the N ranks itself as a child torchrun job
@@ -17,21 +28,24 @@ Arithmetic of the headline (`value`, `dtype: "f32"`): IEEE fp32 everywhere — e
 fmaf chain), fp32 storage and elementwise math — replayed from a captured hipGraph (both backbone streams as parallel branches).
 
 One JSON line is printed by rank 0 with, besides the contract fields:
-  roofline     : the dominant kernel of the headline run (igemm_f32_kernel) — achieved = algorithmic conv/GEMM FLOPs (2*M*N*K) of all its
+  roofline     : [--full] the dominant kernel of the headline run (igemm_f32_kernel) — achieved = algorithmic conv/GEMM FLOPs (2*M*N*K) of all its
                  launches in one step / summed device time of those launches (HIP events recorded on the launch stream in an
                  instrumented pass after the timed region, both backbones on ONE stream), against the dense f32-input MFMA peak
                  157.3 TFLOP/s.  `traffic` = HBM bytes per launch from the rocprofv3 PMC passes of this same command, collected
                  offline and committed (profiles/r06_traffic*.json, tools/collect_traffic.py): `traffic_source` says so; a figure
                  below 0.9 x the algorithmic bytes, or one whose launch count is not a whole number of this run's steps, is refused
                  (`traffic: null` + `traffic_rejected`).
-  split_f16x3  : SECONDARY record, not the headline and not IEEE fp32: the same workload with KPF_GEMM=split (the ConvNeXt-block GEMMs
+  split_f16x3  : [--full] SECONDARY record, not the headline and not IEEE fp32: the same workload with KPF_GEMM=split (the ConvNeXt-block GEMMs
                  as 3 x f16 MFMA on hi/lo-split operands with a pack-time range proof; everything else stays on the f32 MFMA).
-  extra        : (default run, N = 1) one timed record per further BASELINE config that fits one GPU — `cnb512_f16` (configs[4]: ConvNeXt-B,
+  extra        : [--full] (default workload, N = 1) one timed record per further BASELINE config that fits one GPU — `cnb512_f16` (configs[4]: ConvNeXt-B,
                  512x512, f16, B=64), `full128_bf16` (configs[2]: full model, B=32, bf16), `train128_bf16` (configs[3]: one training
                  iteration, B=32, bf16), `full128_f16` (configs[2] in the recommended 16-bit mode) — and `full256` (the FULL model at the headline's batch and crop size: the labelled wide extension,
                  not a reference configuration), each measured by this script as a child process on that workload, with its own `roofline`.
   world_size   : ranks that took part (dist.get_world_size()), `collective_backend` the RCCL version when a process group exists.
-  cpu_baseline : the CPU oracle (oracle/kpf_oracle.py, torch-CPU fp32 = the reference's own arithmetic) on the host
+  single_batch_latency / single_step_into_idle_gpu : [--full] the full-model eval workloads one batch at a time; one training step
+                 issued into an idle GPU.
+  collectives  : [--full] (N > 1) HIP events around eager RCCL calls after the timed region (collective_probe).
+  cpu_baseline : [--full] the CPU oracle (oracle/kpf_oracle.py, torch-CPU fp32 = the reference's own arithmetic) on the host
                  cores of this box: thread-count sweep, then 5 timed passes at the best count over a bounded sample of the same
                  workload — `value` is their median, the best pass is stated beside it (rank 0, N=1 only).
 """
@@ -141,7 +155,7 @@ EXTRA_WORKLOADS = (("train128_bf16", 30, 5), ("full128_bf16", 30, 5), ("full128_
 def run_extra(workload, steps, warmup, timeout):
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(steps), "--warmup", str(warmup),
-           "--no-cpu-baseline", "--no-extra"]
+           "--full", "--no-cpu-baseline", "--no-extra"]
     t0 = time.perf_counter()
     try:
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
@@ -161,6 +175,56 @@ def run_extra(workload, steps, warmup, timeout):
     out["workload"] = rec["config"]["workload"]
     out["wall_s"] = round(time.perf_counter() - t0, 1)
     return out
+
+
+DUMP_MAX_ELEMS = 1 << 20  # per array (4 MB in float32); at most 8 arrays per workload
+
+
+def step_arrays(out, train_params=None):
+    """{name: device tensor} of what one step returned to its caller (see the module docstring, --dump-outputs)."""
+    def dense(a):  # an engine Act (channel slice of an NHWC buffer) as a B x H x W x C view
+        assert not a.split, "split-format activation"
+        return a.buf.view(a.B * a.H * a.W, a.ld)[:, a.coff:a.coff + a.C].reshape(a.B, a.H, a.W, a.C)
+
+    if train_params is not None:
+        return {"loss": out.detach().reshape(-1), "parameters": torch.cat([p.detach().reshape(-1).float() for p in train_params])}
+    if isinstance(out, tuple) and len(out) == 2 and isinstance(out[0], tuple):  # backbones: ((img_result, img_feature) depth, (...) RGB)
+        (res_d, feat_d), (res_rgb, feat_rgb) = out
+        return {"depth_result": res_d, "depth_feature": dense(feat_d), "rgb_result": res_rgb, "rgb_feature": dense(feat_rgb)}
+    res, sws = out[0], out[1]
+    arrays = {"results_%d" % i: t for i, t in enumerate(res)}
+    arrays.update({"sws_%d" % i: t for i, t in enumerate(sws)})
+    return arrays
+
+
+def dump_sample_indices(name, n):
+    """The flat indices dump_outputs writes of an n-element array `name`: None (all of it) up to DUMP_MAX_ELEMS elements, else the sorted
+    distinct values of DUMP_MAX_ELEMS draws from numpy's default_rng(crc32(name)) — the same for every run."""
+    import zlib
+    import numpy as np
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    return np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, DUMP_MAX_ELEMS))
+
+
+def dump_outputs(arrays, out_dir):
+    """Write {name: device tensor} as out_dir/<name>.npy (float64 stays float64, anything else float32); an array of more than
+    DUMP_MAX_ELEMS elements as the seeded sample the module docstring describes.  Returns {name: [shape, elements written]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        flat = flat.double() if flat.dtype == torch.float64 else flat.float()
+        idx = dump_sample_indices(name, flat.numel())
+        if idx is not None:
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        a = flat.cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a if idx is not None else a.reshape(tuple(t.shape)))
+        written[name] = [list(t.shape), int(a.size)]
+    assert total <= 64 * 1000 * 1000, "dump of %d bytes exceeds 64 MB" % total
+    return written
 
 
 def collective_probe(dist, dev, world, gstep, iters=5):
@@ -223,6 +287,9 @@ def main():
     ap.add_argument("--in-flight", type=int, default=2, help="full-model eval workloads: batches in flight (serving.PipelinedEval: independent "
                     "hipGraph slots on their own streams, the latency-bound fusion head of one batch beside the backbones of the next); "
                     "1 = one synchronous forward per step")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline pass, split record, CPU baseline, "
+                    "secondary workloads, single-batch latency, collective probes (a plain run only times the steps)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -298,13 +365,14 @@ def main():
 
     graph_on = [not args.no_graph and not args.serial_streams]
     pipe, pending = [None], []
+    last = [None]  # what the latest step (pipelined eval: the latest collected batch) returned to its caller
 
     def step():
         if train:
             if graphed_train and graph_on[0]:
                 if gstep[0] is None:
                     gstep[0] = T.GraphedTrainStep(model, opt, train_loss, tbatch, dist_mod=dist, params=live, scaler=scaler)
-                gstep[0](tbatch)
+                last[0] = gstep[0](tbatch)
                 return
             opt.zero_grad(set_to_none=False)
             if reducer is not None:
@@ -317,13 +385,14 @@ def main():
                 opt.step()
             else:
                 opt.step(scaler=scaler)
+            last[0] = loss.detach()
             return
         with torch.no_grad():
             if backbones_only:
                 if graph_on[0]:
-                    model._plan(dev).backbones_graphed(batch["img"], batch["img_rgb"])
+                    last[0] = model._plan(dev).backbones_graphed(batch["img"], batch["img_rgb"])
                 else:
-                    model._plan(dev).backbones(batch["img"], batch["img_rgb"])
+                    last[0] = model._plan(dev).backbones(batch["img"], batch["img_rgb"])
             elif graph_on[0] and args.in_flight > 1:
                 if pipe[0] is None:
                     from keypointfusion_amd.serving import PipelinedEval
@@ -331,15 +400,15 @@ def main():
                 pending.append(pipe[0].submit(batch["img_rgb"], batch["img"], batch["pcl"], _Loader(), batch["center"], batch["M"], batch["cube"],
                                               batch["cam_para"], 0.8))
                 if len(pending) > args.in_flight:  # a real loop consumes the oldest batch's outputs here
-                    pipe[0].collect(pending.pop(0))
+                    last[0] = pipe[0].collect(pending.pop(0))
             else:
                 model.use_graphs = graph_on[0]
-                model(batch["img_rgb"], batch["img"], batch["pcl"], _Loader(), batch["center"], batch["M"], batch["cube"],
-                      batch["cam_para"], 0.8)
+                last[0] = model(batch["img_rgb"], batch["img"], batch["pcl"], _Loader(), batch["center"], batch["M"], batch["cube"],
+                                batch["cam_para"], 0.8)
 
     def barrier():
         while pending:  # (pipelined eval: every submitted batch is collected inside the timed region)
-            pipe[0].collect(pending.pop(0))
+            last[0] = pipe[0].collect(pending.pop(0))
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
@@ -457,8 +526,11 @@ def main():
         launch_mode += (", %d batches in flight (independent graph slots / streams; the loop submits from its own stream)" % args.in_flight) if not args.stage_pipeline else (
             ", stage pipeline over %d buffer sets (backbone graphs on one stream beside the head graphs on another)" % args.in_flight)
     dt, t_issue = timed(args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs on the model: the static output buffers still hold the last timed step's
+        dumped = dump_outputs(step_arrays(last[0], live if train else None), args.dump_outputs)
     single = None
-    if train:  # one step issued into an idle GPU: host time of the enqueue vs the step's whole duration (which of the two bounds a replay)
+    if train and args.full:  # one step issued into an idle GPU: host time of the enqueue vs the step's whole duration (which of the two bounds a replay)
         iss, tot = [], []
         for _ in range(3):
             barrier()
@@ -470,7 +542,7 @@ def main():
             tot.append(time.perf_counter() - t0)
         single = {"issue_ms": round(min(iss) * 1e3, 3), "total_ms": round(min(tot) * 1e3, 3)}
     latency = None
-    if not train and not backbones_only and rank == 0:
+    if not train and not backbones_only and rank == 0 and args.full:
         # the same forward ONE batch at a time (module forward, hipGraph replay when graphs are on): the latency a caller of model(...) sees, beside the
         # throughput of the pipelined loop above; and the library entry points one eager forward calls (a handful issue two kernels)
         model.use_graphs = graph_on[0]
@@ -504,12 +576,13 @@ def main():
         ms = [float(t.item()) / args.steps * 1e3 for t in every]
         per_rank = {"min": round(min(ms), 3), "max": round(max(ms), 3), "spread_pct": round((max(ms) / min(ms) - 1) * 100, 2), "all": [round(v, 3) for v in ms]}
         dt = max(float(t.item()) for t in every)
-        collectives = collective_probe(dist, dev, world, gstep[0] if train else None)
+        if args.full:
+            collectives = collective_probe(dist, dev, world, gstep[0] if train else None)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
 
     roofline = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.per_launch):
         recs = instrumented()
         if args.per_launch:
             with open(args.per_launch, "w") as f:
@@ -521,7 +594,7 @@ def main():
 
     # ---- secondary record: split (3 x f16) arithmetic where a range proof exists; NOT the headline, NOT IEEE fp32 ----
     split_rec = None
-    if rank == 0 and world == 1 and args.gemm == "f32" and not args.no_split_record:
+    if rank == 0 and world == 1 and args.gemm == "f32" and args.full and not args.no_split_record:
         try:
             E.GEMM_MODE = "split"
             fresh_plan()
@@ -539,7 +612,7 @@ def main():
             fresh_plan()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import kpf_oracle as O
         n = min(args.cpu_sample, B)
         cb = {k: torch.from_numpy(v[:n]) for k, v in hb.items()}
@@ -588,9 +661,9 @@ def main():
                "host": "%s, nproc %d" % (cpu_model(), os.cpu_count() or 0)}
 
     extra = None
-    if rank == 0 and world == 1 and dist is None and args.workload == "backbones256" and not args.no_extra and not args.batch and under_profiler():
+    if rank == 0 and world == 1 and dist is None and args.workload == "backbones256" and args.full and not args.no_extra and not args.batch and under_profiler():
         print("bench.py: a profiler is preloaded; the secondary workloads are not started as children of a profiled run", file=sys.stderr)
-    elif rank == 0 and world == 1 and dist is None and args.workload == "backbones256" and not args.no_extra and not args.batch:
+    elif rank == 0 and world == 1 and dist is None and args.workload == "backbones256" and args.full and not args.no_extra and not args.batch:
         # the headline's buffers are no longer needed: give the memory back before the children build their own models
         pipe[0] = None
         model._plans.clear()
@@ -629,6 +702,8 @@ def main():
         }
         if extra is not None:
             line["extra"] = extra
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if single is not None:
             line["single_step_into_idle_gpu"] = single
         if latency is not None:

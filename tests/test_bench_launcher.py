@@ -1,7 +1,8 @@
 """bench.py's own launcher (replaces train.py:81 / demo_RGBD.py:49, `DataParallel(net).cuda()`: one command, all GPUs of the node).
 CPU: the command `python bench.py --gpus 8` would start is the driver's form, and the traffic guard refuses impossible figures.
 GPU (one device is enough): the launcher route with ONE RCCL rank, as a fresh child process, for the eval headline and for the graphed
-data-parallel training step — world_size, the RCCL backend and the one-graph `overlap` form are asserted from the printed line."""
+data-parallel training step — world_size, the RCCL backend and the one-graph `overlap` form are asserted from the printed line (--full);
+and a plain run: the headline only, with the last timed step's outputs written by --dump-outputs."""
 import json
 import os
 import subprocess
@@ -47,7 +48,7 @@ def _run_bench(extra_args):
     env = dict(os.environ, KPF_BENCH_FORCE_DIST="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--no-extra", "--no-cpu-baseline", "--no-split-record",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--no-extra", "--no-cpu-baseline", "--no-split-record",
                           "--steps", "3", "--warmup", "2"] + extra_args, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -80,3 +81,51 @@ def test_self_launched_one_rank_rccl_graphed_training_step():
     assert len(co["buckets"]) == rec["dp_graph"]["buckets"] >= 2 and all(b["ms"] > 0 and b["bytes"] > 0 for b in co["buckets"])
     assert co["all_buckets"]["bytes"] == rec["dp_graph"]["payload_bytes_per_rank"]
     assert len(rec["per_rank_ms_per_step"]["all"]) == 1 and "prediction" in rec["dp_graph"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) carries the headline only; --dump-outputs writes the last timed step's backbone outputs (float32, <= 64 MB):
+    the dumped values equal, at bench.dump_sample_indices, the same seeded batch through the module's eager forward_backbones (the graph
+    replay bench.py times is bit-identical to the eager launches: tests/test_parity_gpu.py)."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "KPF_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["dtype"] == "f32"
+    assert abs(rec["value"] - 64 * 1e3 / rec["ms_per_step"]) < 1e-2 * rec["value"]
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["split_f16x3"] is None and "extra" not in rec
+    import numpy as np
+    names = {"depth_result", "depth_feature", "rgb_result", "rgb_feature"}
+    assert {f[:-4] for f in os.listdir(tmp_path)} == names == set(rec["dumped_outputs"]["arrays"])
+    total = 0
+    for n in names:
+        a = np.load(os.path.join(tmp_path, n + ".npy"))
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.size == rec["dumped_outputs"]["arrays"][n][1] > 0
+        total += a.nbytes
+    assert total <= 64e6
+
+    # the values: bench.py's model and seeded batch, recomputed here by the module's own eager forward (NCHW; the features permuted to NHWC)
+    import torch
+    from keypointfusion_amd.model.model import KPFusion
+    from keypointfusion_amd.weights import synthetic_batch, synthetic_state_dict
+    net, dev = bench.WORKLOADS["backbones256"][0], torch.device("cuda:0")
+    m = KPFusion(net, "", 21, "dexycb", "", crop_size=128)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synthetic_state_dict(net, 0, crop_size=128).items()}, strict=True)
+    m = m.to(dev).eval()
+    hb = synthetic_batch(64, 256, seed=1)
+    with torch.no_grad():
+        od, fd, orgb, frgb = m.forward_backbones(torch.from_numpy(hb["img_rgb"]).to(dev), torch.from_numpy(hb["img"]).to(dev))
+    want = {"depth_result": od, "depth_feature": fd.permute(0, 2, 3, 1), "rgb_result": orgb, "rgb_feature": frgb.permute(0, 2, 3, 1)}
+    for n, t in want.items():
+        assert list(t.shape) == rec["dumped_outputs"]["arrays"][n][0]
+        flat = t.reshape(-1).cpu().numpy()
+        idx = bench.dump_sample_indices(n, flat.size)
+        ref = flat if idx is None else flat[idx]
+        got = np.load(os.path.join(tmp_path, n + ".npy")).reshape(-1)
+        assert np.ptp(ref) > 0 and np.array_equal(got, ref), n

@@ -59,8 +59,11 @@ def test_posenet_oracle_matches_reference_vectors():
     for case in POSENET_CASES:
         tag, sd, x = posenet_case(*case)
         preds, feat = A.posenet_forward(sd, x, case[0])
-        _close(preds[:, :, ::2, ::2], g[tag + "_preds_sub"], atol=5e-5)
-        _close(feat[:, ::4], g[tag + "_feat_sub"], atol=5e-5)
+        # fp32 fixtures of a deep stack of convolutions and residual sums: their own distance from the exact (float64) forward is up to
+        # 1.4e-4 where |feat| reaches 228, i.e. ~6e-7 of the map's largest magnitude.  Another summation order (oneDNN's choice depends on
+        # threads and ISA) moves the oracle by as much, so the absolute bound follows that scale: 2e-6 x max|ref|, never below 5e-5.
+        for out, ref in ((preds[:, :, ::2, ::2], g[tag + "_preds_sub"]), (feat[:, ::4], g[tag + "_feat_sub"])):
+            _close(out, ref, atol=max(5e-5, 2e-6 * float(np.abs(ref).max())))
 
 
 def test_mano_oracle_matches_reference_vectors():

@@ -33,13 +33,20 @@ def _inputs():
     return img, uvd_gt, xyz_gt, results, sws
 
 
+def _same_maps(a, ref, ulps):
+    """Maps with values in [-1, 1] computed by the same torch ops as the fixture: the same zero support (the kernel-radius / on-hand
+    masks) and every value within `ulps` float32 roundings of 1.  CPU builds and ISAs may evaluate an elementwise op differently in the
+    last bit (division by a scalar as a product with its reciprocal, another summation order of the three squares: <= 1 rounding each)."""
+    return np.array_equal(a == 0, ref == 0) and float(np.abs(a.astype(np.float64) - ref).max()) <= ulps * float(np.finfo(np.float32).eps)
+
+
 def test_loss_codec_matches_reference_fixtures():
     img, uvd_gt, xyz_gt, results, sws = _inputs()
     pg = TO.joint2offset(uvd_gt, img, 0.8, 32)
-    assert np.array_equal(pg.numpy(), Z["pixel_gt"]), "GFM.joint2offset target maps"  # same torch ops in the same order: bit-exact
+    assert _same_maps(pg.numpy(), Z["pixel_gt"], 2), "GFM.joint2offset target maps"  # same torch ops in the same order
     assert np.abs(TO.offset2joint_weight(results[0], img, 0.8).numpy() - Z["decode0"]).max() < 1e-6
-    assert np.array_equal(TO.joint2heatmap(uvd_gt[:, :, :2], 0.8, 32, sigma=3).numpy()[:, ::5], Z["hm_sigma3"])
-    assert np.array_equal(TO.joint2heatmap(uvd_gt[:, :, :2], 0.8, 32, sigma=2).numpy()[:, ::5], Z["hm_sigma2"])
+    assert _same_maps(TO.joint2heatmap(uvd_gt[:, :, :2], 0.8, 32, sigma=3).numpy()[:, ::5], Z["hm_sigma3"], 4)
+    assert _same_maps(TO.joint2heatmap(uvd_gt[:, :, :2], 0.8, 32, sigma=2).numpy()[:, ::5], Z["hm_sigma2"], 4)
     z = torch.from_numpy(Z["sl1_x"])
     assert abs(float(T.SmoothL1Loss()(z, torch.zeros_like(z))) - float(Z["sl1_mean"])) < 1e-9
     assert abs(float(T.SmoothL1Loss(size_average=False)(z, torch.zeros_like(z))) - float(Z["sl1_sum"])) < 1e-9

@@ -1,4 +1,4 @@
-run() { echo "== $1: $(python bench.py $1 --no-cpu-baseline --no-extra --no-split-record --steps ${2:-30} --warmup 5 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"; }
+run() { echo "== $1: $(python bench.py $1 --full --no-cpu-baseline --no-extra --no-split-record --steps ${2:-30} --warmup 5 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"; }
 run ""
 run "--workload train128" 20
 run "--workload train128" 20

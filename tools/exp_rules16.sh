@@ -1,4 +1,4 @@
-run() { echo "== $1 $2: $(env $1 python bench.py --workload $2 --no-cpu-baseline --no-extra --steps ${3:-10} --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"; }
+run() { echo "== $1 $2: $(env $1 python bench.py --workload $2 --full --no-cpu-baseline --no-extra --steps ${3:-10} --warmup 3 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"; }
 for rep in 1 2; do
 run KPF_NO_KXK16=1 cnb512_f16
 run A=1 cnb512_f16

@@ -1,7 +1,8 @@
 """One synchronised forward at a time (bench.py's single_batch_latency loop) from a rocprofv3 kernel trace: the trace is cut at idle gaps, and for the
 last forwards it prints launches, span, busy (union of kernel intervals), per-queue launch counts, where the backbones end and the head begins, and the
 largest kernels / gaps — what bounds the latency a caller of model(...) sees.
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/p -- python3 bench.py --workload full128_bf16 --no-cpu-baseline --no-extra; python3 tools/latency_segments.py /tmp/p [out.txt]
+  rocprofv3 --kernel-trace --output-format csv -d <trace dir> -- python3 bench.py --workload full128_bf16 --full --no-cpu-baseline --no-extra
+  python3 tools/latency_segments.py <trace dir> [out.txt]
 """
 import collections, csv, glob, re, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -26,7 +26,7 @@ traffic() {  # traffic <name> <kernel> <bench args...>: two PMC passes of one be
     && cp $OUT/${TAG}_traffic$name.json $ROOT/profiles/
   rm -rf $OUT/pmc_${TAG}_fetch$name $OUT/pmc_${TAG}_write$name
 }
-HEAD="--serial-streams --no-cpu-baseline --no-split-record --no-extra"
+HEAD="--serial-streams --full --no-cpu-baseline --no-split-record --no-extra"
 if [ "$MODE" != rest ]; then  # (rest: the first half already ran)
 # configs[1], the headline: 136 igemm_f32_kernel launches per step
 stats bench igemm_f32_kernel $HEAD --steps 15
@@ -44,7 +44,7 @@ if [ "$MODE" != quick ]; then
   # its FETCH_SIZE pass and did not return from its WRITE_SIZE pass within 40 minutes on this pool (round 5, gpurun_out/r05_profile.log); `traffic` stays null there
   for W in train128 train128_bf16; do
     rm -rf $OUT/prof_${TAG}_$W
-    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$W -- python3 $ROOT/bench.py --workload $W --no-cpu-baseline --no-extra --steps 10 --warmup 3 > $OUT/prof_${TAG}_$W.log 2> $OUT/prof_${TAG}_$W.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$W -- python3 $ROOT/bench.py --workload $W --full --no-cpu-baseline --no-extra --steps 10 --warmup 3 > $OUT/prof_${TAG}_$W.log 2> $OUT/prof_${TAG}_$W.err
     python3 $ROOT/tools/pick_stats.py $OUT/prof_${TAG}_$W adamw_multi_kernel $OUT/${TAG}_${W}_kernel_stats.csv
     # ONE graph replay of the training iteration cut out of the same trace: launches, kernel time, library share
     python3 $ROOT/tools/replay_histogram.py $OUT/prof_${TAG}_$W $OUT/${TAG}_${W}_replay_hist.txt 2> /dev/null
@@ -52,10 +52,10 @@ if [ "$MODE" != quick ]; then
 fi
 # the bench lines of the same build, without the profiler (the traffic files just collected are what `roofline.traffic` quotes)
 cd $ROOT
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 if [ "$MODE" != quick ]; then
   for W in full128 full128_bf16 full128_f16 cnb512_f16 train128 train128_bf16 train128_f16 full256; do
-    python3 bench.py --workload $W --no-cpu-baseline --no-extra > $OUT/${TAG}_bench_$W.json 2> $OUT/${TAG}_bench_$W.err
+    python3 bench.py --workload $W --full --no-cpu-baseline --no-extra > $OUT/${TAG}_bench_$W.json 2> $OUT/${TAG}_bench_$W.err
   done
   python3 tools/shape_table.py > $OUT/${TAG}_shape_table.txt 2>/dev/null
   python3 tools/shape_table.py 64 512 f16 KPFusion-convnext-base > $OUT/${TAG}_shape_cnb512.txt 2>/dev/null
@@ -63,10 +63,10 @@ if [ "$MODE" != quick ]; then
 fi
 # configs[2]: one synchronised forward at a time, cut out of a kernel trace (what bounds the single-batch latency)
 cd /tmp
-rm -rf /tmp/pl_$TAG
-rocprofv3 --kernel-trace --output-format csv -d /tmp/pl_$TAG -- python3 $ROOT/bench.py --workload full128_bf16 --no-cpu-baseline --no-extra --steps 10 --warmup 3 > /dev/null 2>&1
-python3 $ROOT/tools/latency_segments.py /tmp/pl_$TAG $OUT/${TAG}_full128_bf16_latency_segments.txt
-rm -rf /tmp/pl_$TAG
+PL=$(mktemp -d)
+rocprofv3 --kernel-trace --output-format csv -d $PL -- python3 $ROOT/bench.py --workload full128_bf16 --full --no-cpu-baseline --no-extra --steps 10 --warmup 3 > /dev/null 2>&1
+python3 $ROOT/tools/latency_segments.py $PL $OUT/${TAG}_full128_bf16_latency_segments.txt
+rm -rf $PL
 cd $ROOT
 # keep the merge small: the raw traces stay on the box
 for d in $OUT/prof_${TAG}_*; do [ -d "$d" ] && rm -rf "$d"; done

@@ -2,7 +2,7 @@
 # one-off experiment batch (GPU box)
 O=gpurun_out
 python -m pytest tests/test_parity_gpu.py tests/test_kernels_train_gpu.py tests/test_reduced_precision_gpu.py tests/test_training.py -m gpu -x -q > $O/r05c_gputest.log 2>&1; tail -3 $O/r05c_gputest.log
-B="python bench.py --no-cpu-baseline --no-extra"
+B="python bench.py --full --no-cpu-baseline --no-extra"
 $B --workload cnb512_f16 > $O/r05c_cnb_base.json 2> $O/r05c_cnb_base.err
 KPF_MLP16_CHUNKS=2 $B --workload cnb512_f16 > $O/r05c_cnb_ch2.json 2> $O/r05c_cnb_ch2.err
 KPF_MLP16_CHUNKS=4 $B --workload cnb512_f16 > $O/r05c_cnb_ch4.json 2> $O/r05c_cnb_ch4.err
