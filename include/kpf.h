@@ -739,12 +739,45 @@ int kpf_geom_gate_uvd_forward(const float* pix_xyz, const float* joint_uvd, cons
 int kpf_geom_gate_uvd_backward(const float* pix_xyz, const float* joint_uvd, const float* par16, const float* dgam, float* djoint_uvd, int B, int J, int P,
                                float half_size, float flip, void* stream);
 
+/* Device-side RGB-D preprocessing (ABI 18): keypointfusion_amd/preprocess.py::prepare_rgbd for a batch of frames, and the un-crop of predicted joints
+ * (reference: demo_RGBD.py:72-108, :121-147).  Every argument is a device buffer, so a captured graph picks up new frames, boxes and seeds at replay; grids
+ * depend on B, S and n only; a sample's result does not depend on B.  Integer decisions and both images are bit-equal to the host path.
+ *
+ * kpf_prep_crop_u16: rgb [B][Hs][Ws][3] uint8 (channel order kept), depth [B][Hs][Ws] uint16 mm, bbox [B][4] double (x, y, w, h; top-left), cam [B][4] double
+ * (fx fy u0 v0), cube [B][3] double (mm).  The stored image is the window [y0, y0 + Hs) x [x0, x0 + Ws) of a logical H x W frame whose other pixels read as
+ * zero (a whole frame: x0 = y0 = 0, H = Hs, W = Ws).  One workgroup per sample: centre of mass of the valid depth in the box (64-bit integer sums, exact) ->
+ * pixel bounds of the cube -> nearest-neighbour crop with zero padding, letterboxed into S x S -> z-clamp (near plane truncated to uint16) -> normalised depth.
+ * -> img [B][1][S][S], img_rgb [B][3][S][S] (/ 255), center [B][3], M [B][3][3], cube_out [B][3], cam_para [B][4] (float: the model's inputs), and the record
+ * com [B][3] double (u, v, d mm), bounds [B][6] int (xs, xe, ys, ye, resize width, resize height), M64 [B][3][3] double (M before its rounding to float).
+ * S * S <= 16384. */
+int kpf_prep_crop_u16(const unsigned char* rgb, const unsigned short* depth, const double* bbox, const double* cam, const double* cube, int B, int Hs, int Ws,
+                      int x0, int y0, int H, int W, int S, float* img, float* img_rgb, float* center, float* M, float* cube_out, float* cam_para, double* com,
+                      int* bounds, double* M64, void* stream);
+
+/* kpf_prep_pcl_sample: depth_to_pcl + sample_points on kpf_prep_crop_u16's outputs (img, center, M64) and the same cube / cam.  The foreground pixels in
+ * row-major order (np.where) are the candidates; N = their number.  n of them are drawn without replacement IN RANDOM ORDER: (key, candidate) pairs, key = a
+ * counter hash of (seed[b], candidate), are sorted in LDS and the first n taken.  0 < N < n: every candidate floor(n / N) times, n mod N distinct ones once
+ * more, the n slots shuffled.  N == 0: zeros, index -1.  -> pcl [B][n][3] float (clipped to [-1, 1]), pcl_index [B][n] int (candidate index), pcl_count [B]
+ * int (N).  cand_pts: NULL, or [B][S * S][3] float receiving every candidate's point at its candidate index (rows >= N untouched): tests and debugging.
+ * seed [B] 64-bit.  n <= S * S <= 16384, and (pow2ceil(S * S) + pow2ceil(n)) * 8 + 128 bytes of LDS must fit 160 KiB. */
+int kpf_prep_pcl_sample(const float* img, const float* center, const double* M64, const double* cube, const double* cam, const long long* seed, int B, int S,
+                        int n, float* pcl, int* pcl_index, int* pcl_count, float* cand_pts, void* stream);
+
+/* kpf_prep_uncrop_f32: joints [B][J][3] normalised to the cube + center, M, cube_out, cam_para of kpf_prep_crop_u16 -> crop_px [B][J][3] (u, v in crop
+ * pixels, d mm: preprocess.project_to_crop) and frame_px [B][J][3] (u, v in frame pixels: preprocess.uncrop_points).  Double inside, one thread per joint. */
+int kpf_prep_uncrop_f32(const float* joints, const float* center, const float* M, const float* cube, const float* cam, int B, int J, float* crop_px,
+                        float* frame_px, void* stream);
+
+int kpf_prep_set_stamps(void* stamps64 /* tuning aid: [B][8] device uint64 slots for in-kernel wall-clock stamps (100 MHz) of every sample's workgroup:
+                                            kpf_prep_crop_u16 0 start, 1 geometry, 2 gather, 3 end; kpf_prep_pcl_sample 4 start, 5 compacted, 6 sorted, 7 end;
+                                            NULL = off.  Synchronises with the device: not for captured code */);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 17
+#define KPF_ABI_VERSION 18
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -57,6 +57,17 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// "lowbias32" integer hash: full avalanche in three multiplies.  The project's counter hash: dropout masks (kpf_train.hip, kpf_trstack.hip) and the
+// point-cloud sampling keys (kpf_prep.hip) are hash32 of (seed, counter) words.
+__host__ __device__ __forceinline__ unsigned hash32(unsigned x) {
+  x ^= x >> 16;
+  x *= 0x7feb352dU;
+  x ^= x >> 15;
+  x *= 0x846ca68bU;
+  x ^= x >> 16;
+  return x;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // "Split" operand format for the 3 x f16 MFMA path (kpf_conv.hip): a row of C fp32 values (C % 32 == 0) occupies the same
 // C*4 bytes as C/32 blocks of [32 x f16 hi | 32 x f16 lo] with x ~= hi + lo (22 significant bits; |x| is clamped to the

@@ -1,0 +1,534 @@
+// Device-side RGB-D preprocessing (keypointfusion_amd/preprocess.py on the GPU): frames and boxes in, the model's seven inputs out, and the un-crop of
+// the predicted joints.  Three launches, one workgroup per sample (kpf_prep_uncrop_f32: one thread per joint), fixed grids, no host synchronisation:
+//
+//   kpf_prep_crop_u16    box -> centre of mass (exact 64-bit integer sums, finished by one lane in double) -> metric bounds -> nearest-neighbour crop with
+//                        zero padding -> z-clamp -> normalised depth image and RGB crop, plus center / M / cube / cam_para
+//   kpf_prep_pcl_sample  foreground pixels of the normalised crop -> candidate points in np.where order -> n of them without replacement IN RANDOM ORDER:
+//                        (hash key, candidate) pairs sorted by a bitonic network in LDS (only those under a threshold that about 1.5 n pass), the first n taken
+//   kpf_prep_uncrop_f32  normalised joints -> crop pixels -> frame pixels
+//
+// The host path is the yardstick (tests/test_preprocess_gpu.py): integer decisions and both images are bit-equal to it.  Everything that decides an integer
+// is computed in double in the HOST'S operation order, and the whole file is compiled with floating-point contraction OFF (the Makefile's -ffp-contract=on
+// would fuse `a * b + c`, which numpy rounds twice); float32 divisions are IEEE divisions.
+#include "kpf_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int PREP_NT = 1024;  // threads per sample: 16 waves on one CU
+constexpr int PREP_NW = PREP_NT / 64;
+constexpr int PREP_MAX_PIX = 16384;  // S * S: a candidate index and a pixel index take 14 bits each of a sort element
+
+// ---- preprocess.center_from_bbox: the box in integer pixels, clipped to the frame like a numpy slice (negative corners, which numpy would wrap, clip to 0)
+struct PrepBox {
+  int x0, x1, y0, y1;  // clipped: columns [x0, x1), rows [y0, y1)
+};
+__host__ __device__ inline PrepBox prep_box(const double* bbox, int H, int W) {
+  const int bx0 = (int)bbox[0], bx1 = (int)(bbox[0] + bbox[2]), by0 = (int)bbox[1], by1 = (int)(bbox[1] + bbox[3]);
+  PrepBox r;
+  r.x0 = min(max(bx0, 0), W);
+  r.x1 = min(max(bx1, r.x0), W);
+  r.y0 = min(max(by0, 0), H);
+  r.y1 = min(max(by1, r.y0), H);
+  return r;
+}
+
+struct PrepGeom {
+  double com[3];                   // centre of mass (u, v, d mm)
+  int xs, xe, ys, ye;              // com_to_bounds
+  int szw, szh, offx, offy;        // resize size (w, h) and letterbox offsets inside the S x S crop
+  double zs, ze;                   // z range of the cube
+  double stepx, stepy;             // resize_nearest: source pixels per destination pixel
+  double scale, m02, m12;          // M = [[scale, 0, m02], [0, scale, m12], [0, 0, 1]]
+  float far, near, comz, halfz;    // normalize_depth's float32 scalars
+  float center[3];                 // image_to_3d(com)
+};
+
+// count / sums over the valid depth of the box (indices relative to the clipped box) -> everything crop_image and normalize_depth need
+__host__ __device__ inline void prep_geom(unsigned long long cnt, unsigned long long sumx, unsigned long long sumy, unsigned long long sumd, const PrepBox& bx,
+                                          const double* bbox, const double* cam, const double* cube, int S, PrepGeom& g) {
+  double c0 = 0.0, c1 = 0.0, c2 = 300.0;
+  if (cnt > 0) {
+    // np.meshgrid(np.linspace(0, w, w), np.linspace(0, h, h)): sample i sits at i * (w / (w - 1)); the mean of the selected ones is the integer mean
+    // times that step (the host sums the float64 coordinates pairwise: a few 1e-13 relative apart)
+    const int w = bx.x1 - bx.x0, h = bx.y1 - bx.y0;
+    const double sx = w > 1 ? (double)w / (double)(w - 1) : 0.0, sy = h > 1 ? (double)h / (double)(h - 1) : 0.0;
+    c0 = (double)sumx * sx / (double)cnt;
+    c1 = (double)sumy * sy / (double)cnt;
+    c2 = (double)sumd / (double)cnt;  // exact integer sum, one division: the host's float64 mean of uint16 values bit for bit
+    if (c2 <= 0) c2 = 300.0;
+  }
+  c0 += bbox[0];
+  c1 += bbox[1];
+  g.com[0] = c0;
+  g.com[1] = c1;
+  g.com[2] = c2;
+  const double fx = cam[0], fy = cam[1], fu = cam[2], fv = cam[3];
+  g.zs = c2 - cube[2] / 2.0;
+  g.ze = c2 + cube[2] / 2.0;
+  g.xs = (int)floor((c0 * c2 / fx - cube[0] / 2.0) / c2 * fx + 0.5);
+  g.xe = (int)floor((c0 * c2 / fx + cube[0] / 2.0) / c2 * fx + 0.5);
+  g.ys = (int)floor((c1 * c2 / fy - cube[1] / 2.0) / c2 * fy + 0.5);
+  g.ye = (int)floor((c1 * c2 / fy + cube[1] / 2.0) / c2 * fy + 0.5);
+  const int wb = g.xe - g.xs, hb = g.ye - g.ys;
+  if (wb <= 0 || hb <= 0) {  // a cube that projects to nothing (not reachable with positive focal lengths and cube sizes): an empty crop
+    g.szw = g.szh = 0;
+  } else if (wb > hb) {
+    g.szw = S;
+    g.szh = (int)((double)((long long)hb * S) / (double)wb);
+  } else {
+    g.szw = (int)((double)((long long)wb * S) / (double)hb);
+    g.szh = S;
+  }
+  g.scale = hb > wb ? (double)g.szh / (double)hb : (double)g.szw / (double)(wb > 0 ? wb : 1);
+  g.stepx = g.szw > 0 ? (double)wb / (double)g.szw : 0.0;
+  g.stepy = g.szh > 0 ? (double)hb / (double)g.szh : 0.0;
+  g.offx = (int)floor((double)S / 2.0 - (double)g.szw / 2.0);
+  g.offy = (int)floor((double)S / 2.0 - (double)g.szh / 2.0);
+  g.m02 = g.scale * (double)(-g.xs) + (double)g.offx;  // off . (scale . trans): one product, one sum, each rounded
+  g.m12 = g.scale * (double)(-g.ys) + (double)g.offy;
+  g.far = (float)(c2 + cube[2] / 2.0);
+  g.near = (float)(c2 - cube[2] / 2.0);
+  g.comz = (float)c2;
+  g.halfz = (float)(cube[2] / 2.0);
+  g.center[0] = (float)((c0 - fu) * c2 / fx);
+  g.center[1] = (float)((c1 - fv) * c2 / fy);
+  g.center[2] = (float)c2;
+}
+
+// Frame pixel behind crop pixel (oy, ox): false = letterbox border
+__host__ __device__ inline bool prep_source(const PrepGeom& g, int oy, int ox, int& fy, int& fx) {
+  const int ry = oy - g.offy, rx = ox - g.offx;
+  if (ry < 0 || ry >= g.szh || rx < 0 || rx >= g.szw) return false;
+  const int hb = g.ye - g.ys, wb = g.xe - g.xs;
+  fy = g.ys + min((int)floor((double)ry * g.stepy), hb - 1);  // resize_nearest's index rule
+  fx = g.xs + min((int)floor((double)rx * g.stepx), wb - 1);
+  return true;
+}
+
+// get_crop's z-clamp on the sensor's uint16 values: nearer than the cube -> the near plane TRUNCATED to uint16, farther -> 0
+__host__ __device__ inline unsigned short prep_zclamp(unsigned short v, const PrepGeom& g) {
+  if (v != 0 && (double)v < g.zs) return (unsigned short)g.zs;
+  if (v != 0 && (double)v > g.ze) return 0;
+  return v;
+}
+
+// normalize_depth on one pixel (premax: the maximum of the z-clamped S x S crop), float32 like the host
+__host__ __device__ inline float prep_normalize(unsigned short raw, unsigned short premax, const PrepGeom& g) {
+  float v = (float)raw;
+  if (raw == premax) v = g.far;
+  if (v == 0.0f) v = g.far;
+  if (v >= g.far) v = g.far;
+  if (v <= g.near) v = g.near;
+  v = v - g.comz;
+#ifdef __HIP_DEVICE_COMPILE__
+  return __fdiv_rn(v, g.halfz);
+#else
+  return v / g.halfz;
+#endif
+}
+
+// ---- preprocess.depth_to_pcl for one pixel of the normalised crop: false = background; else the cube-normalised point clipped to [-1, 1]
+struct PclGeom {
+  double scale, m02, m12, fx, fy, fu, fv, cx, cy, cz, hx, hy, hz, cube2;
+};
+__host__ __device__ inline bool prep_point(float a, int row, int col, const PclGeom& g, float* out) {
+  const bool mask = fabs((double)a - 1.0) <= (1e-8 + 1e-5 * 1.0) || a == 1.0f;  // np.isclose(img, 1)
+  double dpt = (double)a * g.cube2 / 2.0 + g.cz;
+  if (mask) dpt = 0.0;
+  if (fabs(dpt) <= 1e-8) return false;  // np.isclose(dpt, 0)
+  const double px = ((double)col + 0.5 - g.m02) / g.scale, py = ((double)row + 0.5 - g.m12) / g.scale;  // M^-1 (pixel centre)
+  const double x = (px - g.fu) / g.fx * dpt, y = (py - g.fv) / g.fy * dpt;
+  const double nx = (x - g.cx) / g.hx, ny = (y - g.cy) / g.hy, nz = (dpt - g.cz) / g.hz;
+  out[0] = (float)fmin(fmax(nx, -1.0), 1.0);
+  out[1] = (float)fmin(fmax(ny, -1.0), 1.0);
+  out[2] = (float)fmin(fmax(nz, -1.0), 1.0);
+  return true;
+}
+
+// ---- sampling keys: 36 hash bits | 14 bits candidate | 14 bits pixel.  Distinct ids give distinct elements, so the sorted order is one total order whatever
+// network sorts it; the payload rides in the low bits.
+__host__ __device__ inline unsigned prep_seed_base(long long seed) {
+  return hash32((unsigned)(unsigned long long)seed ^ hash32((unsigned)((unsigned long long)seed >> 32) + 0x9e3779b9U));
+}
+__host__ __device__ inline unsigned long long prep_key(unsigned base, unsigned id, unsigned salt, unsigned cand, unsigned pix) {
+  const unsigned h1 = hash32(base ^ hash32(id * 0x85ebca6bU + salt));
+  const unsigned h2 = hash32(h1 + 0x68bc21ebU + id);
+  return ((unsigned long long)h1 << 32) | ((unsigned long long)(h2 & 15u) << 28) | (unsigned long long)(cand << 14) | (unsigned long long)pix;
+}
+
+#ifdef __HIPCC__
+// tuning aid: wall-clock stamps (100 MHz) of every workgroup's thread 0 at phase boundaries, [B][8] slots set by kpf_prep_set_stamps (NULL = off, the default):
+// crop 0 start, 1 geometry published, 2 gather done, 3 end; sample 4 start, 5 candidates compacted and keyed, 6 sorted, 7 end
+__device__ unsigned long long* kpf_prep_stamps = nullptr;
+#define PREP_STAMP(i)                                                                                     \
+  do {                                                                                                    \
+    if (kpf_prep_stamps && threadIdx.x == 0) kpf_prep_stamps[8 * blockIdx.x + (i)] = wall_clock64();      \
+  } while (0)
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
+                                                            const double* __restrict__ bbox, const double* __restrict__ cam, const double* __restrict__ cube,
+                                                            int Hs, int Ws, int ox, int oy, int H, int W, int S, float* __restrict__ img,
+                                                            float* __restrict__ img_rgb, float* __restrict__ center, float* __restrict__ M,
+                                                            float* __restrict__ cube_out, float* __restrict__ cam_out, double* __restrict__ com,
+                                                            int* __restrict__ bounds, double* __restrict__ Md) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(smem);            // [4][PREP_NW]
+  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + 4 * PREP_NW * 8);               // 512: 16-byte aligned
+  unsigned* wmax = reinterpret_cast<unsigned*>(smem + 4 * PREP_NW * 8 + 256);       // [PREP_NW]
+  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + 4 * PREP_NW * 8 + 256 + PREP_NW * 4);  // [S * S]
+  static_assert(sizeof(PrepGeom) <= 256, "PrepGeom outgrew its LDS slot");
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const unsigned short* dep = depth + (size_t)b * Hs * Ws;
+  const unsigned char* col = rgb + (size_t)b * Hs * Ws * 3;
+  const double* bb = bbox + 4 * b;
+
+  // 1. centre of mass over the box: pixels outside the stored window read as 0, which is invalid depth, so only the intersection is visited
+  PREP_STAMP(0);
+  const PrepBox bx = prep_box(bb, H, W);
+  const int wx0 = max(bx.x0, ox), wx1 = min(bx.x1, ox + Ws), wy0 = max(bx.y0, oy), wy1 = min(bx.y1, oy + Hs);
+  const int bw = max(wx1 - wx0, 0), bh = max(wy1 - wy0, 0);
+  unsigned long long cnt = 0, sx = 0, sy = 0, sd = 0;
+  for (int y = wy0 + wv; y < wy0 + bh; y += PREP_NW)  // one wave per row: coalesced 128-byte reads
+    for (int x = wx0 + lane; x < wx0 + bw; x += 64) {
+      const unsigned v = dep[(size_t)(y - oy) * Ws + (x - ox)];
+      if (v >= 171u && v <= 1500u) {
+        cnt += 1;
+        sx += (unsigned)(x - bx.x0);
+        sy += (unsigned)(y - bx.y0);
+        sd += v;
+      }
+    }
+  cnt = wave_sum_u64(cnt);
+  sx = wave_sum_u64(sx);
+  sy = wave_sum_u64(sy);
+  sd = wave_sum_u64(sd);
+  if (lane == 0) {
+    red[0 * PREP_NW + wv] = cnt;
+    red[1 * PREP_NW + wv] = sx;
+    red[2 * PREP_NW + wv] = sy;
+    red[3 * PREP_NW + wv] = sd;
+  }
+  __syncthreads();
+  // 2. one lane finishes in double and publishes the geometry
+  if (t == 0) {
+    unsigned long long a[4] = {0, 0, 0, 0};
+    for (int q = 0; q < 4; ++q)
+      for (int w = 0; w < PREP_NW; ++w) a[q] += red[q * PREP_NW + w];
+    PrepGeom g;
+    prep_geom(a[0], a[1], a[2], a[3], bx, bb, cam + 4 * b, cube + 3 * b, S, g);
+    *gs = g;
+    for (int k = 0; k < 3; ++k) {
+      center[3 * b + k] = g.center[k];
+      com[3 * b + k] = g.com[k];
+      cube_out[3 * b + k] = (float)cube[3 * b + k];
+    }
+    for (int k = 0; k < 4; ++k) cam_out[4 * b + k] = (float)cam[4 * b + k];
+    const double m[9] = {g.scale, 0.0, g.m02, 0.0, g.scale, g.m12, 0.0, 0.0, 1.0};
+    for (int k = 0; k < 9; ++k) {
+      Md[9 * b + k] = m[k];
+      M[9 * b + k] = (float)m[k];
+    }
+    int* bo = bounds + 6 * b;
+    bo[0] = g.xs;
+    bo[1] = g.xe;
+    bo[2] = g.ys;
+    bo[3] = g.ye;
+    bo[4] = g.szw;
+    bo[5] = g.szh;
+  }
+  __syncthreads();
+  const PrepGeom g = *gs;
+  PREP_STAMP(1);
+
+  // 3. gather: z-clamped depth into LDS (its maximum decides the far plane), RGB straight out
+  const int P = S * S;
+  unsigned mx = 0;
+  for (int p = t; p < P; p += PREP_NT) {
+    const int oyp = p / S, oxp = p - oyp * S;
+    int fy, fx;
+    unsigned short v = 0;
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+    if (prep_source(g, oyp, oxp, fy, fx) && fy >= 0 && fy < H && fx >= 0 && fx < W) {
+      const int wy = fy - oy, wx = fx - ox;
+      if (wy >= 0 && wy < Hs && wx >= 0 && wx < Ws) {
+        const size_t s = (size_t)wy * Ws + wx;
+        v = prep_zclamp(dep[s], g);
+        c0 = (float)col[3 * s];
+        c1 = (float)col[3 * s + 1];
+        c2 = (float)col[3 * s + 2];
+      }
+    }
+    crop[p] = v;
+    mx = max(mx, (unsigned)v);
+    float* o = img_rgb + (size_t)b * 3 * P + p;
+    o[0] = __fdiv_rn(c0, 255.0f);
+    o[P] = __fdiv_rn(c1, 255.0f);
+    o[2 * (size_t)P] = __fdiv_rn(c2, 255.0f);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+  if (lane == 0) wmax[wv] = mx;
+  __syncthreads();
+  PREP_STAMP(2);
+  unsigned premax = 0;
+  for (int w = 0; w < PREP_NW; ++w) premax = max(premax, wmax[w]);
+  // 4. normalize_depth
+  for (int p = t; p < P; p += PREP_NT) img[(size_t)b * P + p] = prep_normalize(crop[p], (unsigned short)premax, g);
+  PREP_STAMP(3);
+}
+
+// Sorts a[0, P2) ascending (P2 a power of two), all PREP_NT threads of the workgroup; ends with a barrier.
+__device__ __forceinline__ void prep_bitonic_sort(unsigned long long* a, int P2) {
+  const int t = threadIdx.x;
+  for (int k = 2; k <= P2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = t; p < (P2 >> 1); p += PREP_NT) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), x = i | j;
+        const unsigned long long u = a[i], v = a[x];
+        if ((u > v) == ((i & k) == 0)) {
+          a[i] = v;
+          a[x] = u;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+__device__ __forceinline__ int prep_pow2ceil(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+__global__ __launch_bounds__(PREP_NT) void prep_pcl_kernel(const float* __restrict__ img, const float* __restrict__ center, const double* __restrict__ Md,
+                                                           const double* __restrict__ cube, const double* __restrict__ cam, const long long* __restrict__ seed, int S,
+                                                           int n, int cap1, float* __restrict__ pcl, int* __restrict__ pcl_index, int* __restrict__ pcl_count,
+                                                           float* __restrict__ cand_pts) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);  // [cap1]: one element per candidate
+  unsigned long long* pick = keys + cap1;                                  // [pow2ceil(n)]: the n output slots when the cloud is tiled
+  int* wsum = reinterpret_cast<int*>(pick + prep_pow2ceil(n));             // [PREP_NW] wave totals, [PREP_NW]: number of keys kept by the pre-filter
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6, P = S * S;
+  const float* im = img + (size_t)b * P;
+  PclGeom g;
+  g.scale = Md[9 * b];
+  g.m02 = Md[9 * b + 2];
+  g.m12 = Md[9 * b + 5];
+  g.fx = cam[4 * b];
+  g.fy = cam[4 * b + 1];
+  g.fu = cam[4 * b + 2];
+  g.fv = cam[4 * b + 3];
+  g.cx = (double)center[3 * b];
+  g.cy = (double)center[3 * b + 1];
+  g.cz = (double)center[3 * b + 2];
+  g.cube2 = cube[3 * b + 2];
+  g.hx = cube[3 * b] / 2.0;
+  g.hy = cube[3 * b + 1] / 2.0;
+  g.hz = cube[3 * b + 2] / 2.0;
+  const unsigned base = prep_seed_base(seed[b]);
+  PREP_STAMP(4);
+
+  // 1. compaction in row-major order (np.where): thread t owns pixels [t * per, (t + 1) * per)
+  const int per = (P + PREP_NT - 1) / PREP_NT, p0 = min(t * per, P), p1 = min(p0 + per, P);
+  float pt[3];
+  int mine = 0;
+  for (int p = p0; p < p1; ++p) mine += prep_point(im[p], p / S, p % S, g, pt) ? 1 : 0;
+  int inc = mine;  // inclusive scan over the wave, then over the waves
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += up;
+  }
+  if (lane == 63) wsum[wv] = inc;
+  if (t == 0) wsum[PREP_NW] = 0;
+  __syncthreads();
+  int before = inc - mine, N = 0;
+  for (int w = 0; w < PREP_NW; ++w) {
+    const int s = wsum[w];
+    if (w < wv) before += s;
+    N += s;
+  }
+  // Only the n smallest keys are wanted.  With N > 2 n candidates, keep the keys under a threshold that 1.5 n of them are expected to pass (hash bits are
+  // uniform: 1.5 n +- sqrt(1.5 n), so between n and 2 n) and sort those: the same n smallest in the same order, from a sort over 2 n elements instead of up
+  // to 16 384 (in-kernel stamps: the sort was 146 of the 190 us of a full crop).  Fewer than n pass (never observed): every key is written and sorted.
+  const bool filt = N > 2 * n;
+  const unsigned long long thr = filt ? ((3ull * (unsigned long long)n) << 35) / (unsigned long long)N : 0ull;
+  int cand = before;
+  for (int p = p0; p < p1; ++p)
+    if (prep_point(im[p], p / S, p % S, g, pt)) {
+      const unsigned long long key = prep_key(base, (unsigned)cand, 0x243f6a88U, (unsigned)cand, (unsigned)p);
+      if (!filt)
+        keys[cand] = key;
+      else if ((key >> 28) < thr)
+        keys[atomicAdd(&wsum[PREP_NW], 1)] = key;  // (any order: the sort follows)
+      if (cand_pts) {
+        float* o = cand_pts + ((size_t)b * P + cand) * 3;
+        o[0] = pt[0];
+        o[1] = pt[1];
+        o[2] = pt[2];
+      }
+      ++cand;
+    }
+  if (t == 0) pcl_count[b] = N;
+  float* out = pcl + (size_t)b * n * 3;
+  int* oidx = pcl_index + (size_t)b * n;
+  if (N == 0) {  // (N is the same in every thread: the branches below are workgroup-uniform)
+    for (int i = t; i < n; i += PREP_NT) {
+      out[3 * i] = out[3 * i + 1] = out[3 * i + 2] = 0.f;
+      oidx[i] = -1;
+    }
+    PREP_STAMP(5);
+    PREP_STAMP(6);
+    PREP_STAMP(7);
+    return;
+  }
+  int K = N;  // keys to sort
+  if (filt) {
+    __syncthreads();
+    K = wsum[PREP_NW];
+    if (K < n) {  // (workgroup-uniform) the threshold kept too few: all keys
+      cand = before;
+      for (int p = p0; p < p1; ++p)
+        if (prep_point(im[p], p / S, p % S, g, pt)) {
+          keys[cand] = prep_key(base, (unsigned)cand, 0x243f6a88U, (unsigned)cand, (unsigned)p);
+          ++cand;
+        }
+      K = N;
+    }
+  }
+  const int P1 = prep_pow2ceil(K);
+  for (int i = K + t; i < P1; i += PREP_NT) keys[i] = ~0ull;
+  __syncthreads();
+  PREP_STAMP(5);
+  const unsigned long long* src = keys;
+  if (N >= n) {
+    // 2a. n of N without replacement in random order: the n smallest keys, in key order
+    prep_bitonic_sort(keys, P1);
+  } else {
+    // 2b. sample_points' multiset: every candidate floor(n / N) times, n mod N distinct ones (the smallest keys) once more, then all n slots shuffled
+    const int q = n / N, r = n - q * N;
+    if (r > 0) prep_bitonic_sort(keys, P1);
+    const int P2 = prep_pow2ceil(n);
+    for (int i = t; i < P2; i += PREP_NT) {
+      unsigned long long e = ~0ull;
+      if (i < n) {
+        const int copy = i < q * N ? i / N : q, j = i < q * N ? i - copy * N : i - q * N;  // j: position in keys (tiled part: all of them; extras: the first r)
+        const unsigned pay = (unsigned)(keys[j] & 0xfffffffull), c = pay >> 14;
+        e = prep_key(base, (unsigned)(copy * N) + c, 0x85a308d3U, c, pay & 0x3fffu);
+      }
+      pick[i] = e;
+    }
+    __syncthreads();
+    prep_bitonic_sort(pick, P2);
+    src = pick;
+  }
+  PREP_STAMP(6);
+  // 3. the points of the chosen candidates
+  for (int i = t; i < n; i += PREP_NT) {
+    const unsigned pay = (unsigned)(src[i] & 0xfffffffull);
+    const int c = (int)(pay >> 14), p = (int)(pay & 0x3fffu);
+    prep_point(im[p], p / S, p % S, g, pt);
+    out[3 * i] = pt[0];
+    out[3 * i + 1] = pt[1];
+    out[3 * i + 2] = pt[2];
+    oidx[i] = c;
+  }
+  PREP_STAMP(7);
+}
+
+// project_to_crop + uncrop_points, one thread per joint, double inside
+__global__ __launch_bounds__(256) void prep_uncrop_kernel(const float* __restrict__ joints, const float* __restrict__ center, const float* __restrict__ M,
+                                                          const float* __restrict__ cube, const float* __restrict__ cam, int B, int J, float* __restrict__ crop_px,
+                                                          float* __restrict__ frame_px) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * J) return;
+  const int b = e / J;
+  double m[9];
+  for (int k = 0; k < 9; ++k) m[k] = (double)M[9 * b + k];
+  const double x = (double)joints[3 * e] * ((double)cube[3 * b] / 2.0) + (double)center[3 * b];
+  const double y = (double)joints[3 * e + 1] * ((double)cube[3 * b + 1] / 2.0) + (double)center[3 * b + 1];
+  const double z = (double)joints[3 * e + 2] * ((double)cube[3 * b + 2] / 2.0) + (double)center[3 * b + 2];
+  const double u = x * (double)cam[4 * b] / z + (double)cam[4 * b + 2], v = y * (double)cam[4 * b + 1] / z + (double)cam[4 * b + 3];
+  const double cu = u * m[0] + v * m[1] + m[2], cv = u * m[3] + v * m[4] + m[5];
+  crop_px[3 * e] = (float)cu;
+  crop_px[3 * e + 1] = (float)cv;
+  crop_px[3 * e + 2] = (float)z;
+  // M^-1 by cofactors (the host takes LAPACK's inverse: a few 1e-16 relative apart on these affine matrices)
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[2] * m[7] - m[1] * m[8], c02 = m[1] * m[5] - m[2] * m[4];
+  const double c10 = m[5] * m[6] - m[3] * m[8], c11 = m[0] * m[8] - m[2] * m[6], c12 = m[2] * m[3] - m[0] * m[5];
+  const double c20 = m[3] * m[7] - m[4] * m[6], c21 = m[1] * m[6] - m[0] * m[7], c22 = m[0] * m[4] - m[1] * m[3];
+  const double det = m[0] * c00 + m[1] * c10 + m[2] * c20;
+  const double h0 = (cu * c00 + cv * c01 + c02) / det, h1 = (cu * c10 + cv * c11 + c12) / det, h2 = (cu * c20 + cv * c21 + c22) / det;
+  frame_px[3 * e] = (float)(h0 / h2);
+  frame_px[3 * e + 1] = (float)(h1 / h2);
+  frame_px[3 * e + 2] = (float)z;
+}
+#endif  // __HIPCC__
+
+constexpr size_t kCropFixedLds = 4 * PREP_NW * 8 + 256 + PREP_NW * 4;
+inline int host_pow2ceil(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+}  // namespace
+
+#define ST(s) reinterpret_cast<hipStream_t>(s)
+
+extern "C" int kpf_prep_crop_u16(const unsigned char* rgb, const unsigned short* depth, const double* bbox, const double* cam, const double* cube, int B,
+                                 int Hs, int Ws, int x0, int y0, int H, int W, int S, float* img, float* img_rgb, float* center, float* M, float* cube_out,
+                                 float* cam_para, double* com, int* bounds, double* M64, void* stream) {
+  KPF_REQUIRE(rgb && depth && bbox && cam && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64,
+              "kpf_prep_crop_u16: null pointer argument");
+  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "kpf_prep_crop_u16: bad shape (B %d, window %d x %d, frame %d x %d)", B, Hs, Ws, H, W);
+  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "kpf_prep_crop_u16: the %d x %d window at (%d, %d) leaves the %d x %d frame", Ws, Hs, x0, y0, W, H);
+  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "kpf_prep_crop_u16: window of %d x %d pixels is too large", Hs, Ws);
+  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "kpf_prep_crop_u16: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", S, PREP_MAX_PIX);
+  const size_t lds = kCropFixedLds + (size_t)S * S * 2;
+  hipLaunchKernelGGL(prep_crop_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, bbox, cam, cube, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M,
+                     cube_out, cam_para, com, bounds, M64);
+  return kpf_check_launch("kpf_prep_crop_u16");
+}
+
+extern "C" int kpf_prep_pcl_sample(const float* img, const float* center, const double* M64, const double* cube, const double* cam, const long long* seed,
+                                   int B, int S, int n, float* pcl, int* pcl_index, int* pcl_count, float* cand_pts, void* stream) {
+  KPF_REQUIRE(img && center && M64 && cube && cam && seed && pcl && pcl_index && pcl_count, "kpf_prep_pcl_sample: null pointer argument");
+  KPF_REQUIRE(B > 0, "kpf_prep_pcl_sample: B = %d", B);
+  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "kpf_prep_pcl_sample: S = %d unsupported (S * S <= %d: one 8-byte sort element per pixel in LDS)", S, PREP_MAX_PIX);
+  KPF_REQUIRE(n > 0 && n <= S * S, "kpf_prep_pcl_sample: n = %d samples of at most S * S = %d pixels", n, S * S);
+  const int cap1 = host_pow2ceil(S * S);
+  const size_t lds = ((size_t)cap1 + host_pow2ceil(n)) * 8 + 2 * PREP_NW * 4;
+  KPF_REQUIRE(lds <= 160 * 1024, "kpf_prep_pcl_sample: S = %d with n = %d needs %zu bytes of LDS (160 KiB per workgroup)", S, n, lds);
+  static std::atomic<bool> raised[KPF_MAX_DEVICES];
+  if (lds > 64 * 1024)
+    KPF_REQUIRE(kpf_raise_lds_limit(reinterpret_cast<const void*>(prep_pcl_kernel), raised), "kpf_prep_pcl_sample: cannot raise the dynamic LDS limit");
+  hipLaunchKernelGGL(prep_pcl_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), img, center, M64, cube, cam, seed, S, n, cap1, pcl, pcl_index, pcl_count, cand_pts);
+  return kpf_check_launch("kpf_prep_pcl_sample");
+}
+
+extern "C" int kpf_prep_uncrop_f32(const float* joints, const float* center, const float* M, const float* cube, const float* cam, int B, int J, float* crop_px,
+                                   float* frame_px, void* stream) {
+  KPF_REQUIRE(joints && center && M && cube && cam && crop_px && frame_px, "kpf_prep_uncrop_f32: null pointer argument");
+  KPF_REQUIRE(B > 0 && J > 0 && (long)B * J < (1L << 30), "kpf_prep_uncrop_f32: bad shape (B %d, J %d)", B, J);
+  hipLaunchKernelGGL(prep_uncrop_kernel, dim3((B * J + 255) / 256), dim3(256), 0, ST(stream), joints, center, M, cube, cam, B, J, crop_px, frame_px);
+  return kpf_check_launch("kpf_prep_uncrop_f32");
+}
+
+/* tuning aid: [B][8] 8-byte stamp slots in device memory for the next launches (NULL switches the stamps off) */
+extern "C" int kpf_prep_set_stamps(void* p) {
+  unsigned long long* q = reinterpret_cast<unsigned long long*>(p);
+  if (hipMemcpyToSymbol(HIP_SYMBOL(kpf_prep_stamps), &q, sizeof(q)) != hipSuccess) {
+    kpf_set_error("kpf_prep_set_stamps: cannot set the device symbol");
+    return KPF_ELAUNCH;
+  }
+  return KPF_OK;
+}

@@ -1024,15 +1024,6 @@ constexpr int AT_T = 21, AT_HD = 32;
 constexpr int AT_NT = 256;  // threads per (sample, head): every phase is a loop over 441 or 672 independent outputs, each computed by ONE thread in the same
                             // sequential order whatever the thread count (round 4: 64 -> 256 threads; the kernels are latency chains of five phases)
 
-__device__ __forceinline__ unsigned hash32(unsigned x) {  // "lowbias32" integer hash: full avalanche in three multiplies
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-
 __global__ __launch_bounds__(AT_NT) void attn21_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, float* __restrict__ ctx,
                                                         float* __restrict__ P, unsigned char* __restrict__ M, int H, int ld, float scale, float p_drop,
                                                         const long* __restrict__ rng, int call_id, int ldc) {

@@ -66,14 +66,6 @@ __device__ int kpf_trs_dbg = 0;  // tuning aid (kpf_tr_stack_set_stamps' second 
 __device__ __forceinline__ int swz(int row) { return (row ^ (row >> 2)) & 15; }
 __device__ __forceinline__ void BAR() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__device__ __forceinline__ unsigned hash32(unsigned x) {  // "lowbias32" (kpf_train.hip)
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
 struct Drop {
   unsigned base, thr;
   float ks;

@@ -1,0 +1,143 @@
+"""Device-side RGB-D preprocessing: frames and bounding boxes in, the model's seven inputs out, joints back to frame pixels.
+
+The batched, graph-capturable form of `preprocess.prepare_rgbd` (which stays the yardstick: tests/test_preprocess_gpu.py pins this path to it) on the three
+kpf_prep_* entry points of libkpf_hip.so (keypointfusion_amd/csrc/kpf_prep.hip).  No host synchronisation and no allocation per call: the outputs of one
+`(B, Hs, Ws)` are preallocated and reused, every input is a device tensor (so a captured graph picks up new frames, boxes and seeds), and the launches go
+to the current stream.
+
+    pre = DevicePreprocessor(img_size=128, sample_num=1024)
+    prep = pre.prepare(rgb_u8, depth_u16, bbox, cam, seed)             # [B][H][W][3] uint8, [B][H][W] uint16, [B][4] f64, [B][4] f64, [B] int64
+    res, sws, _ = plan.forward(*[prep[k] for k in MODEL_INPUTS], 0.8, 128, 1)
+    crop_px, frame_px = pre.uncrop(res[5], prep)                       # joints in crop pixels and in frame pixels
+
+A frame may be uploaded as a window: `origin=(x0, y0), frame_size=(H, W)` says where the stored [Hs][Ws] image sits in the camera frame; pixels outside
+it read as zero.  The point sample is drawn from a counter hash of (seed[b], candidate) and is not numpy's RandomState stream: it has the same
+distribution (n candidates without replacement in random order; a cloud smaller than n tiled first), see kpf_prep_pcl_sample in include/kpf.h.
+"""
+import torch
+
+from . import lib
+
+MODEL_INPUTS = ("img_rgb", "img", "pcl", "center", "M", "cube", "cam_para")  # the argument order of KPFusion.forward / plan.forward
+MAX_PIXELS = 16384  # img_size ** 2: one 8-byte sort element per pixel in the 160-KiB LDS of a CU (kpf_prep_pcl_sample)
+
+
+def _pow2ceil(v):
+    return 1 << max(int(v) - 1, 0).bit_length()
+
+
+class DevicePreprocessor:
+    def __init__(self, img_size=128, sample_num=1024, cube=(250.0, 250.0, 250.0), debug_candidates=False):
+        """debug_candidates: prepare() also returns `candidates` [B][img_size**2][3], every foreground point at its candidate index (rows >= pcl_count
+        are not written) — what `pcl_index` points into; for tests and debugging."""
+        self.img_size, self.sample_num = int(img_size), int(sample_num)
+        if not 0 < self.img_size ** 2 <= MAX_PIXELS:
+            raise ValueError("DevicePreprocessor: img_size %d unsupported (img_size ** 2 <= %d)" % (self.img_size, MAX_PIXELS))
+        if not 0 < self.sample_num <= self.img_size ** 2:
+            raise ValueError("DevicePreprocessor: sample_num %d of at most img_size ** 2 = %d pixels" % (self.sample_num, self.img_size ** 2))
+        if (_pow2ceil(self.img_size ** 2) + _pow2ceil(self.sample_num)) * 8 + 128 > 160 * 1024:
+            raise ValueError("DevicePreprocessor: img_size %d with sample_num %d exceeds the LDS of a compute unit" % (self.img_size, self.sample_num))
+        self.cube = tuple(float(c) for c in cube)
+        if len(self.cube) != 3 or min(self.cube) <= 0:
+            raise ValueError("DevicePreprocessor: cube is three positive sizes in mm")
+        self.debug_candidates = bool(debug_candidates)
+        self._bufs = {}
+
+    # -- argument checks: nothing here touches a device
+    @staticmethod
+    def check_inputs(rgb, depth, bbox, cam, seed, origin=None, frame_size=None):
+        """Validates one batch and returns (B, Hs, Ws, x0, y0, H, W).  Raises TypeError / ValueError with the reason."""
+        for name, t in (("rgb", rgb), ("depth", depth), ("bbox", bbox), ("cam", cam), ("seed", seed)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("DevicePreprocessor.prepare: %s must be a torch tensor on the GPU (got %s)" % (name, type(t).__name__))
+        if depth.dtype != torch.uint16:
+            raise TypeError("DevicePreprocessor.prepare: depth must be torch.uint16 millimetres (got %s); the host path's z-clamp for float depth differs "
+                            "and is not reproduced here: use preprocess.prepare_rgbd for float depth" % depth.dtype)
+        if rgb.dtype != torch.uint8:
+            raise TypeError("DevicePreprocessor.prepare: rgb must be torch.uint8 (got %s)" % rgb.dtype)
+        if depth.dim() != 3:
+            raise ValueError("DevicePreprocessor.prepare: depth must be [B][Hs][Ws] (got %s)" % (tuple(depth.shape),))
+        B, Hs, Ws = (int(v) for v in depth.shape)
+        if B < 1 or Hs < 1 or Ws < 1:
+            raise ValueError("DevicePreprocessor.prepare: empty depth %s" % (tuple(depth.shape),))
+        if tuple(rgb.shape) != (B, Hs, Ws, 3):
+            raise ValueError("DevicePreprocessor.prepare: rgb %s does not match depth %s (expected [B][Hs][Ws][3])" % (tuple(rgb.shape), tuple(depth.shape)))
+        for name, t, shape, dt in (("bbox", bbox, (B, 4), torch.float64), ("cam", cam, (B, 4), torch.float64), ("seed", seed, (B,), torch.int64)):
+            if tuple(t.shape) != shape:
+                raise ValueError("DevicePreprocessor.prepare: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            if t.dtype != dt:
+                raise TypeError("DevicePreprocessor.prepare: %s must be %s (got %s)" % (name, dt, t.dtype))
+        if (origin is None) != (frame_size is None):
+            raise ValueError("DevicePreprocessor.prepare: origin=(x0, y0) and frame_size=(H, W) go together")
+        x0, y0 = (0, 0) if origin is None else (int(origin[0]), int(origin[1]))
+        H, W = (Hs, Ws) if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
+        if x0 < 0 or y0 < 0 or x0 + Ws > W or y0 + Hs > H:
+            raise ValueError("DevicePreprocessor.prepare: the %d x %d window at (%d, %d) leaves the %d x %d frame" % (Ws, Hs, x0, y0, W, H))
+        return B, Hs, Ws, x0, y0, H, W
+
+    def _buffers(self, dev, B, Hs, Ws):
+        key = (dev, B, Hs, Ws)
+        b = self._bufs.get(key)
+        if b is None:
+            S, n = self.img_size, self.sample_num
+            f32 = dict(device=dev, dtype=torch.float32)
+            b = dict(img_rgb=torch.zeros(B, 3, S, S, **f32), img=torch.zeros(B, 1, S, S, **f32), pcl=torch.zeros(B, n, 3, **f32), center=torch.zeros(B, 3, **f32),
+                     M=torch.zeros(B, 3, 3, **f32), cube=torch.zeros(B, 3, **f32), cam_para=torch.zeros(B, 4, **f32),
+                     pcl_index=torch.zeros(B, n, device=dev, dtype=torch.int32), pcl_count=torch.zeros(B, device=dev, dtype=torch.int32),
+                     com=torch.zeros(B, 3, device=dev, dtype=torch.float64), bounds=torch.zeros(B, 6, device=dev, dtype=torch.int32),
+                     M64=torch.zeros(B, 3, 3, device=dev, dtype=torch.float64),
+                     _cube64=torch.tensor([self.cube] * B, device=dev, dtype=torch.float64))
+            if self.debug_candidates:
+                b["candidates"] = torch.zeros(B, S * S, 3, **f32)
+            self._bufs[key] = b
+        return b
+
+    def prepare(self, rgb, depth, bbox, cam, seed, origin=None, frame_size=None):
+        """rgb [B][Hs][Ws][3] uint8, depth [B][Hs][Ws] uint16 (mm), bbox [B][4] float64 (x, y, w, h; x, y the top-left corner), cam [B][4] float64
+        (fx, fy, u0, v0), seed [B] int64: contiguous tensors on one GPU.  Returns a dict of device tensors: the keys of preprocess.prepare_rgbd that the
+        model consumes (MODEL_INPUTS, batched) plus pcl_index [B][n] (candidate index of every sample, -1 for an empty cloud), pcl_count [B], com [B][3]
+        float64, bounds [B][6] int32 (xs, xe, ys, ye, resize width, resize height) and M64 (M before its rounding to float32).  The tensors are this
+        object's buffers for (B, Hs, Ws): the next prepare() of the same shape overwrites them."""
+        B, Hs, Ws, x0, y0, H, W = self.check_inputs(rgb, depth, bbox, cam, seed, origin, frame_size)
+        dev = depth.device
+        for name, t in (("rgb", rgb), ("depth", depth), ("bbox", bbox), ("cam", cam), ("seed", seed)):
+            if t.device.type != "cuda" or t.device != dev:
+                raise RuntimeError("DevicePreprocessor.prepare: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
+                                   "preprocess.prepare_rgbd is the host path)" % (name, t.device))
+            if not t.is_contiguous():
+                raise ValueError("DevicePreprocessor.prepare: %s must be contiguous" % name)
+        l = lib.load()
+        o = self._buffers(dev, B, Hs, Ws)
+        S, n = self.img_size, self.sample_num
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lib.check(l.kpf_prep_crop_u16(rgb.data_ptr(), depth.data_ptr(), bbox.data_ptr(), cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, S,
+                                          o["img"].data_ptr(), o["img_rgb"].data_ptr(), o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(),
+                                          o["cam_para"].data_ptr(), o["com"].data_ptr(), o["bounds"].data_ptr(), o["M64"].data_ptr(), st), "kpf_prep_crop_u16")
+            cand = o["candidates"].data_ptr() if self.debug_candidates else None
+            lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["_cube64"].data_ptr(), cam.data_ptr(),
+                                            seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
+                      "kpf_prep_pcl_sample")
+        return {k: v for k, v in o.items() if not k.startswith("_")}
+
+    def uncrop(self, joints_nl, prep):
+        """joints_nl [B][J][3] float32 normalised to the cube (the model's xyz outputs) + a prepare() result (or any dict with center, M, cube, cam_para)
+        -> (crop_px [B][J][3]: u, v in crop pixels and d in mm; frame_px [B][J][3]: u, v in frame pixels and d in mm).  New tensors."""
+        if not isinstance(joints_nl, torch.Tensor) or joints_nl.dim() != 3 or joints_nl.shape[2] != 3 or joints_nl.dtype != torch.float32:
+            raise ValueError("DevicePreprocessor.uncrop: joints must be a float32 tensor [B][J][3]")
+        B, J = int(joints_nl.shape[0]), int(joints_nl.shape[1])
+        dev = joints_nl.device
+        if dev.type != "cuda":
+            raise RuntimeError("DevicePreprocessor.uncrop: joints are on %s (no CPU fallback: preprocess.project_to_crop / uncrop_points are the host path)" % dev)
+        par = []
+        for k, shape in (("center", (B, 3)), ("M", (B, 3, 3)), ("cube", (B, 3)), ("cam_para", (B, 4))):
+            t = prep[k]
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev:
+                raise ValueError("DevicePreprocessor.uncrop: prep[%r] must be float32 %s on %s" % (k, shape, dev))
+            par.append(t.contiguous())
+        j = joints_nl.contiguous()
+        crop_px, frame_px = torch.empty_like(j), torch.empty_like(j)
+        with torch.cuda.device(dev):
+            lib.check(lib.load().kpf_prep_uncrop_f32(j.data_ptr(), *[t.data_ptr() for t in par], B, J, crop_px.data_ptr(), frame_px.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "kpf_prep_uncrop_f32")
+        return crop_px, frame_px

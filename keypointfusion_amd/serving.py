@@ -97,6 +97,34 @@ class PipelinedEval:
             self._head_done[slot] = ev
         return (res, sws, ev, sb)
 
+    def submit_frames(self, preprocessor, rgb, depth, bbox, cam, seed, loader=None, origin=None, frame_size=None, kernel=0.8):
+        """Frames and boxes in: `preprocess_gpu.DevicePreprocessor.prepare` on the slot's stream in front of the slot's graph(s), then submit().  `preprocessor`
+        gives the crop size, sample count and cube; every slot works on its own copy of it (own output buffers: `depth` batches are in flight).  Returns
+        (ticket for collect(), prep): prep holds this batch's center, M, cube and cam_para (copies, ordered like the results: valid after collect(ticket)) for
+        `preprocessor.uncrop(results[5], prep)`."""
+        from .preprocess_gpu import DevicePreprocessor
+        DevicePreprocessor.check_inputs(rgb, depth, bbox, cam, seed, origin, frame_size)
+        dev = depth.device
+        nstreams = 2 if self.stages else self.depth
+        if self._streams is None or self._streams[0].device != dev:  # (as submit() does)
+            self._streams = [torch.cuda.Stream(device=dev) for _ in range(nstreams)]
+            self._head_done = [None] * self.depth
+        if getattr(self, "_preps", None) is None or self._preps[0] is not preprocessor:
+            self._preps = (preprocessor, [DevicePreprocessor(preprocessor.img_size, preprocessor.sample_num, preprocessor.cube) for _ in range(self.depth)])
+        slot = self._next
+        st = self._streams[0] if self.stages else self._streams[slot]  # the stream the slot's (first) graph replays on
+        cur = torch.cuda.current_stream(dev)
+        st.wait_stream(cur)  # the frames were produced on the caller's stream
+        with torch.cuda.device(dev), torch.cuda.stream(st):
+            for t in (rgb, depth, bbox, cam, seed):
+                t.record_stream(st)
+            prep = self._preps[1][slot].prepare(rgb, depth, bbox, cam, seed, origin, frame_size)
+            keep = {k: prep[k].clone() for k in ("center", "M", "cube", "cam_para")}
+            for t in keep.values():
+                t.record_stream(cur)  # allocated on the slot's stream, consumed on the caller's
+            ticket = self.submit(prep["img_rgb"], prep["img"], prep["pcl"], loader, prep["center"], prep["M"], prep["cube"], prep["cam_para"], kernel)
+        return ticket, keep
+
     def collect(self, ticket):
         """(list of 6 results, list of 2 spatial weights, None) of a submitted batch, ordered after it on the caller's stream."""
         res, sws, ev, st = ticket
