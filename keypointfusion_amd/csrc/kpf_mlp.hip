@@ -15,6 +15,8 @@
 //     (global_load_lds_dwordx4) one chunk ahead; weights are L2-resident (295 KB at C=96).
 //   * LDS images are row-major with the 16-byte chunk index XOR-swizzled per row (on the DMA source address) so that the
 //     ds_read_b128 fragment reads of 16 consecutive rows hit 16 different bank groups.
+// convnext_mlp_kernel below is this design with one tile per workgroup; convnext_mlp_persistent_kernel (the default for fp32 at
+// C = 96 / 128) keeps the dataflow and the arithmetic and removes the per-tile prologue and epilogue (its own comment).
 #include "kpf_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -76,6 +78,16 @@ __device__ __forceinline__ void dma_image(float* lds_dst, const float* src, long
   }
 }
 
+#ifdef KPF_DBG_TIME  // tuning build (make dbg): per-tile stamps of both fp32 MLP kernels, read back by tools/mlp_tile_time.py
+// per tile: [0..3] shader-clock stamps (tile start, chunk loop start, chunk loop end, tile end), [4],[5] 100-MHz real-time stamps at start / end
+__device__ unsigned long long kpf_mlp_dbg_t[8 * 8192];
+#define KPF_MLP_STAMP(tile, i) do { if (threadIdx.x == 0 && (tile) < 8192) { kpf_mlp_dbg_t[8 * (tile) + (i)] = __builtin_readcyclecounter(); \
+    if ((i) == 0) kpf_mlp_dbg_t[8 * (tile) + 4] = __builtin_amdgcn_s_memrealtime(); \
+    if ((i) == 3) kpf_mlp_dbg_t[8 * (tile) + 5] = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#else
+#define KPF_MLP_STAMP(tile, i)
+#endif
+
 template <int NC, int TM, int HT, int NW>
 __global__ __launch_bounds__(64 * NW) void convnext_mlp_kernel(const MlpArgs a) {
   constexpr int NT = 64 * NW;    // NW = 8: two waves per SIMD, so one wave's GELU (VALU) and LDS waits run under its partner's MFMAs
@@ -100,6 +112,7 @@ __global__ __launch_bounds__(64 * NW) void convnext_mlp_kernel(const MlpArgs a) 
   const int fr = lane & 15, fg = lane >> 4;
   const long m0 = (long)blockIdx.x * BM;
   const int valid = (int)((a.M - m0) < BM ? (a.M - m0) : BM);
+  KPF_MLP_STAMP(blockIdx.x, 0);
 
   dma_image<BM, RCY, NT>(Ys, a.y + m0 * C, C, valid, a.zero, tid);
   dma_image<HC, RCY, NT>(W1s, a.w1, C, HC, a.zero, tid);
@@ -122,6 +135,7 @@ __global__ __launch_bounds__(64 * NW) void convnext_mlp_kernel(const MlpArgs a) 
   __syncthreads();
 
   const int yrow0 = wave * TM * 16 + fr;  // this lane's first y row
+  KPF_MLP_STAMP(blockIdx.x, 1);
   for (int ch = 0; ch < NCH; ++ch) {
     const int cur = ch & 1;
     if (ch + 1 < NCH) {  // next chunk's weights fly into the other buffers under this chunk's MFMAs
@@ -182,6 +196,7 @@ __global__ __launch_bounds__(64 * NW) void convnext_mlp_kernel(const MlpArgs a) 
     __syncthreads();  // next chunk's weights landed; everyone is done with the current buffers
   }
 
+  KPF_MLP_STAMP(blockIdx.x, 2);
   // ---- epilogue: out = x + gamma * (acc2 + b2); lane owns channels n*16 + 4*fg .. +3 of pixel row.  `out` may alias `x`, so
   // the compiler will not move a residual load above an earlier store: issue all of a row's residual loads first, then store.
 #pragma unroll
@@ -201,6 +216,171 @@ __global__ __launch_bounds__(64 * NW) void convnext_mlp_kernel(const MlpArgs a) 
       for (int e = 0; e < 4; ++e) v[e] = xv[n][e] + gv[e] * (acc2[n][j][e] + bv[e]);
       *reinterpret_cast<f32x4*>(a.out + m * C + c) = v;
     }
+  }
+  KPF_MLP_STAMP(blockIdx.x, 3);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Persistent form of the kernel above (the default for C = 96 / 128; KPF_MLP_V1=1 selects the one above).  Same arithmetic, lane for
+// lane: every accumulator receives the same MFMA sequence (GEMM1: 16-deep steps ascending, e ascending; GEMM2: hidden tiles ascending
+// across chunks, e ascending), the same gelu_f and the same epilogue expression, so the output is bit-identical and a row's result does
+// not depend on M, on the chunk width or on which workgroup computed it.  What changes is where the time outside the MFMAs goes:
+//   * the grid is min(tiles, CUs x workgroups per CU); a workgroup walks tiles blockIdx.x + i * gridDim.x.  b1 / b2 / gamma go into
+//     LDS once per workgroup, and the weight ring never drains: the last chunk of tile t prefetches chunk 0 of tile t + 1 (the chunk
+//     count is even, so chunk c always lives in buffer c & 1).
+//   * y is not staged in LDS.  Lane (fr, fg) loads its GEMM1 B fragments (16 bytes at row fr, 16-byte chunk 4 s + fg) from global
+//     memory into registers — the layout the LDS read of the kernel above produces — once per tile; the loads for tile t + 1 are
+//     issued in the last chunk of tile t, behind its GEMM1 (the last reader of tile t's fragments).
+//   * the residual rows of tile t are requested at the start of its last chunk, so the epilogue finds them in registers.
+//     `out` may alias `x`: tiles own disjoint rows, and element (row, channel) is read and written by the same lane, read first, so
+//     no early residual load can see another tile's store.  `y` must not alias `out` (tile t + 1's y is read before tile t is stored,
+//     which is harmless, but tile t + 2's is read after).
+//   Rows beyond M repeat row M - 1 (pixels are independent MFMA columns); their results are never stored.
+// ---------------------------------------------------------------------------------------------------------------
+
+template <int NC, int TM, int HT, int NW, int WPE>
+__global__ __launch_bounds__(64 * NW, WPE) void convnext_mlp_persistent_kernel(const MlpArgs a, const int tiles) {
+  constexpr int NT = 64 * NW;
+  constexpr int C = 16 * NC, H4 = 4 * C, HC = 16 * HT;
+  constexpr int BM = 16 * TM * NW;  // pixel rows per tile
+  constexpr int RCY = C / 4, RCW = HC / 4;
+  constexpr int NCH = H4 / HC;
+  constexpr int W1F = HC * C, W2F = C * HC;
+  static_assert(H4 % HC == 0 && NCH % 2 == 0, "an even number of chunks keeps chunk c in buffer c & 1 across tiles");
+
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* W1s = lds;                  // [2][HC][C]
+  float* W2s = W1s + 2 * W1F;        // [2][C][HC]
+  float* B1s = W2s + 2 * W2F;        // [4C], [C], [C]: read from LDS for the reason given in the kernel above
+  float* B2s = B1s + H4;
+  float* Gs = B2s + C;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int row0 = wave * TM * 16 + fr;  // this lane's first row inside a tile
+  const long M = a.M;
+
+  for (int i = tid; i < H4; i += NT) B1s[i] = a.b1[i];
+  for (int i = tid; i < C; i += NT) {
+    B2s[i] = a.b2[i];
+    Gs[i] = a.gamma[i];
+  }
+  dma_image<HC, RCY, NT>(W1s, a.w1, C, HC, a.zero, tid);
+  dma_image<C, RCW, NT>(W2s, a.w2, H4, C, a.zero, tid);
+
+  f32x4 yf[NC][TM];
+  auto load_y = [&](long tile) {
+#pragma unroll
+    for (int j = 0; j < TM; ++j) {
+      long m = tile * BM + row0 + j * 16;
+      m = m < M ? m : M - 1;
+      const float* yr = a.y + m * C + 4 * fg;
+#pragma unroll
+      for (int s = 0; s < NC; ++s) yf[s][j] = *reinterpret_cast<const f32x4*>(yr + 16 * s);
+    }
+  };
+  load_y(blockIdx.x);
+  __syncthreads();
+
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    KPF_MLP_STAMP(tile, 0);
+    const bool more = tile + gridDim.x < tiles;
+    f32x4 acc2[NC][TM], xv[TM][NC];
+#pragma unroll
+    for (int n = 0; n < NC; ++n)
+#pragma unroll
+      for (int j = 0; j < TM; ++j) acc2[n][j] = zero4;
+
+    auto chunk = [&](const int ch, auto LAST) {
+      constexpr bool last = decltype(LAST)::value;
+      const int cur = ch & 1;
+      if (!last || more) {  // the next chunk — of this tile or chunk 0 of the next one — flies into the other buffers under this chunk's MFMAs
+        const int nx = last ? 0 : ch + 1;
+        dma_image<HC, RCY, NT>(W1s + (cur ^ 1) * W1F, a.w1 + (long)nx * HC * C, C, HC, a.zero, tid);
+        dma_image<C, RCW, NT>(W2s + (cur ^ 1) * W2F, a.w2 + (long)nx * HC, H4, C, a.zero, tid);
+      }
+      if constexpr (last) {  // residual rows: in flight under the whole last chunk
+#pragma unroll
+        for (int j = 0; j < TM; ++j) {
+          long m = tile * BM + row0 + j * 16;
+          m = m < M ? m : M - 1;
+#pragma unroll
+          for (int n = 0; n < NC; ++n) xv[j][n] = *reinterpret_cast<const f32x4*>(a.x + m * C + n * 16 + 4 * fg);
+        }
+      }
+      const float* w1b = W1s + cur * W1F;
+      const float* w2b = W2s + cur * W2F;
+
+      // ---- GEMM1: acc1[ht][tm] = W1chunk (HC x C) . y^T ----
+      f32x4 acc1[HT][TM];
+#pragma unroll
+      for (int h = 0; h < HT; ++h)
+#pragma unroll
+        for (int j = 0; j < TM; ++j) acc1[h][j] = zero4;
+#pragma unroll
+      for (int s = 0; s < NC; ++s) {
+        f32x4 wf[HT];
+#pragma unroll
+        for (int h = 0; h < HT; ++h) {
+          const int r = h * 16 + fr;
+          wf[h] = *reinterpret_cast<const f32x4*>(w1b + r * C + (((4 * s + fg) ^ row_sw<RCY>(r)) << 2));
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int h = 0; h < HT; ++h)
+#pragma unroll
+            for (int j = 0; j < TM; ++j) acc1[h][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[h][e], yf[s][j][e], acc1[h][j], 0, 0, 0);
+      }
+      if constexpr (last)
+        if (more) load_y(tile + gridDim.x);  // this tile's fragments are dead: the next tile's arrive under GELU + GEMM2
+
+      // ---- bias + GELU in registers; GEMM2: acc2[n][tm] += W2chunk (C x HC) . h ----
+#pragma unroll
+      for (int h = 0; h < HT; ++h) {
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(B1s + ch * HC + h * 16 + 4 * fg);
+#pragma unroll
+        for (int j = 0; j < TM; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc1[h][j][e] = gelu_f(acc1[h][j][e] + bv[e]);
+        f32x4 wf[NC];
+#pragma unroll
+        for (int n = 0; n < NC; ++n) {
+          const int r = n * 16 + fr;
+          wf[n] = *reinterpret_cast<const f32x4*>(w2b + r * HC + (((4 * h + fg) ^ row_sw<RCW>(r)) << 2));
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int n = 0; n < NC; ++n)
+#pragma unroll
+            for (int j = 0; j < TM; ++j) acc2[n][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[n][e], acc1[h][j][e], acc2[n][j], 0, 0, 0);
+      }
+      __syncthreads();  // the prefetched chunk (and, in the last chunk, x and the next y) landed; everyone is done with the current buffers
+    };
+    KPF_MLP_STAMP(tile, 1);
+    for (int ch = 0; ch < NCH - 1; ++ch) chunk(ch, std::false_type{});
+    chunk(NCH - 1, std::true_type{});
+    KPF_MLP_STAMP(tile, 2);
+
+    // ---- epilogue: out = x + gamma * (acc2 + b2), the residual already in registers ----
+#pragma unroll
+    for (int j = 0; j < TM; ++j) {
+      const long m = tile * BM + row0 + j * 16;
+      if (m >= M) continue;
+#pragma unroll
+      for (int n = 0; n < NC; ++n) {
+        const int c = n * 16 + 4 * fg;
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(B2s + c);
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(Gs + c);
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = xv[j][n][e] + gv[e] * (acc2[n][j][e] + bv[e]);
+        *reinterpret_cast<f32x4*>(a.out + m * C + c) = v;
+      }
+    }
+    KPF_MLP_STAMP(tile, 3);
   }
 }
 
@@ -641,7 +821,52 @@ int launch_mlp(MlpArgs& a, hipStream_t st) {
   return kpf_check_launch("kpf_convnext_mlp_f32");
 }
 
+// CUs of the current device (persistent grid size), looked up once per device
+int mlp_cu_count() {
+  static std::atomic<int> cus[KPF_MAX_DEVICES];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= KPF_MAX_DEVICES) return 0;
+  int n = cus[dev].load(std::memory_order_acquire);
+  if (n > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+  cus[dev].store(n, std::memory_order_release);
+  return n;
+}
+
+// WPC = workgroups the LDS and register budget admit per CU (the build prints both: -Rpass-analysis=kernel-resource-usage)
+template <int NC, int TM, int HT, int NW, int WPC>
+int launch_mlp_persistent(MlpArgs& a, hipStream_t st) {
+  constexpr int C = 16 * NC, HC = 16 * HT, BM = 16 * TM * NW;
+  constexpr int WPE = NW * WPC / 4;  // waves per SIMD the register allocation must leave room for
+  constexpr size_t lds = (size_t)(2 * HC * C + 2 * C * HC + 6 * C) * sizeof(float);
+  static_assert(WPC * lds <= 160 * 1024 && WPE >= 1 && WPE <= 8, "workgroups per CU");
+  auto kern = convnext_mlp_persistent_kernel<NC, TM, HT, NW, WPE>;
+  static std::atomic<bool> lds_opt_in[KPF_MAX_DEVICES];
+  if (!kpf_raise_lds_limit(reinterpret_cast<const void*>(kern), lds_opt_in)) {
+    kpf_set_error("kpf_convnext_mlp_f32: cannot raise the dynamic LDS limit");
+    return KPF_ELAUNCH;
+  }
+  const int cus = mlp_cu_count();
+  if (cus <= 0) {
+    kpf_set_error("kpf_convnext_mlp_f32: cannot read the CU count");
+    return KPF_ELAUNCH;
+  }
+  const long tiles = (a.M + BM - 1) / BM, slots = (long)cus * WPC;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles < slots ? tiles : slots)), dim3(64 * NW), lds, st, a, (int)tiles);
+  return kpf_check_launch("kpf_convnext_mlp_f32");
+}
+
 }  // namespace
+
+#ifdef KPF_DBG_TIME
+extern "C" int kpf_mlp_dbg_read(unsigned long long* host, int n) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(kpf_mlp_dbg_t), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
+}
+extern "C" int kpf_mlp_dbg_clear(void) {
+  static unsigned long long z[8 * 8192];
+  return hipMemcpyToSymbol(HIP_SYMBOL(kpf_mlp_dbg_t), z, sizeof(z)) == hipSuccess ? 0 : -1;
+}
+#endif
 
 // 192 is implemented (4-wave variant: a 128-row y tile does not fit beside the weight ring) but measured slower than the two plain
 // GEMM launches at that width (93 vs 102 TF), so it is not advertised; kpf_convnext_mlp_f32 still accepts it.
@@ -672,6 +897,16 @@ extern "C" int kpf_convnext_mlp_f32(const float* y, const float* x, const float*
     a.zero = zero_of_dev[dev];
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // read per call, not cached: one process can run both kernels (tests compare them bit for bit)
+  const char* v1 = getenv("KPF_MLP_V1");
+  if (!(v1 && atoi(v1) != 0) && C != 192) {
+    // Two pixel tiles per wave (BM 256) need more than 256 VGPRs with y, x and both accumulators in registers (the build spills), and at
+    // C = 96 a 32-wide chunk is not a whole number of 8-wave DMA passes: one form per width.
+    if (C == 96) return launch_mlp_persistent<6, 1, 4, 8, 1>(a, st);  // BM 128, HC 64: 96 KB ring, one workgroup per CU
+    const char* ce = getenv("KPF_MLP_CFG");                           // tuning aid (tools/mlp_bench.py)
+    if (ce && atoi(ce) == 1) return launch_mlp_persistent<8, 1, 2, 8, 1>(a, st);  // C = 128, HC 32: 64 KB ring, 16 chunks (0.618 ms at M = 262144)
+    return launch_mlp_persistent<8, 1, 4, 8, 1>(a, st);               // C = 128: BM 128, HC 64: 128 KB ring, 8 chunks (0.591 ms)
+  }
   switch (C) {
     case 96: return launch_mlp<6, 1, 4, 8>(a, st);    // 8 waves, BM 128, HC 64: 48 + 96 KB LDS
     case 128: return launch_mlp<8, 1, 2, 8>(a, st);   // 8 waves, BM 128, HC 32: 64 + 64 KB
