@@ -213,13 +213,15 @@ int kpf_img2pcl_top4_f32(const float* pcl, const float* depth, const float* cent
 
 /* Point feature gather + pcl_joint2offset (model/model.py:295-309, 503-525): builds the operand rows of the point
  * embedding GEMMs: A1 [B*N][240] = [pf 128 | xyz 3 | pw 21 | unit offsets 63 | closeness 21 | 0 x4], A2 [B*N][128] = pf_rgb.
- * feat_* NHWC [B][P][128]; offset NCHW [B][105][P]. */
+ * feat_* NHWC [B][P][128]; offset NCHW [B][105][P].  B * N % 4 == 0 (a workgroup takes four points; they may belong to two samples);
+ * index values in [0, P). */
 int kpf_point_assemble_f32(const float* feat_d, const float* feat_rgb, const float* offset, const float* pcl,
                            const float* joint_xyz, const float* closeness, const int* index, float* A1, float* A2, int B,
                            int N, int P, float kernel, void* stream);
 
 /* attention = softmax_N(pw), joint_feat = attention @ X (model/model.py:319-320).  X [B*N][128];
- * -> JA [B*21][132] = [joint_feat 128 | joint xyz 3 | 0]. */
+ * -> JA [B*21][132] = [joint_feat 128 | joint xyz 3 | 0].  A1 is the [B*N][240] buffer of kpf_point_assemble_f32, of which only the pw columns 131..151
+ * are read.  N % 4 == 0 and 4 <= N <= 2048 (7 N + 32 floats of LDS sit in front of an array that takes 16-byte stores; N > 1312 opts into > 64 KiB of LDS). */
 int kpf_softmax_pool_f32(const float* A1, const float* X, const float* joint_xyz, float* JA, int B, int N, void* stream);
 
 /* pointnet2_ops ball_query + group_points for the 3 DESA radii (model/model.py:158,171-178): points = cat(pcl, joints),
@@ -228,7 +230,8 @@ int kpf_softmax_pool_f32(const float* A1, const float* X, const float* joint_xyz
 int kpf_ball_group_f32(const float* pcl, const float* joint_xyz, const float* X, const float* JF, int jf_ld, float* G,
                        int* idx_out, int B, int N, float r0, float r1, float r2, void* stream);
 
-/* max over groups of `group` consecutive rows (torch.max(dim=-1), model/model.py:198). */
+/* max over groups of `group` consecutive rows (torch.max(dim=-1), model/model.py:198): in [rows*group][C] -> columns [out_coff, out_coff + C) of
+ * out [rows][out_ld], out_coff + C <= out_ld.  Any C; C % 4 == 0, C <= 1024 with 16-byte aligned rows on both sides takes the float4 kernel (same bits). */
 int kpf_group_max_f32(const float* in, float* out, long rows, int group, int C, int out_ld, int out_coff, void* stream);
 /* The same grouping with the three radii CHANNEL-STACKED (ABI 16; the training step's grouped DESA launches): GF [B*21*64][3*128] grouped feature
  * differences, GX [B*21*64][3*4] offsets / radius (3 + a zero channel) — radius i in columns [128 i, 128 i + 128) / [4 i, 4 i + 4). */
@@ -243,19 +246,22 @@ int kpf_heat_gam_gate_f32(const float* r3d, const float* img_xyz, const float* S
                           const float* Minv, const float* cube, const float* cam, float* sw_out, float* Gw, int B, int F,
                           int img_size, int flip, void* stream);
 
-/* img_feat_j = Gw @ relu(feat) + b (model/model.py:340-344), optional relu((. + prev)/2).  -> out [B][21][128]. */
+/* img_feat_j = Gw @ relu(feat) + b (model/model.py:340-344), optional relu((. + prev)/2).  -> out [B][21][128].
+ * P % 32 == 0 (two pixel halves of 16-pixel MFMA blocks), Gw 16-byte aligned. */
 int kpf_gate_reduce_f32(const float* Gw, const float* feat, const float* bfc, const float* prev, float* out, int B, int P,
                         void* stream);
 
 /* KP_Interaction_TR (model/model.py:106-126): embed + 4 BERT layers + 3-vector heads on 21 tokens, one workgroup per
  * sample.  x [B*21][ldx] (Din used), W = packed weights (keypointfusion_amd/engine.py:pack_tr), -> h [B][21][128],
- * score [B][21][3]; score2 (may be NULL) receives a second copy with row stride score2_ld. */
+ * score [B][21][3]; score2 (may be NULL) receives a second copy with row stride score2_ld.
+ * 0 < Din <= 208 (the [21][Din rounded up to 16] input tokens share the CU's 160 KiB of LDS with the rest of the stack; the model uses 128 and 131),
+ * ldx >= Din; columns [Din, ldx) of x are not read. */
 int kpf_tr_encoder_f32(const float* x, int ldx, int Din, const float* W, float* h, float* score, float* score2,
                        int score2_ld, int B, void* stream);
 int kpf_tr_encoder_weight_floats(int Din);
 
 /* The observable layer of updatedDecoder (model/transfusion_head.py:137-173 with cross_only): query/key [B][21][128]
- * -> out rows [B*21] with stride out_ld at column out_coff. */
+ * -> out rows [B*21] with stride out_ld at column out_coff, out_coff + 128 <= out_ld. */
 int kpf_xattn_layer_f32(const float* query, const float* key, const float* W, float* out, int out_ld, int out_coff, int B,
                         void* stream);
 int kpf_xattn_weight_floats(void);

@@ -781,7 +781,9 @@ extern "C" int kpf_point_assemble_f32(const float* feat_d, const float* feat_rgb
 }
 
 extern "C" int kpf_softmax_pool_f32(const float* A1, const float* X, const float* joint_xyz, float* JA, int B, int N, void* stream) {
-  KPF_REQUIRE(A1 && X && joint_xyz && JA && B > 0 && N > 1 && N % 2 == 0 && N <= 2048, "kpf_softmax_pool_f32: bad arguments");
+  // N % 4: the kernel's LDS is att[7N] | red[32] | part[...] and `part` takes 16-byte stores, so 7N + 32 must be a multiple of 4
+  KPF_REQUIRE(A1 && X && joint_xyz && JA && B > 0 && N > 0 && N % 4 == 0 && N <= 2048,
+              "kpf_softmax_pool_f32: bad arguments (N %% 4 == 0, 4 <= N <= 2048)");
   const size_t lds = (size_t)(7 * N + 32 + 8 * 7 * 128) * sizeof(float);
   static std::atomic<bool> lds_opt_in[KPF_MAX_DEVICES];
   if (lds > 64 * 1024 && !kpf_raise_lds_limit(reinterpret_cast<const void*>(&softmax_pool_kernel), lds_opt_in)) {
@@ -831,7 +833,7 @@ extern "C" int kpf_heat_gam_gate_f32(const float* r3d, const float* img_xyz, con
 
 extern "C" int kpf_gate_reduce_f32(const float* Gw, const float* feat, const float* bfc, const float* prev, float* out, int B, int P,
                                    void* stream) {
-  KPF_REQUIRE(Gw && feat && bfc && out && B > 0 && P % 32 == 0 && kpf_aligned16(Gw), "kpf_gate_reduce_f32: bad arguments (P %% 32 == 0)");
+  KPF_REQUIRE(Gw && feat && bfc && out && B > 0 && P > 0 && P % 32 == 0 && kpf_aligned16(Gw), "kpf_gate_reduce_f32: bad arguments (P %% 32 == 0)");
   hipLaunchKernelGGL(gate_reduce_kernel, dim3(4, B), dim3(256), 0, ST(stream), Gw, feat, bfc, prev, out, P);
   return kpf_check_launch("kpf_gate_reduce_f32");
 }

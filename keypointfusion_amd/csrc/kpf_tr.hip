@@ -349,18 +349,26 @@ __global__ __launch_bounds__(NTHR) void xattn_layer_kernel(const float* __restri
   for (int i = threadIdx.x; i < T * H; i += NTHR) out[((long)b * T + i / H) * ldo + ocoff + (i % H)] = CTX[(i / H) * 132 + (i % H)];
 }
 
+// LDS of tr_encoder_kernel in floats: the input tokens [T][ldi] are the only part that grows with Din.  The CU has 160 KiB, which ends at ldi = 208.
+constexpr size_t enc_lds_floats(int Din) {
+  return (size_t)(21 * ((Din + 15) & ~15) + 21 * 132 * 3 + 21 * 388 + 4 * 21 * 21 + 21 * 20 + 4 + 2 * RING_SLOT + SCHED_FLOATS);
+}
+constexpr int ENC_MAX_DIN = 208;
+static_assert(enc_lds_floats(ENC_MAX_DIN) * sizeof(float) <= 160 * 1024 && enc_lds_floats(ENC_MAX_DIN + 1) * sizeof(float) > 160 * 1024,
+              "ENC_MAX_DIN is the largest embedding depth whose token array fits the 160 KiB of LDS");
+
 }  // namespace
 
 extern "C" int kpf_tr_encoder_f32(const float* x, int ldx, int Din, const float* W, float* h, float* score, float* score2,
                                   int score2_ld, int B, void* stream) {
-  KPF_REQUIRE(x && W && h && score && B > 0 && Din > 0 && Din <= 256 && ldx >= Din, "kpf_tr_encoder_f32: bad arguments");
-  const size_t lds = (size_t)(21 * ((Din + 15) & ~15) + 21 * 132 * 3 + 21 * 388 + 4 * 21 * 21 + 21 * 20 + 4 + 2 * RING_SLOT + SCHED_FLOATS) * sizeof(float);
+  KPF_REQUIRE(x && W && h && score && B > 0 && Din > 0 && Din <= ENC_MAX_DIN && ldx >= Din,
+              "kpf_tr_encoder_f32: bad arguments (0 < Din <= %d, ldx >= Din)", ENC_MAX_DIN);
+  const size_t lds = enc_lds_floats(Din) * sizeof(float);
   static std::atomic<bool> lds_opt_in[KPF_MAX_DEVICES];
   if (!kpf_raise_lds_limit(reinterpret_cast<const void*>(tr_encoder_kernel), lds_opt_in)) {
     kpf_set_error("kpf_tr_encoder_f32: cannot raise the dynamic LDS limit");
     return KPF_ELAUNCH;
   }
-  KPF_REQUIRE(lds <= 160 * 1024, "kpf_tr_encoder_f32: Din=%d needs too much LDS", Din);
   hipLaunchKernelGGL(tr_encoder_kernel, dim3(B), dim3(NTHR), lds, reinterpret_cast<hipStream_t>(stream), x, ldx, Din, W, h, score,
                      score2, score2_ld);
   return kpf_check_launch("kpf_tr_encoder_f32");

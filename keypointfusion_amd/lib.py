@@ -234,6 +234,10 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise KpfError("libkpf_hip.so is not built: run `make -C keypointfusion_amd/csrc` "
                        "(or __graft_entry__.build()); there is no fallback compute path")
+    # torch first: libkpf_hip.so needs libamdhip64.so.7, and the loader gives it the copy that is already mapped under that name.  Loaded before torch,
+    # it would pull in the system's copy and torch then its own: two HIP runtimes in one process, and the launches here go to one that owns no device
+    # ("no ROCm-capable device is detected" at the first launch — build() followed by smoke() in one process)
+    import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, args in _SIGS.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing

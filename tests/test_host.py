@@ -221,3 +221,43 @@ def test_layernorm_fold_rule_depends_on_the_layer_not_on_the_batch():
     assert lib.kpf_conv2d_h16_ln_fold_supported(C.byref(desc(8, 32, 96, 384, L.KPF_ACT_GELU, Kp=128))) == 0     # Cin % 64 != 0 / N % 256 != 0 (ConvNeXt-T stage 1)
     assert lib.kpf_conv2d_h16_ln_fold_supported(C.byref(desc(8, 32, 192, 768, L.KPF_ACT_GELU))) == 0            # Kp % 128 != 0 (stage 2)
     assert lib.kpf_conv2d_h16_ln_fold_supported(C.byref(desc(8, 32, 512, 2048, L.KPF_ACT_GELU, k=3))) == 0      # not a dense 1x1
+
+
+def test_fusion_head_entry_points_refuse_shapes_their_kernels_cannot_take():
+    """KPF_REQUIRE returns before any HIP call, so the refusals of the fusion head's fp32 entry points are checked here, on pointers into a host buffer
+    that nothing dereferences: each returns KPF_EINVAL and leaves a message that names the entry point."""
+    l = L.load()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)  # 16-byte aligned, as kpf_gate_reduce_f32 asks of Gw
+    cases = [
+        ("kpf_softmax_pool_f32", (p, p, p, p, 2, 1022, None)),   # 7 N + 32 floats in front of 16-byte LDS stores: N % 4
+        ("kpf_softmax_pool_f32", (p, p, p, p, 2, 2052, None)),   # N <= 2048
+        ("kpf_softmax_pool_f32", (p, p, p, p, 2, 0, None)),
+        ("kpf_point_assemble_f32", (p, p, p, p, p, p, p, p, p, 3, 1022, 1024, 0.8, None)),  # B * N % 4: four points per workgroup
+        ("kpf_gate_reduce_f32", (p, p, p, None, p, 2, 48, None)),  # P % 32
+        ("kpf_tr_encoder_f32", (p, 128, 0, p, p, p, None, 0, 2, None)),
+        ("kpf_tr_encoder_f32", (p, 256, 209, p, p, p, None, 0, 2, None)),  # the [21][Din] tokens no longer fit the LDS
+        ("kpf_tr_encoder_f32", (p, 256, 256, p, p, p, None, 0, 2, None)),
+        ("kpf_tr_encoder_f32", (p, 260, 257, p, p, p, None, 0, 2, None)),
+        ("kpf_tr_encoder_f32", (p, 127, 128, p, p, p, None, 0, 2, None)),  # ldx < Din
+        ("kpf_xattn_layer_f32", (p, p, p, p, 132, 5, 2, None)),            # out_coff + 128 > out_ld
+        ("kpf_group_max_f32", (p, p, 42, 64, 128, 512, 385, None)),        # out_coff + C > out_ld
+    ]
+    for name, args in cases:
+        assert l.kpf_inv3x3_f32(None, None, 0, 0, None) == -1 and l.kpf_last_error().decode().startswith("kpf_inv3x3_f32:")  # another message in between
+        rc = getattr(l, name)(*args)
+        msg = l.kpf_last_error().decode()
+        assert rc == -1 and msg.startswith(name + ":"), (name, args[-4:], rc, msg)  # KPF_EINVAL of include/kpf.h
+    hdr = open(os.path.join(ROOT, "include", "kpf.h")).read()
+    assert re.search(r"#define KPF_EINVAL \(-1\)", hdr)
+
+
+def test_loading_the_library_before_torch_leaves_one_hip_runtime_in_the_process(tmp_path):
+    """lib.load() in a process that has not imported torch yet (what build() does) must not map a second libamdhip64 beside torch's own: the library's
+    launches would go to a runtime that owns no device."""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r); from keypointfusion_amd import lib; lib.load(); import torch;"
+            "print(len(set(l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l)))") % ROOT
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(tmp_path))
+    assert out.returncode == 0 and out.stdout.strip() == "1", (out.stdout, out.stderr[-2000:])
