@@ -15,6 +15,7 @@ import math
 import torch
 
 from . import lib as L
+from .packs import ConvGeom, Pack, Packed16, PackedConv, split_pack  # noqa: F401 (re-exported: the operand types live in packs.py)
 from .spec import CONVNEXT, parse_net
 
 BN_EPS = 1e-5
@@ -72,8 +73,8 @@ class Act:
         self.split = split  # rows hold [32 x f16 hi | 32 x f16 lo] blocks instead of fp32 (same bytes; include/kpf.h)
 
     @staticmethod
-    def empty(B, H, W, C, device):
-        return Act(torch.empty(B * H * W * C, device=device, dtype=torch.float32), B, H, W, C)
+    def empty(B, H, W, C, device, dtype=torch.float32):
+        return Act(torch.empty(B * H * W * C, device=device, dtype=dtype), B, H, W, C)
 
     def slice(self, coff, C_):
         return Act(self.buf, self.B, self.H, self.W, C_, self.ld, self.coff + coff)
@@ -94,118 +95,37 @@ def bn_scale_shift(sd, p):
     return s, b - m * s
 
 
-def split_pack(w):
-    """fp32/fp64 [N][K] (K % 32 == 0) -> (fp32-viewed [N][K] tensor holding [K/32][hi 32 | lo 32] f16 of w * 2^s, 2^-s): the split
-    operand format of include/kpf.h; s keeps the lo halves out of the f16 subnormals."""
-    w = w.double().cpu()
-    N, K = w.shape
-    assert K % 32 == 0
-    amax = float(w.abs().max())
-    s = 7 - math.floor(math.log2(amax)) if amax > 0 else 0
-    ws = w * (2.0 ** s)
-    hi = ws.half()
-    lo = (ws - hi.double()).half()
-    blk = torch.stack([hi.view(N, K // 32, 32), lo.view(N, K // 32, 32)], 2).contiguous()  # N, K/32, 2, 32
-    return blk.view(torch.float32).reshape(N, K).contiguous(), 2.0 ** (-s)
-
-
 # order in which GEMM1's accumulator registers of two neighbouring 16-wide hidden tiles form a 32-deep f16 MFMA operand
 # (csrc/kpf_mlp.hip, convnext_mlp_split_kernel): k-slot 8g+j holds hidden 16*(j>>2) + 4g + (j&3)
 MLP_HIDDEN_PERM = [16 * ((k & 7) >> 2) + 4 * (k >> 3) + (k & 3) for k in range(32)]
 
 
-class PackedConv:
-    """Weights of one convolution/linear in kernel layout: w [N][Kp] with k = (ky,kx,c), bias [N], optional input
-    prologue (scale, shift) [Cin].  `view_kw` > 1 marks a patchify convolution executed as KHx1 over a merged view."""
-
-    def __init__(self, weight, bias, device, stride=1, pad=0, fold_bn=None, prologue=None, cin_pad=None, patchify=False, n_pad=None):
-        w = weight.detach().double().cpu()
-        if w.dim() == 2:
-            w = w[:, :, None, None]
-        elif w.dim() == 3:
-            w = w[:, :, :, None]
-        N, Cin, KH, KW = w.shape
-        b = bias.detach().double().cpu() if bias is not None else torch.zeros(N, dtype=torch.float64)
-        if fold_bn is not None:  # conv -> BN : W' = W*s, b' = b*s + t
-            s, t = fold_bn
-            w = w * s.cpu()[:, None, None, None]
-            b = b * s.cpu() + t.cpu()
-        if n_pad is not None and n_pad > N:  # extra output channels that are identically zero (zero rows, zero bias)
-            w = torch.cat([w, torch.zeros(n_pad - N, Cin, KH, KW, dtype=w.dtype)], 0)
-            b = torch.cat([b, torch.zeros(n_pad - N, dtype=b.dtype)])
-            N = n_pad
-        if cin_pad is not None and cin_pad > Cin:
-            w = torch.cat([w, torch.zeros(N, cin_pad - Cin, KH, KW, dtype=w.dtype)], 1)
-            Cin = cin_pad
-        w = w.permute(0, 2, 3, 1).contiguous()  # N KH KW Cin
-        if patchify:  # kernel == stride, pad 0: merge (kx, c) into the channel axis of a [H, W/KW, KW*C] view
-            assert stride == KH == KW and pad == 0
-            self.KH, self.KW, self.Cin = KH, 1, KW * Cin
-            self.sh, self.sw, self.ph, self.pw = KH, 1, 0, 0
-            self.merge = KW
-        else:
-            self.KH, self.KW, self.Cin = KH, KW, Cin
-            self.sh = self.sw = stride
-            self.ph = self.pw = pad
-            self.merge = 1
-        assert self.Cin % 4 == 0, "input channels (after view) must be a multiple of 4"
-        K = KH * KW * Cin
-        self.N, self.K = N, K
-        self.Kp = (K + 31) // 32 * 32
-        wp = torch.zeros(N, self.Kp, dtype=torch.float64)
-        wp[:, :K] = w.reshape(N, K)
-        self.w = wp.float().to(device)
-        self.b = b.float().to(device)
-        # split (3 x f16) arithmetic only where the caller has proven |activation| < 65504 at pack time (ConvNeXtBlockPlan, the
-        # downsample LayerNorms): everywhere else a large activation would saturate silently, so the default is the f32 MFMA
-        self.split_allowed = False
-        self.tuned = {}  # (shape, epilogue) -> tile configuration index + 1 (autotuning cache)
-        self.ps = self.pt = None
-        if prologue is not None:
-            s, t = prologue
-            assert s.numel() == Cin
-            self.ps, self.pt = s.float().to(device).contiguous(), t.float().to(device).contiguous()
-
-    def flops(self, M):
-        return 2.0 * M * self.N * self.K
-
-    def split_weights(self):
-        """(w_split, w_unscale): rows of [Kp/32][hi 32 | lo 32] f16 of w * 2^s (s keeps the lo halves out of the f16 subnormals),
-        viewed as fp32 [N][Kp]; built once from the fp32 pack (exactly representable inputs: the split is of the fp32 weights)."""
-        if getattr(self, "_ws", None) is None:
-            ws, self._wus = split_pack(self.w)
-            self._ws = ws.to(self.w.device)
-        return self._ws, self._wus
-
-    def row_l1(self):
-        return float(self.w.abs().sum(1).max())
-
-
-def conv(pc, x, out=None, flags=0, gamma=None, res=None, out_nchw=None, out_split=False, out2=None):
-    """Launch kpf_conv2d_f32.  x: Act; out: Act (or None to allocate dense); res: Act."""
-    lib = L.load()
+def conv_desc(pc, x, Kp, out=None, out_nchw=None, res=None, out2=None, gamma=None, flags=0):
+    """The launch descriptor of one implicit GEMM, fp32 or 16-bit (Kp: the operand's row length, pc.Kp or pc.Kp16).  x / out / res / out2: Acts
+    (out None: allocated dense in x's storage type; out_nchw: an fp32 NCHW tensor instead).  Host arithmetic only: nothing is launched.
+    Returns (ConvDesc, out, output tensor, effective res, (M, OH, OW))."""
+    g = pc.geom
     B = x.B
-    if pc.merge > 1:
-        assert x.ld == x.C and x.coff == 0 and x.W % pc.merge == 0
-        IH, IW, in_ld, in_coff = x.H, x.W // pc.merge, x.C * pc.merge, 0
-        assert in_ld == pc.Cin, (in_ld, pc.Cin)
+    if g.merge > 1:
+        assert x.ld == x.C and x.coff == 0 and x.W % g.merge == 0
+        IH, IW, in_ld, in_coff = x.H, x.W // g.merge, x.C * g.merge, 0
+        assert in_ld == g.Cin, (in_ld, g.Cin)
     else:
         IH, IW, in_ld, in_coff = x.H, x.W, x.ld, x.coff
-        assert x.C == pc.Cin, (x.C, pc.Cin)
-    OH = (IH + 2 * pc.ph - pc.KH) // pc.sh + 1
-    OW = (IW + 2 * pc.pw - pc.KW) // pc.sw + 1
+        assert x.C == g.Cin, (x.C, g.Cin)
+    OH, OW = g.out_hw(IH, IW)
     d = L.ConvDesc()
-    d.B, d.IH, d.IW, d.Cin, d.in_ld, d.in_coff = B, IH, IW, pc.Cin, in_ld, in_coff
-    d.OH, d.OW, d.N = OH, OW, pc.N
-    d.KH, d.KW, d.sh, d.sw, d.ph, d.pw, d.Kp = pc.KH, pc.KW, pc.sh, pc.sw, pc.ph, pc.pw, pc.Kp
+    d.B, d.IH, d.IW, d.Cin, d.in_ld, d.in_coff = B, IH, IW, g.Cin, in_ld, in_coff
+    d.OH, d.OW, d.N = OH, OW, g.N
+    d.KH, d.KW, d.sh, d.sw, d.ph, d.pw, d.Kp = g.KH, g.KW, g.sh, g.sw, g.ph, g.pw, Kp
     if out_nchw is not None:
         flags |= L.KPF_OUT_NCHW
         optr = out_nchw
-        d.out_ld, d.out_coff = pc.N, 0
+        d.out_ld, d.out_coff = g.N, 0
     else:
         if out is None:
-            out = Act.empty(B, OH, OW, pc.N, x.buf.device)
-        assert (out.B, out.H, out.W, out.C) == (B, OH, OW, pc.N), ((out.B, out.H, out.W, out.C), (B, OH, OW, pc.N))
+            out = Act.empty(B, OH, OW, g.N, x.buf.device, x.buf.dtype)
+        assert (out.B, out.H, out.W, out.C) == (B, OH, OW, g.N), ((out.B, out.H, out.W, out.C), (B, OH, OW, g.N))
         optr = out.buf
         d.out_ld, d.out_coff = out.ld, out.coff
     if res is not None:
@@ -218,11 +138,21 @@ def conv(pc, x, out=None, flags=0, gamma=None, res=None, out_nchw=None, out_spli
         res = out2
     if gamma is not None:
         flags |= L.KPF_RES_GAMMA
+    d.flags = flags
+    d.groups, d.w_gstride = pc.groups, pc.w_gstride  # (grouped launch: training.GroupedPack; 0 = one convolution)
+    return d, out, optr, res, (B * OH * OW, OH, OW)
+
+
+def conv(pc, x, out=None, flags=0, gamma=None, res=None, out_nchw=None, out_split=False, out2=None):
+    """Launch kpf_conv2d_f32.  x: Act; out: Act (or None to allocate dense); res: Act."""
+    lib = L.load()
+    d, out, optr, res, (M, _, _) = conv_desc(pc, x, pc.geom.Kp, out, out_nchw, res, out2, gamma, flags)
+    g, flags = pc.geom, d.flags
     w = pc.w
     if x.split:
         flags |= L.KPF_IN_SPLIT
         w, d.w_unscale = pc.split_weights()
-    elif GEMM_MODE == "split" and pc.Cin % 32 == 0 and pc.split_allowed:
+    elif GEMM_MODE == "split" and g.Cin % 32 == 0 and pc.split_allowed:
         flags |= L.KPF_W_SPLIT  # fp32 activations, split in registers
         w, d.w_unscale = pc.split_weights()
     if out_split:
@@ -231,22 +161,20 @@ def conv(pc, x, out=None, flags=0, gamma=None, res=None, out_nchw=None, out_spli
     elif out is not None and out_nchw is None:
         out.split = False
     d.flags = flags
-    d.groups, d.w_gstride = getattr(pc, "groups", 0), getattr(pc, "w_gstride", 0)  # (grouped launch: training.GroupedPack; 0 = one convolution)
-    M = B * OH * OW
     if AUTOTUNE:
-        key = (M, IH, IW, flags, in_ld, in_coff, d.out_ld, d.out_coff, d.res_ld, d.res_coff)
+        key = (M, d.IH, d.IW, flags, d.in_ld, d.in_coff, d.out_ld, d.out_coff, d.res_ld, d.res_coff)
         cfg = pc.tuned.get(key)
         if cfg is None and PROFILE is None and not torch.cuda.is_current_stream_capturing():
             cfg = pc.tuned[key] = _autotune(lib, d, x, w, pc, gamma, res, optr, flags)
         d.tile_cfg = cfg or 0
     if _TILE_RULES and not AUTOTUNE:
-        d.tile_cfg = _TILE_RULES.get((M, pc.N, pc.K, pc.KH), 0)
+        d.tile_cfg = _TILE_RULES.get((M, g.N, g.K, g.KH), 0)
     if FORCE_TILE:
         d.tile_cfg = FORCE_TILE
     # algorithmic bytes: input pixels once, weights once, output once (+ residual once)
-    nbytes = 4.0 * (B * IH * IW * pc.Cin + pc.N * pc.K + M * pc.N * (2 if res is not None else 1))
+    nbytes = 4.0 * (x.B * d.IH * d.IW * g.Cin + g.N * g.K + M * g.N * (2 if res is not None else 1))
     ng = max(1, d.groups)
-    _launch("igemm_split_kernel" if flags & (L.KPF_IN_SPLIT | L.KPF_W_SPLIT) else "igemm_f32_kernel", pc.flops(M) * ng, nbytes * ng, (M, pc.N, pc.K, pc.KH, pc.KW),
+    _launch("igemm_split_kernel" if flags & (L.KPF_IN_SPLIT | L.KPF_W_SPLIT) else "igemm_f32_kernel", g.flops(M) * ng, nbytes * ng, (M, g.N, g.K, g.KH, g.KW),
             lambda: L.check(lib.kpf_conv2d_f32(C.byref(d), _ptr(x.buf), _ptr(w), _ptr(pc.b), _ptr(pc.ps), _ptr(pc.pt), _ptr(gamma),
                                                _ptr(res.buf if res is not None else None), _ptr(optr), _stream()), "kpf_conv2d_f32"))
     return out
@@ -351,24 +279,24 @@ class ResidualPlan:
     Always on the f32-input MFMA, also under KPF_GEMM=split: its operands are unbounded ReLU outputs and residual sums (no pack-time
     bound on |activation| exists), which the f16 split format would saturate at 65504."""
 
-    def __init__(self, sd, p, device):
+    def __init__(self, sd, p, device, pack=None, launch=None):
+        """pack(weight, bias, **kw) -> the operand `launch(operand, x, **kw)` takes: PackedConv / conv unless given (engine16.Residual16)"""
+        P = pack or (lambda w, b, **k: PackedConv(w, b, device, **k))
+        self.launch = launch or conv
         cin = sd[p + ".conv1.conv.weight"].shape[1]
         cout = sd[p + ".conv3.conv.weight"].shape[0]
         self.cin, self.cout = cin, cout
-        self.c1 = PackedConv(sd[p + ".conv1.conv.weight"], sd[p + ".conv1.conv.bias"], device,
-                             fold_bn=bn_scale_shift(sd, p + ".bn2"), prologue=bn_scale_shift(sd, p + ".bn1"))
-        self.c2 = PackedConv(sd[p + ".conv2.conv.weight"], sd[p + ".conv2.conv.bias"], device, pad=1,
-                             fold_bn=bn_scale_shift(sd, p + ".bn3"))
-        self.c3 = PackedConv(sd[p + ".conv3.conv.weight"], sd[p + ".conv3.conv.bias"], device)
-        self.skip = None
-        if cin != cout:
-            self.skip = PackedConv(sd[p + ".skip_layer.conv.weight"], sd[p + ".skip_layer.conv.bias"], device)
+        self.c1 = P(sd[p + ".conv1.conv.weight"], sd[p + ".conv1.conv.bias"], fold_bn=bn_scale_shift(sd, p + ".bn2"), prologue=bn_scale_shift(sd, p + ".bn1"))
+        self.c2 = P(sd[p + ".conv2.conv.weight"], sd[p + ".conv2.conv.bias"], pad=1, fold_bn=bn_scale_shift(sd, p + ".bn3"))
+        self.c3 = P(sd[p + ".conv3.conv.weight"], sd[p + ".conv3.conv.bias"])
+        self.skip = P(sd[p + ".skip_layer.conv.weight"], sd[p + ".skip_layer.conv.bias"]) if cin != cout else None
 
     def __call__(self, x, out=None):
+        conv = self.launch
         h = conv(self.c1, x, flags=L.KPF_ACT_RELU)
         h = conv(self.c2, h, flags=L.KPF_ACT_RELU)
         if out is None:
-            out = Act.empty(x.B, x.H, x.W, self.cout, x.buf.device)
+            out = Act.empty(x.B, x.H, x.W, self.cout, x.buf.device, x.buf.dtype)
         if self.skip is not None:
             conv(self.skip, x, out=out)
             return conv(self.c3, h, out=out, res=out)
@@ -445,6 +373,36 @@ class ConvNeXtBlockPlan:
         return x
 
 
+def resnet_stages(sdp, b, P):
+    """The four ResNet stages of state dict `sdp` under prefix b (model/resnet.py:78-135, 232-244) as lists of (c1, c2, c3, ds) operands built by
+    P(weight, bias, **kw), every BatchNorm folded: Bottleneck (v1.5: the stride sits on the 3x3) or BasicBlock (c3 None), ds = the 1x1 downsample or None."""
+    layers = []
+    for li in range(1, 5):
+        blocks, j = [], 0
+        while (b + ".layer%d.%d.conv1.weight" % (li, j)) in sdp:
+            q = b + ".layer%d.%d" % (li, j)
+            stride = 2 if (li > 1 and j == 0) else 1
+            bn = lambda n: bn_scale_shift(sdp, q + n)
+            ds = P(sdp[q + ".downsample.0.weight"], None, stride=stride, fold_bn=bn(".downsample.1")) if (q + ".downsample.0.weight") in sdp else None
+            if (q + ".conv3.weight") in sdp:
+                blocks.append((P(sdp[q + ".conv1.weight"], None, fold_bn=bn(".bn1")), P(sdp[q + ".conv2.weight"], None, stride=stride, pad=1, fold_bn=bn(".bn2")),
+                               P(sdp[q + ".conv3.weight"], None, fold_bn=bn(".bn3")), ds))
+            else:
+                blocks.append((P(sdp[q + ".conv1.weight"], None, stride=stride, pad=1, fold_bn=bn(".bn1")), P(sdp[q + ".conv2.weight"], None, pad=1, fold_bn=bn(".bn2")), None, ds))
+            j += 1
+        layers.append(blocks)
+    return layers
+
+
+def unet_decoder(sdp, fam, R, P):
+    """The decoder behind either encoder: ((up, skip, fusion) Residual blocks of levels 4, 3, 2 built by R(name), result_emb (ConvNeXt only), the three
+    `finals` 1x1 heads concatenated into one 105-channel operand built by P)."""
+    levels = [(R("up%d.0" % i), R("skip_layer%d" % i), R("fusion_layer%d" % i)) for i in (4, 3, 2)]
+    wf = torch.cat([sdp["finals.%d.weight" % i] for i in range(3)], 0)
+    bf = torch.cat([sdp["finals.%d.bias" % i] for i in range(3)], 0)
+    return levels, (R("result_emb") if fam == "convnext" else None), P(wf, bf)
+
+
 class UNetPlan:
     """One backbone stream (encoder + 3-level Residual UNet decoder + heads): convNeXT/resnetUnet.py:129-152 /
     model/resnetUnet.py:309-330.  __call__(img NCHW) -> (img_result NCHW B x 105 x F x F, img_feature Act NHWC 128)."""
@@ -454,10 +412,10 @@ class UNetPlan:
         self.device = device
         sdp = {k[len(p) + 1:]: v for k, v in sd.items() if k.startswith(p + ".")}
         self.in_ch = (sdp["backbone.downsample_layers.0.0.weight"] if self.fam == "convnext" else sdp["backbone.conv1.weight"]).shape[1]
+        P = lambda w, bias, **k: PackedConv(w, bias, device, **k)
+        b = "backbone"
         if self.fam == "convnext":
-            depths, dims = CONVNEXT[size]
-            self.dims = dims
-            b = "backbone"
+            depths, _ = CONVNEXT[size]
             self.stem = PackedConv(sdp[b + ".downsample_layers.0.0.weight"], sdp[b + ".downsample_layers.0.0.bias"], device,
                                    stride=4, patchify=True)
             self.stem_ln = (sdp[b + ".downsample_layers.0.1.weight"].float().to(device), sdp[b + ".downsample_layers.0.1.bias"].float().to(device))
@@ -471,40 +429,9 @@ class UNetPlan:
                                             device, stride=2, patchify=True))
             self.stages = [[ConvNeXtBlockPlan(sdp, b + ".stages.%d.%d" % (i, j), device) for j in range(depths[i])] for i in range(4)]
         else:
-            self.dims = dims = (64, 128, 256, 512)
-            b = "backbone"
             self.stem = PackedConv(sdp[b + ".conv1.weight"], None, device, stride=2, pad=3, fold_bn=bn_scale_shift(sdp, b + ".bn1"), cin_pad=4)
-            self.layers = []
-            for li in range(1, 5):
-                blocks = []
-                j = 0
-                while (b + ".layer%d.%d.conv1.weight" % (li, j)) in sdp:
-                    q = b + ".layer%d.%d" % (li, j)
-                    stride = 2 if (li > 1 and j == 0) else 1
-                    ds = None
-                    if (q + ".downsample.0.weight") in sdp:
-                        ds = PackedConv(sdp[q + ".downsample.0.weight"], None, device, stride=stride, fold_bn=bn_scale_shift(sdp, q + ".downsample.1"))
-                    if (q + ".conv3.weight") in sdp:  # Bottleneck (v1.5: the stride sits on the 3x3), model/resnet.py:78-135
-                        c1 = PackedConv(sdp[q + ".conv1.weight"], None, device, fold_bn=bn_scale_shift(sdp, q + ".bn1"))
-                        c2 = PackedConv(sdp[q + ".conv2.weight"], None, device, stride=stride, pad=1, fold_bn=bn_scale_shift(sdp, q + ".bn2"))
-                        c3 = PackedConv(sdp[q + ".conv3.weight"], None, device, fold_bn=bn_scale_shift(sdp, q + ".bn3"))
-                        blocks.append((c1, c2, c3, ds))
-                        j += 1
-                        continue
-                    c1 = PackedConv(sdp[q + ".conv1.weight"], None, device, stride=stride, pad=1, fold_bn=bn_scale_shift(sdp, q + ".bn1"))
-                    c2 = PackedConv(sdp[q + ".conv2.weight"], None, device, pad=1, fold_bn=bn_scale_shift(sdp, q + ".bn2"))
-                    blocks.append((c1, c2, None, ds))
-                    j += 1
-                self.layers.append(blocks)
-        d = dims
-        R = lambda name: ResidualPlan(sdp, name, device)
-        self.up4, self.skip4, self.fus4 = R("up4.0"), R("skip_layer4"), R("fusion_layer4")
-        self.up3, self.skip3, self.fus3 = R("up3.0"), R("skip_layer3"), R("fusion_layer3")
-        self.up2, self.skip2, self.fus2 = R("up2.0"), R("skip_layer2"), R("fusion_layer2")
-        self.result_emb = R("result_emb") if self.fam == "convnext" else None
-        wf = torch.cat([sdp["finals.%d.weight" % i] for i in range(3)], 0)
-        bf = torch.cat([sdp["finals.%d.bias" % i] for i in range(3)], 0)
-        self.finals = PackedConv(wf, bf, device)
+            self.layers = resnet_stages(sdp, b, P)
+        self.levels, self.result_emb, self.finals = unet_decoder(sdp, self.fam, lambda name: ResidualPlan(sdp, name, device), P)
 
     # -- encoders -------------------------------------------------------------------------------------------
     def _convnext(self, img):
@@ -547,19 +474,14 @@ class UNetPlan:
 
     def __call__(self, img):
         c1, c2, c3, c4 = self._convnext(img) if self.fam == "convnext" else self._resnet(img)
-        d = self.dims
         dev = self.device
         B = c1.B
-
-        def level(up, skip, fus, lo, hi, fus_out_c):
+        feat = c4
+        for (up, skip, fus), hi in zip(self.levels, (c3, c2, c1)):
             cat = Act.empty(B, hi.H, hi.W, up.cout + skip.cout, dev)
-            upsample2x(up(lo), cat.slice(0, up.cout))
+            upsample2x(up(feat), cat.slice(0, up.cout))
             skip(hi, out=cat.slice(up.cout, skip.cout))
-            return fus(cat)
-
-        c3f = level(self.up4, self.skip4, self.fus4, c4, c3, d[2])
-        c2f = level(self.up3, self.skip3, self.fus3, c3f, c2, d[1])
-        feat = level(self.up2, self.skip2, self.fus2, c2f, c1, 128)
+            feat = fus(cat)
         if self.result_emb is not None:
             feat = self.result_emb(feat)
         res = torch.empty(B, 105, feat.H, feat.W, device=dev, dtype=torch.float32)

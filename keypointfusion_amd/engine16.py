@@ -11,7 +11,8 @@ import ctypes as C
 import torch
 
 from . import lib as L
-from .engine import Act, PackedConv, _launch, _ptr, _stream, bn_scale_shift, conv, maxpool3x3s2, nchw_to_nhwc
+from .engine import Act, ResidualPlan, _launch, _ptr, _stream, bn_scale_shift, conv, conv_desc, maxpool3x3s2, nchw_to_nhwc, resnet_stages, unet_decoder
+from .packs import ConvGeom, Packed16, PackedConv  # noqa: F401 (Packed16: the 16-bit operand, defined with the pack types)
 from .spec import CONVNEXT, parse_net
 
 DTYPES = {"bf16": (torch.bfloat16, L.KPF_DT_BF16), "f16": (torch.float16, L.KPF_DT_F16)}
@@ -32,19 +33,7 @@ def PROFILE_LABELS():
 
 
 def empty16(B, H, W, Cc, device, tdt):
-    a = Act(torch.empty(B * H * W * Cc, device=device, dtype=tdt), B, H, W, Cc)
-    return a
-
-
-class Packed16:
-    """16-bit image of a PackedConv: rows [N][Kp], Kp padded to 64 elements, in the storage dtype; bias stays fp32."""
-
-    def __init__(self, pc, tdt):
-        self.pc = pc
-        self.Kp = (pc.K + 63) // 64 * 64
-        w = torch.zeros(pc.N, self.Kp, dtype=torch.float32, device=pc.w.device)
-        w[:, :pc.K] = pc.w[:, :pc.K]
-        self.w = w.to(tdt).contiguous()
+    return Act.empty(B, H, W, Cc, device, tdt)
 
 
 def conv16(p16, x, kdt, out=None, flags=0, gamma=None, res=None, out_nchw=None, out2=None, ln=None, probe=False):
@@ -52,84 +41,33 @@ def conv16(p16, x, kdt, out=None, flags=0, gamma=None, res=None, out_nchw=None, 
     W diag(ln_w)).  probe: no launch — returns whether the library takes this layer with KPF_PRO_LN (a rule over the layer's shape, not its batch)."""
     lib = L.load()
     pc = p16.pc
-    B = x.B
-    if pc.merge > 1:
-        assert x.ld == x.C and x.coff == 0 and x.W % pc.merge == 0
-        IH, IW, in_ld, in_coff = x.H, x.W // pc.merge, x.C * pc.merge, 0
-        assert in_ld == pc.Cin, (in_ld, pc.Cin)
-    else:
-        IH, IW, in_ld, in_coff = x.H, x.W, x.ld, x.coff
-        assert x.C == pc.Cin, (x.C, pc.Cin)
-    OH = (IH + 2 * pc.ph - pc.KH) // pc.sh + 1
-    OW = (IW + 2 * pc.pw - pc.KW) // pc.sw + 1
-    d = L.ConvDesc()
-    d.B, d.IH, d.IW, d.Cin, d.in_ld, d.in_coff = B, IH, IW, pc.Cin, in_ld, in_coff
-    d.OH, d.OW, d.N = OH, OW, pc.N
-    d.KH, d.KW, d.sh, d.sw, d.ph, d.pw, d.Kp = pc.KH, pc.KW, pc.sh, pc.sw, pc.ph, pc.pw, p16.Kp
-    if out_nchw is not None:
-        flags |= L.KPF_OUT_NCHW
-        optr = out_nchw
-        d.out_ld, d.out_coff = pc.N, 0
-    else:
-        if out is None:
-            out = empty16(B, OH, OW, pc.N, x.buf.device, x.buf.dtype)
-        assert (out.B, out.H, out.W, out.C) == (B, OH, OW, pc.N)
-        optr = out.buf
-        d.out_ld, d.out_coff = out.ld, out.coff
-    if res is not None:
-        flags |= L.KPF_RES_ADD
-        d.res_ld, d.res_coff = res.ld, res.coff
-    if out2 is not None:  # KPF_ACT_GELU_SAVE: the pre-activation goes to a second buffer, passed in the residual's slot (nothing is read from it)
-        assert res is None and (flags & L.KPF_ACT_GELU)
-        flags |= L.KPF_ACT_GELU_SAVE
-        d.res_ld, d.res_coff = out2.ld, out2.coff
-        res = out2
-    if gamma is not None:
-        flags |= L.KPF_RES_GAMMA
+    d, out, optr, res, (M, _, _) = conv_desc(pc, x, p16.Kp, out, out_nchw, res, out2, gamma, flags)
+    g = pc.geom
     ps, pt, bias = pc.ps, pc.pt, pc.b
     if ln is not None:
-        flags |= L.KPF_PRO_LN
+        d.flags |= L.KPF_PRO_LN
         ps, pt, bias = ln
-    d.flags = flags
-    d.groups, d.w_gstride = getattr(pc, "groups", 0), getattr(pc, "w_gstride", 0)  # (grouped launch: training.GroupedPack; 0 = one convolution)
     if _TILE_RULES16:
-        d.tile_cfg = _TILE_RULES16.get((B * OH * OW, pc.N, pc.K, pc.KH), 0)
+        d.tile_cfg = _TILE_RULES16.get((M, g.N, g.K, g.KH), 0)
     if FORCE_TILE16:
         d.tile_cfg = FORCE_TILE16
     if probe:
         return bool(lib.kpf_conv2d_h16_ln_fold_supported(C.byref(d)))
-    M = B * OH * OW
-    nbytes = 2.0 * (B * IH * IW * pc.Cin + pc.N * pc.K + M * pc.N * (2 if res is not None else 1))
+    nbytes = 2.0 * (x.B * d.IH * d.IW * g.Cin + g.N * g.K + M * g.N * (2 if res is not None else 1))
     name = "gemm16_8ph_kernel" if (PROFILE_LABELS() and (ln is not None or lib.kpf_conv2d_h16_uses_8ph(C.byref(d), 1 if pc.ps is not None else 0))) else "igemm_h16_kernel"
     ng = max(1, d.groups)
-    _launch(name, pc.flops(M) * ng, nbytes * ng, (M, pc.N, pc.K, pc.KH, pc.KW),
+    _launch(name, g.flops(M) * ng, nbytes * ng, (M, g.N, g.K, g.KH, g.KW),
             lambda: L.check(lib.kpf_conv2d_h16(C.byref(d), _ptr(x.buf), _ptr(p16.w), _ptr(bias), _ptr(ps), _ptr(pt), _ptr(gamma),
                                                _ptr(res.buf if res is not None else None), _ptr(optr), kdt, _stream()), "kpf_conv2d_h16"))
     return out
 
 
-class Residual16:
-    """engine.ResidualPlan on 16-bit storage."""
+class Residual16(ResidualPlan):
+    """engine.ResidualPlan on 16-bit storage: Packed16 operands, launched by conv16 in the kernel dtype of `tdt`."""
 
     def __init__(self, sd, p, device, tdt):
-        cin = sd[p + ".conv1.conv.weight"].shape[1]
-        self.cout = sd[p + ".conv3.conv.weight"].shape[0]
-        P = lambda *a, **k: Packed16(PackedConv(*a, **k), tdt)
-        self.c1 = P(sd[p + ".conv1.conv.weight"], sd[p + ".conv1.conv.bias"], device, fold_bn=bn_scale_shift(sd, p + ".bn2"),
-                    prologue=bn_scale_shift(sd, p + ".bn1"))
-        self.c2 = P(sd[p + ".conv2.conv.weight"], sd[p + ".conv2.conv.bias"], device, pad=1, fold_bn=bn_scale_shift(sd, p + ".bn3"))
-        self.c3 = P(sd[p + ".conv3.conv.weight"], sd[p + ".conv3.conv.bias"], device)
-        self.skip = P(sd[p + ".skip_layer.conv.weight"], sd[p + ".skip_layer.conv.bias"], device) if cin != self.cout else None
-
-    def __call__(self, x, kdt, out=None):
-        h = conv16(self.c1, x, kdt, flags=L.KPF_ACT_RELU)
-        h = conv16(self.c2, h, kdt, flags=L.KPF_ACT_RELU)
-        if out is None:
-            out = empty16(x.B, x.H, x.W, self.cout, x.buf.device, x.buf.dtype)
-        if self.skip is not None:
-            conv16(self.skip, x, kdt, out=out)
-            return conv16(self.c3, h, kdt, out=out, res=out)
-        return conv16(self.c3, h, kdt, out=out, res=x)
+        kdt = dict(DTYPES.values())[tdt]
+        super().__init__(sd, p, device, pack=lambda w, b, **k: Packed16(PackedConv(w, b, device, **k), tdt), launch=lambda pc, x, **k: conv16(pc, x, kdt, **k))
 
 
 def _ln_fold_shape_ok(c):
@@ -138,7 +76,7 @@ def _ln_fold_shape_ok(c):
     d.B, d.IH, d.IW, d.Cin, d.in_ld, d.in_coff = 1, 16, 16, c, c, 0
     d.OH, d.OW, d.N = 16, 16, 4 * c
     d.KH = d.KW = d.sh = d.sw = 1
-    d.Kp = (c + 63) // 64 * 64
+    d.Kp = ConvGeom.plain(4 * c, c, 1, 1).Kp16
     d.out_ld, d.out_coff, d.flags = 4 * c, 0, L.KPF_ACT_GELU
     return bool(L.load().kpf_conv2d_h16_ln_fold_supported(C.byref(d)))
 
@@ -216,46 +154,20 @@ class UNetPlan16:
         sdp = {k[len(p) + 1:]: v for k, v in sd.items() if k.startswith(p + ".")}
         b = "backbone"
         f32 = lambda k: sdp[k].detach().float().contiguous().to(device)
-        P16 = lambda *a, **k: Packed16(PackedConv(*a, **k), self.tdt)
+        P16 = lambda w, bias, **k: Packed16(PackedConv(w, bias, device, **k), self.tdt)
         if self.fam == "convnext":
-            depths, dims = CONVNEXT[size]
-            self.dims = dims
+            depths, _ = CONVNEXT[size]
             self.stem = PackedConv(sdp[b + ".downsample_layers.0.0.weight"], sdp[b + ".downsample_layers.0.0.bias"], device, stride=4, patchify=True)
             self.stem_ln = (f32(b + ".downsample_layers.0.1.weight"), f32(b + ".downsample_layers.0.1.bias"))
             self.down, self.down_ln = [None], [None]
             for i in range(1, 4):
                 self.down_ln.append((f32(b + ".downsample_layers.%d.0.weight" % i), f32(b + ".downsample_layers.%d.0.bias" % i)))
-                self.down.append(P16(sdp[b + ".downsample_layers.%d.1.weight" % i], sdp[b + ".downsample_layers.%d.1.bias" % i], device, stride=2, patchify=True))
+                self.down.append(P16(sdp[b + ".downsample_layers.%d.1.weight" % i], sdp[b + ".downsample_layers.%d.1.bias" % i], stride=2, patchify=True))
             self.stages = [[Block16(sdp, b + ".stages.%d.%d" % (i, j), device, self.tdt) for j in range(depths[i])] for i in range(4)]
         else:  # ResNet (model/resnet.py:232-244): fp32 7x7/s2 stem (BatchNorm folded) + max-pool, then 16-bit stages with folded BatchNorms
             self.stem = PackedConv(sdp[b + ".conv1.weight"], None, device, stride=2, pad=3, fold_bn=bn_scale_shift(sdp, b + ".bn1"), cin_pad=4)
-            self.layers = []
-            for li in range(1, 5):
-                blocks = []
-                j = 0
-                while (b + ".layer%d.%d.conv1.weight" % (li, j)) in sdp:
-                    q = b + ".layer%d.%d" % (li, j)
-                    stride = 2 if (li > 1 and j == 0) else 1
-                    ds = None
-                    if (q + ".downsample.0.weight") in sdp:
-                        ds = P16(sdp[q + ".downsample.0.weight"], None, device, stride=stride, fold_bn=bn_scale_shift(sdp, q + ".downsample.1"))
-                    if (q + ".conv3.weight") in sdp:
-                        blocks.append((P16(sdp[q + ".conv1.weight"], None, device, fold_bn=bn_scale_shift(sdp, q + ".bn1")),
-                                       P16(sdp[q + ".conv2.weight"], None, device, stride=stride, pad=1, fold_bn=bn_scale_shift(sdp, q + ".bn2")),
-                                       P16(sdp[q + ".conv3.weight"], None, device, fold_bn=bn_scale_shift(sdp, q + ".bn3")), ds))
-                    else:
-                        blocks.append((P16(sdp[q + ".conv1.weight"], None, device, stride=stride, pad=1, fold_bn=bn_scale_shift(sdp, q + ".bn1")),
-                                       P16(sdp[q + ".conv2.weight"], None, device, pad=1, fold_bn=bn_scale_shift(sdp, q + ".bn2")), None, ds))
-                    j += 1
-                self.layers.append(blocks)
-        R = lambda name: Residual16(sdp, name, device, self.tdt)
-        self.up4, self.skip4, self.fus4 = R("up4.0"), R("skip_layer4"), R("fusion_layer4")
-        self.up3, self.skip3, self.fus3 = R("up3.0"), R("skip_layer3"), R("fusion_layer3")
-        self.up2, self.skip2, self.fus2 = R("up2.0"), R("skip_layer2"), R("fusion_layer2")
-        self.result_emb = R("result_emb") if self.fam == "convnext" else None
-        wf = torch.cat([sdp["finals.%d.weight" % i] for i in range(3)], 0)
-        bf = torch.cat([sdp["finals.%d.bias" % i] for i in range(3)], 0)
-        self.finals = Packed16(PackedConv(wf, bf, device), self.tdt)
+            self.layers = resnet_stages(sdp, b, P16)
+        self.levels, self.result_emb, self.finals = unet_decoder(sdp, self.fam, lambda name: Residual16(sdp, name, device, self.tdt), P16)
 
     def _ln(self, x, wb, out, x_kdt):
         L.check(L.load().kpf_layernorm_h16(_ptr(x.buf), x_kdt, _ptr(wb[0]), _ptr(wb[1]), _ptr(out.buf), self.kdt, x.B * x.H * x.W, x.C, 1e-6,
@@ -311,20 +223,16 @@ class UNetPlan16:
         dev, tdt, kdt = self.device, self.tdt, self.kdt
         B = img.shape[0]
         c1, c2, c3, c4 = self._convnext(img) if self.fam == "convnext" else self._resnet(img)
-
-        def level(up, skip, fus, lo, hi):
+        feat = c4
+        for (up, skip, fus), hi in zip(self.levels, (c3, c2, c1)):
             cat = empty16(B, hi.H, hi.W, up.cout + skip.cout, dev, tdt)
-            u = up(lo, kdt)
+            u = up(feat)
             dst = cat.slice(0, up.cout)
             L.check(lib.kpf_upsample2x_h16(_ptr(u.buf), _ptr(dst.buf), u.B, u.H, u.W, u.C, dst.ld, dst.coff, kdt, _stream()), "kpf_upsample2x_h16")
-            skip(hi, kdt, out=cat.slice(up.cout, skip.cout))
-            return fus(cat, kdt)
-
-        c3f = level(self.up4, self.skip4, self.fus4, c4, c3)
-        c2f = level(self.up3, self.skip3, self.fus3, c3f, c2)
-        feat = level(self.up2, self.skip2, self.fus2, c2f, c1)
+            skip(hi, out=cat.slice(up.cout, skip.cout))
+            feat = fus(cat)
         if self.result_emb is not None:
-            feat = self.result_emb(feat, kdt)
+            feat = self.result_emb(feat)
         res = torch.empty(B, 105, feat.H, feat.W, device=dev, dtype=torch.float32)
         conv16(self.finals, feat, kdt, out_nchw=res)
         f32 = Act.empty(B, feat.H, feat.W, feat.C, dev)

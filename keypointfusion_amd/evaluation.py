@@ -121,7 +121,7 @@ def pck_auc(per_joint_errors, val_min=0.0, val_max=50.0, steps=20):
     aucs, curves = [], []
     for j in range(len(per_joint_errors)):
         d = np.asarray(per_joint_errors[j], dtype=np.float64)
-        curve = np.array([np.mean((d <= t).astype("float")) for t in th])
+        curve = np.array([np.mean((d <= t).astype(float)) for t in th])
         curves.append(curve)
         aucs.append(_trapz(curve, th) / norm)
     curve = np.mean(np.array(curves), 0)

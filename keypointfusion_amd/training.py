@@ -36,6 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from .graphs import prepare_training_graphs
+from .packs import ConvGeom, Pack
 
 prepare_training_graphs()  # DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 unless the host chose a value: process-wide, training side only (graphs.py)
 
@@ -548,108 +549,68 @@ def make_optimizer(params, lr=8e-4, step_size=10, start_epoch=0, capturable=Fals
 # ----------------------------------------------------------------------------------------------------------------
 # convolution / Linear with forward and data-gradient on the HIP implicit GEMM
 # ----------------------------------------------------------------------------------------------------------------
-class DevPack:
-    """Kernel-layout view of a convolution weight built ON THE DEVICE (training repacks every step: no host round trip, no BatchNorm
-    folding): the attributes engine.conv() reads from a PackedConv.  weight OIHW (or [N][K] for Linear) -> rows [N][Kp], k = (ky,kx,c)."""
-    split_allowed = False
-    ps = pt = None
+def _oihw(weight):
+    w = weight.detach()
+    return w[:, :, None, None] if w.dim() == 2 else w
+
+
+def _fp32_bias(bias):
+    return bias.detach().float().contiguous() if bias is not None else None  # NULL bias: the kernel adds nothing
+
+
+class DevPack(Pack):
+    """The device-side constructors of a Pack (training repacks every step: no host round trip, no BatchNorm folding).
+    weight OIHW (or [N][K] for Linear) -> rows [N][Kp], k = (ky,kx,c); `packed` and `from_rows` return plain Packs."""
 
     def __init__(self, weight, bias, stride=1, pad=0, patchify=False):
-        w = weight.detach()
-        if w.dim() == 2:
-            w = w[:, :, None, None]
+        w = _oihw(weight)
         N, Cin, KH, KW = w.shape
-        if patchify:
-            assert stride == KH == KW and pad == 0
-            self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = KH, 1, KW * Cin, KH, 1, 0, 0, KW
-        else:
-            self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = KH, KW, Cin, stride, stride, pad, pad, 1
-        K = KH * KW * Cin
-        self.N, self.K, self.Kp = N, K, (K + 31) // 32 * 32
-        wk = w.permute(0, 2, 3, 1).reshape(N, K)
-        self._set_rows(wk)
-        self.b = bias.detach().float().contiguous() if bias is not None else None  # NULL bias: the kernel adds nothing
-        self.tuned = {}
+        geom = ConvGeom.forward(N, Cin, KH, KW, stride, pad, patchify)
+        super().__init__(geom, b=_fp32_bias(bias), **self._rows(geom, w.permute(0, 2, 3, 1).reshape(N, geom.K)))
 
-    def _set_rows(self, rows):
+    @staticmethod
+    def _rows(geom, rows):
         """rows [N][K]: fp32 -> the fp32 kernel operand (K padded to 32); 16-bit (a shadow copy of the master weight, cast once per
         step for the whole model) -> the 16-bit operand (K padded to 64) with no per-layer cast."""
-        N, K = rows.shape
-        if rows.dtype == torch.float32:
-            self.w = rows.contiguous() if self.Kp == K else F.pad(rows, (0, self.Kp - K)).contiguous()
-            self.w16 = None
-        else:
-            kp = (K + 63) // 64 * 64
-            self.w = None
-            self.w16 = rows.contiguous() if kp == K else F.pad(rows, (0, kp - K)).contiguous()
+        name, kp = ("w", geom.Kp) if rows.dtype == torch.float32 else ("w16", geom.Kp16)
+        return {name: rows.contiguous() if kp == geom.K else F.pad(rows, (0, kp - geom.K)).contiguous()}
 
     @classmethod
     def packed(cls, weight, bias, mode, prec="f32", stride=1, pad=0, patchify=False, n_pad=None):
         """The operand of one launch of kpf_pack_conv_weight (csrc/kpf_train.hip) instead of flip / permute-clone / pad / cast
         expressions: `weight` [N, Cin, KH, KW] (fp32 master or its 16-bit shadow), mode 0 = forward rows, 1 = data-gradient rows of a
-        stride-1 (or dilated) convolution, 2 = data-gradient rows of a patchify convolution; `prec` selects the operand type."""
+        stride-1 (or dilated) convolution, 2 = data-gradient rows of a patchify convolution (3: the depthwise tap table, mirrored);
+        `prec` selects the operand type."""
         from . import lib as L
-        w = weight.detach()
-        if w.dim() == 2:
-            w = w[:, :, None, None]
-        w = w.contiguous()
+        w = _oihw(weight).contiguous()
         N, Cin, KH, KW = w.shape
         n_pad = N if n_pad is None else n_pad
-        self = cls.__new__(cls)
-        gran = 32 if prec == "f32" else 64
         if mode == 0:
-            if patchify:
-                assert stride == KH == KW and pad == 0
-                self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = KH, 1, KW * Cin, KH, 1, 0, 0, KW
-            else:
-                self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = KH, KW, Cin, stride, stride, pad, pad, 1
-            rows, K = n_pad, KH * KW * Cin
-            self.N = n_pad
-        elif mode == 1:  # transposed convolution of (dilated) dY: Cin output channels, n_pad input channels, mirrored taps, padding KH-1-pad
-            self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = KH, KW, n_pad, 1, 1, KH - 1 - pad, KW - 1 - pad, 1
-            rows, K = Cin, KH * KW * n_pad
-            self.N = Cin
-        else:  # mode 2 / 3, patchify: dY rows @ [(ky,kx,c)][n] (Cin = 1: the depthwise tap table [KH*KW][C], mode 3 mirrored)
-            self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = 1, 1, n_pad, 1, 1, 0, 0, 1
-            rows, K = KH * KW * Cin, n_pad
-            self.N = rows
-        self.K = K
-        kp = (K + gran - 1) // gran * gran
-        self.Kp = (K + 31) // 32 * 32  # (the fp32 descriptor's row length; the 16-bit operand carries its own, see as16)
-        tdt = torch.float32 if prec == "f32" else _TDT[prec]
-        buf = torch.empty(rows, kp, device=w.device, dtype=tdt)
+            geom = ConvGeom.forward(n_pad, Cin, KH, KW, stride, pad, patchify)
+        elif mode == 1:
+            geom = ConvGeom.dgrad(Cin, n_pad, KH, KW, pad)
+        else:
+            geom = ConvGeom.dgrad_rows(Cin, n_pad, KH, KW)
+        tdt, kp = (torch.float32, geom.Kp) if prec == "f32" else (_TDT[prec], geom.Kp16)
+        buf = torch.empty(geom.N, kp, device=w.device, dtype=tdt)
         L.check(L.load().kpf_pack_conv_weight(w.data_ptr(), _KDT[w.dtype], buf.data_ptr(), _KDT[tdt], N, Cin, KH, KW, mode, n_pad, kp,
                                               torch.cuda.current_stream().cuda_stream), "kpf_pack_conv_weight")
-        self.w, self.w16 = (buf, None) if prec == "f32" else (None, buf)
-        self.b = bias.detach().float().contiguous() if bias is not None else None
-        self.tuned = {}
-        return self
+        return Pack(geom, b=_fp32_bias(bias), **{"w" if prec == "f32" else "w16": buf})
 
     @classmethod
     def from_rows(cls, rows, KH, KW, Cin, pad):
         """Stride-1 convolution whose weight is already in kernel order: rows [N][(ky,kx,c)] (no bias)."""
-        self = cls.__new__(cls)
-        N, K = rows.shape
-        assert K == KH * KW * Cin
-        self.KH, self.KW, self.Cin, self.sh, self.sw, self.ph, self.pw, self.merge = KH, KW, Cin, 1, 1, pad, pad, 1
-        self.N, self.K, self.Kp = N, K, (K + 31) // 32 * 32
-        self._set_rows(rows)
-        self.b = None
-        self.tuned = {}
-        return self
+        assert rows.shape[1] == KH * KW * Cin
+        geom = ConvGeom.rows(rows.shape[0], KH, KW, Cin, pad)
+        return Pack(geom, **cls._rows(geom, rows))
 
-    def flops(self, M):
-        return 2.0 * M * self.N * self.K
 
-    def as16(self, tdt):
-        """The object engine16.conv16() takes: 16-bit rows [N][Kp64] of the same weights."""
-        kp = (self.K + 63) // 64 * 64
-        if self.w16 is not None:
-            assert self.w16.dtype == tdt and self.w16.shape[1] == kp
-            return type("P16", (), {"pc": self, "Kp": kp, "w": self.w16})()
-        w = self.w[:, :self.K]
-        w16 = (w if kp == self.K else F.pad(w, (0, kp - self.K))).to(tdt).contiguous()
-        return type("P16", (), {"pc": self, "Kp": kp, "w": w16})()
+class StackedPack(Pack):
+    """q | k | v as ONE forward operand [3C][Kp]; .dgrad: the matching data-gradient operand [K][3C] (PackCache.get_stacked)."""
+
+    def __init__(self, geom, w, b, dgrad):
+        super().__init__(geom, w=w, b=b)
+        self.dgrad, self._table = dgrad, None
 
 
 _TDT = {"bf16": torch.bfloat16, "f16": torch.float16}
@@ -677,13 +638,13 @@ class PackCache:
         else:
             assert w.is_contiguous(), "PackCache: a registered source must be a contiguous view of parameter storage"
             pc = DevPack.packed(w, None, mode, prec, **kw)
-            w4 = w if w.dim() == 4 else w[:, :, None, None]
+            w4 = _oihw(w)
             buf = pc.w if pc.w is not None else pc.w16
             self.entries[key] = {"src": w.data_ptr(), "shape": tuple(w.shape), "prec": prec, "pc": pc, "keep": w,
                                  "desc": (w.data_ptr(), buf.data_ptr(), w4.shape[0], w4.shape[1], w4.shape[2], w4.shape[3], mode,
                                           kw.get("n_pad") or w4.shape[0], buf.shape[1], buf.shape[0], _KDT[w.dtype], _KDT[buf.dtype])}
             self.dirty = True
-        pc.b = bias.detach().float().contiguous() if bias is not None else None
+        pc.b = _fp32_bias(bias)
         return pc
 
     def get_stacked(self, names, weights, biases):
@@ -700,21 +661,12 @@ class PackCache:
         n, (Cn, K) = len(weights), weights[0].shape
         dev = weights[0].device
         assert all(w.shape == (Cn, K) and w.dtype == torch.float32 and w.is_contiguous() for w in weights) and Cn % 32 == 0 and K % 4 == 0
-        kp = (K + 31) // 32 * 32
+        geom = ConvGeom.plain(n * Cn, K, 1, 1)
+        kp = geom.Kp
         buf0 = torch.zeros(n * Cn, kp, device=dev)
         buf1 = torch.zeros(K, n * Cn, device=dev)
         bufb = torch.zeros(n * Cn, device=dev)
-        sp = type("StackedPack", (), {})()
-        sp.KH = sp.KW = sp.sh = sp.sw = sp.merge = 1
-        sp.ph = sp.pw = 0
-        sp.Cin, sp.K, sp.Kp, sp.N, sp.w, sp.w16, sp.b, sp.ps, sp.pt, sp.tuned, sp.split_allowed = K, K, kp, n * Cn, buf0, None, bufb, None, None, {}, False
-        sp.flops = lambda M: 2.0 * M * n * Cn * K
-        dg = type("StackedPack", (), {})()
-        dg.KH = dg.KW = dg.sh = dg.sw = dg.merge = 1
-        dg.ph = dg.pw = 0
-        dg.Cin, dg.K, dg.Kp, dg.N, dg.w, dg.w16, dg.b, dg.ps, dg.pt, dg.tuned, dg.split_allowed = n * Cn, n * Cn, n * Cn, K, buf1, None, None, None, None, {}, False
-        dg.flops = lambda M: 2.0 * M * n * Cn * K
-        sp.dgrad = dg
+        sp = StackedPack(geom, buf0, bufb, Pack(ConvGeom.plain(K, n * Cn, 1, 1), w=buf1))  # (Cn % 32 == 0: the data-gradient rows need no padding)
         new = []
         for i, (w, b) in enumerate(zip(weights, biases)):
             w, b = w.detach(), b.detach()
@@ -802,14 +754,14 @@ def _conv_any(pc, x4, prec, out_ld=None, res=None, flags=0, out2=None):
     is [B, OH, OW, out_ld] with only the first N channels written."""
     from .engine import Act, conv
     B, H, W, Cc = x4.shape
-    G = getattr(pc, "groups", 1)
+    G = pc.groups or 1
     if prec == "f32" and _HEAD_MMA[0]:
         flags |= _HEAD_MMA[0]
     if out_ld is not None and out_ld != pc.N:
         assert G == 1 and pc.merge == 1
         tdt, kdt = (None, None) if prec == "f32" else __import__("keypointfusion_amd.engine16", fromlist=["DTYPES"]).DTYPES[prec]
         xb = (x4 if prec == "f32" else x4.to(tdt)).contiguous().view(-1)
-        OH, OW = (H + 2 * pc.ph - pc.KH) // pc.sh + 1, (W + 2 * pc.pw - pc.KW) // pc.sw + 1
+        OH, OW = pc.geom.out_hw(H, W)
         ob = torch.empty(B * OH * OW * out_ld, device=x4.device, dtype=xb.dtype)
         oa = Act(ob, B, OH, OW, pc.N, ld=out_ld)
         if prec == "f32":
@@ -830,7 +782,7 @@ def _conv_any(pc, x4, prec, out_ld=None, res=None, flags=0, out2=None):
         xb = (x4 if prec == "f32" else x4.to(tdt)).contiguous().view(-1)
     if G > 1:
         assert Cc == G * pc.Cin and pc.merge == 1, (Cc, G, pc.Cin)
-        OH, OW = (H + 2 * pc.ph - pc.KH) // pc.sh + 1, (W + 2 * pc.pw - pc.KW) // pc.sw + 1
+        OH, OW = pc.geom.out_hw(H, W)
         xa = Act(xb, B, H, W, pc.Cin, ld=Cc)
         ob = torch.empty(B * OH * OW * G * pc.N, device=x4.device, dtype=xb.dtype)
         oa = Act(ob, B, OH, OW, pc.N, ld=G * pc.N)
@@ -889,52 +841,26 @@ def nchw_to_nhwc_padded(x_nchw, cpad):
     return out
 
 
-class _OddPack:
+class _OddPack(Pack):
     """A Linear operand whose input width is not a whole channel group, seen by the GEMM at the padded width: the packed rows [N][Kp] are zero
     beyond K anyway (Kp >= the padded width), so only the descriptor changes — the activation rows carry the matching zero channels."""
 
     def __init__(self, pc, cin_pad):
-        self.__dict__.update(pc.__dict__)
-        self.Cin = self.K = cin_pad
-        self.tuned = {}
-        self._base = pc
-
-    split_allowed = False
-    ps = pt = None
-
-    def flops(self, M):
-        return 2.0 * M * self.N * self.K
-
-    def as16(self, tdt):
-        return type("P16", (), {"pc": self, "Kp": self.w16.shape[1], "w": self.w16})()
+        super().__init__(pc.geom.widened(cin_pad), w=pc.w, w16=pc.w16, b=pc.b)
 
 
-class GroupedPack:
-    """G kernel-layout operands of the same shape as ONE launch descriptor (kpf_conv_desc::groups): the attributes of group 0's DevPack plus
+class GroupedPack(Pack):
+    """G kernel-layout operands of the same shape as ONE launch descriptor (kpf_conv_desc::groups): group 0's geometry and rows plus
     the element distance to the next group's packed matrix (the G buffers are separate allocations; they only have to be equally spaced)."""
 
     def __init__(self, pcs, bias):
-        p0 = pcs[0]
-        self.__dict__.update({k: getattr(p0, k) for k in ("KH", "KW", "Cin", "sh", "sw", "ph", "pw", "merge", "N", "K", "Kp", "w", "w16")})
-        self.ps = self.pt = None
-        self.split_allowed = False
-        self.tuned = {}
-        self.groups = len(pcs)
-        self.pcs = pcs  # (keeps the G operands alive)
         bufs = [pc.w if pc.w is not None else pc.w16 for pc in pcs]
         es = bufs[0].element_size()
         step = (bufs[1].data_ptr() - bufs[0].data_ptr()) // es
         for a, b in zip(bufs, bufs[1:]):
             assert a.shape == b.shape and a.dtype == b.dtype and (b.data_ptr() - a.data_ptr()) == step * es and step % 8 == 0, "GroupedPack: operands are not equally spaced"
-        self.w_gstride = step
-        self.b = bias.detach().float().contiguous() if bias is not None else None  # [G*N]
-
-    def flops(self, M):
-        return 2.0 * M * self.N * self.K
-
-    def as16(self, tdt):
-        assert self.w16 is not None and self.w16.dtype == tdt
-        return type("P16", (), {"pc": self, "Kp": self.w16.shape[1], "w": self.w16})()
+        super().__init__(pcs[0].geom, w=pcs[0].w, w16=pcs[0].w16, b=_fp32_bias(bias), groups=len(pcs), w_gstride=step)  # b: [G*N]
+        self.pcs = pcs  # (keeps the G operands alive)
 
 
 def _grouped_pack(cache, key, weight, bias, G, mode, prec, **kw):
@@ -2759,9 +2685,9 @@ class Conv2dNHWC(torch.autograd.Function):
     forward : kpf_conv2d_f32 (f32-input MFMA implicit GEMM).
     backward: dX  = kpf_conv2d_f32 of dY with the spatially flipped, channel-transposed weight (stride 1, any padding); for patchify
                     convolutions (kernel == stride, pad 0) a 1x1 GEMM dY @ W[N][(ky,kx,c)] followed by the pixel un-shuffle;
-              dW  = dY^T X as a library GEMM for 1x1, torch.nn.grad.conv2d_weight otherwise (weight gradients are plain reductions
-                    over pixels: not on the hand-written path yet);
-              db  = sum of dY over pixels.
+              dW  = the hand-written split-K weight gradient (conv_wgrad_hip, fp32 accumulation in every precision mode; small Linears join
+                    DeferredParamGrads' grouped launch), db from the same pass; only widths that are not whole channel groups of 4
+                    fall back to a library GEMM (1x1) / torch.nn.grad.conv2d_weight and a sum of dY over pixels.
     Linear layers are the 1x1 case on a [rows, 1, 1, K] view."""
 
     @staticmethod
