@@ -29,7 +29,7 @@ extern "C" {
 #define KPF_DT_F32 0
 #define KPF_DT_BF16 1
 #define KPF_DT_F16 2
-/* kpf_conv2d_wgrad_groups / _deferred only (ABI 17): fp32 operands, the products taken on their bf16 / f16 roundings (16-bit MFMA, fp32 accumulation) — the weight
+/* kpf_conv2d_wgrad only (ABI 17): fp32 operands, the products taken on their bf16 / f16 roundings (16-bit MFMA, fp32 accumulation) — the weight
  * gradient of a layer whose forward ran with KPF_MMA_BF16 / _F16; honoured by the 64 x 64 tile form, fp32 products otherwise */
 #define KPF_DT_F32_MMA_BF16 8
 #define KPF_DT_F32_MMA_F16 9
@@ -336,26 +336,38 @@ int kpf_cast_f32_h16(const float* src, void* dst, int dtype, long n, void* strea
  *     dw[n][c][ky][kx] = sum_{b,oy,ox} dy[b][oy][ox][n] * x[b][oy*sh+ky-ph][ox*sw+kx-pw][c]      (OIHW, PyTorch's layout)
  *     db[n]            = sum_{b,oy,ox} dy[b][oy][ox][n]                                           (db may be NULL)
  * dy: NHWC [B][OH][OW] with pixel stride ldy (N channels used), x: NHWC [B][H][W] with pixel stride ldx (Cin channels used);
- * Cin, N, ldx, ldy multiples of 4, 16-byte aligned pointers.  fp32 on v_mfma_f32_16x16x4_f32, split over the pixel range with a
- * fixed-order (run-to-run deterministic) reduction through `ws` (>= kpf_conv2d_wgrad_ws_floats(B*OH*OW, N, KH*KW*Cin) floats).
+ * Cin, N, ldx, ldy multiples of 4, 16-byte aligned pointers.  Split over the pixel range with a fixed-order (run-to-run deterministic)
+ * reduction through `ws` (>= groups * kpf_conv2d_wgrad_ws_floats(B*OH*OW, N, KH*KW*Cin) floats).
+ * dtype (both operands): KPF_DT_F32 — fp32 on v_mfma_f32_16x16x4_f32; KPF_DT_BF16 / _F16 (mixed-precision training; Cin, N, ldx, ldy % 8 == 0) —
+ *   16-bit storage, products and sums are the fp32 ones (the master weight's gradient is not rounded); KPF_DT_F32_MMA_BF16 / _F16 — see their definition.
+ * groups (1..64; ABI 13; the data-parallel twin of kpf_conv_desc::groups): G channel-stacked weight gradients in one launch.  Group g multiplies
+ *   dy[.., g*N + n] (pixel stride ldy >= G*N) with x[.., g*Cin + c] (pixel stride ldx >= G*Cin) and writes dw[g][N][Cin][KH][KW], db[g][N].  Same kernels as
+ *   G separate calls on the channel slices; fp32 operands also keep their split and summation order (bit-identical results), 16-bit operands split the
+ *   pixel range for 1/G of the chip each (same sums, another order).
+ * cin_valid / n_valid (0 = all of Cin / N): the operands carry zero channels up to whole channel groups (the 3-, 105-, 131-, 149-wide layers of the fusion
+ *   head, model/model.py:99-104, 254-262) and dw [n_valid][cin_valid][KH][KW], db [n_valid] are written without them.
+ * reduce == NULL: the call launches its own reduce and dw / db are written when it returns (in stream order).
+ * reduce != NULL (ABI 17; `loss.backward()` of train.py:262 issues ~100 weight-gradient GEMMs whose partial sums each needed a 5-us reduce launch): the
+ *   call launches the split GEMM only and describes the pending reduce in *reduce (kind < 0: the call wrote dw itself, nothing is pending).  Until
+ *   kpf_wgrad_reduce_multi has run on the same stream, dw / db are UNWRITTEN and ws belongs to the pending reduce.  kpf_wgrad_reduce_multi sums
+ *   in the order the per-call reduce does: the gradients have the same bits either way.
  */
+#define KPF_WGRAD_REDUCE_BATCH 24
+typedef struct kpf_wgrad_reduce_desc {
+  const float* part;   /* [S][N*K] partial tiles ([S][49][C] for the depthwise form) */
+  const float* dbpart; /* [S][N] or NULL */
+  float* dw;
+  float* db;
+  long g_ws;           /* floats between the workspaces of consecutive channel groups */
+  int S, N, K, Cin, KHW, nkb, ndb, groups, Cin_out, N_out;
+  int kind;            /* 0 convolution / Linear, 1 depthwise 7x7 (N = C), < 0 nothing pending */
+  int first_block;     /* filled by kpf_wgrad_reduce_multi */
+} kpf_wgrad_reduce_desc;
 long kpf_conv2d_wgrad_ws_floats(long M, int N, int K);
-int kpf_conv2d_wgrad_f32(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int Cin,
-                         int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, void* stream);
-/* The same with dy and x in 16-bit storage (dtype = KPF_DT_BF16 / KPF_DT_F16; mixed-precision training): values are widened to fp32
- * on the way into LDS, products and sums are the fp32 ones (the master weight's gradient is not rounded).  Cin, N, ldx, ldy % 8 == 0. */
-int kpf_conv2d_wgrad_h16(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int Cin,
-                         int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, void* stream);
-
-/* G channel-stacked weight gradients in one launch (ABI 13; the data-parallel twin of kpf_conv_desc::groups): group g multiplies
- * dy[.., g*N + n] (pixel stride ldy >= G*N) with x[.., g*Cin + c] (pixel stride ldx >= G*Cin) and writes dw[g][N][Cin][KH][KW], db[g][N]
- * (db may be NULL).  Same kernels as G separate kpf_conv2d_wgrad_f32 / _h16 calls on the channel slices; fp32 operands also keep their split and
- * summation order (bit-identical results), 16-bit operands split the pixel range for 1/G of the chip each (same sums, another order).
- * ws_floats >= G * kpf_conv2d_wgrad_ws_floats(M, N, K).  dtype: KPF_DT_F32 / _BF16 / _F16 (both operands). */
-int kpf_conv2d_wgrad_groups(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int groups, int B, int H, int W, int Cin,
-                            int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid, void* stream);
-/* cin_valid / n_valid (0 = Cin / N): the operands carry zero channels up to whole channel groups (the 3-, 105-, 131-, 149-wide layers of the fusion
- * head, model/model.py:99-104, 254-262) and dw [n_valid][cin_valid][KH][KW], db [n_valid] are written without them. */
+int kpf_conv2d_wgrad(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int groups, int B, int H, int W, int Cin,
+                     int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid,
+                     kpf_wgrad_reduce_desc* reduce /* nullable */, void* stream);
+int kpf_wgrad_reduce_multi(const kpf_wgrad_reduce_desc* descs, int n, void* stream);
 
 /* Row pad / column-slice copy / type change in one launch, and the pose tokens of a fusion block at their padded width (csrc/kpf_train.hip). */
 int kpf_pad_rows(const void* src, int src_dtype, void* dst, int dst_dtype, long rows, int C, int src_ld, int Cp, void* stream);
@@ -382,34 +394,12 @@ int kpf_gate_mix_backward(const float* sw, const float* gam, const float* weight
 int kpf_dwconv7_f32(const float* x, const float* w_dw, const float* b_dw, float* y, int B, int H, int W, int C, void* stream);
 /* the same + addend (y's shape) on the output: the data gradient of a ConvNeXt block with the skip path's gradient folded in */
 int kpf_dwconv7_add_f32(const float* x, const float* w_dw, const float* b_dw, const float* addend, float* y, int B, int H, int W, int C, void* stream);
-/* The same for the ConvNeXt block's depthwise 7x7 (pad 3): dw [C][7][7] (= PyTorch's [C][1][7][7]), db [C] or NULL; dy, x dense NHWC
- * [B][H][W][C], C % 4 == 0; ws >= kpf_dwconv7_wgrad_ws_floats(B, H, C) floats. */
+/* The weight gradient of the ConvNeXt block's depthwise 7x7 (pad 3): dw [C][7][7] (= PyTorch's [C][1][7][7]), db [C] or NULL; dy, x dense NHWC
+ * [B][H][W][C], C % 4 == 0; ws >= kpf_dwconv7_wgrad_ws_floats(B, H, C) floats.  reduce (nullable): as kpf_conv2d_wgrad's — NULL reduces at once,
+ * otherwise dw / db stay UNWRITTEN until kpf_wgrad_reduce_multi. */
 long kpf_dwconv7_wgrad_ws_floats(int B, int H, int C);
-int kpf_dwconv7_wgrad_f32(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
-                          void* stream);
-
-/* Split weight gradients with the fixed-order reduce of MANY calls in one launch (ABI 17; `loss.backward()` of train.py:262 issues ~100 weight-gradient
- * GEMMs whose partial sums each needed a 5-us reduce launch).  kpf_conv2d_wgrad_deferred / kpf_dwconv7_wgrad_deferred are kpf_conv2d_wgrad_groups /
- * kpf_dwconv7_wgrad_f32 without the reduce: they launch the split GEMM and describe the pending reduce in *reduce (kind < 0: the call wrote dw itself,
- * nothing is pending).  Until kpf_wgrad_reduce_multi has run on the same stream, dw / db are UNWRITTEN and ws belongs to the pending reduce.
- * kpf_wgrad_reduce_multi sums in the order the per-call reduce does: the gradients have the same bits either way. */
-#define KPF_WGRAD_REDUCE_BATCH 24
-typedef struct kpf_wgrad_reduce_desc {
-  const float* part;   /* [S][N*K] partial tiles ([S][49][C] for the depthwise form) */
-  const float* dbpart; /* [S][N] or NULL */
-  float* dw;
-  float* db;
-  long g_ws;           /* floats between the workspaces of consecutive channel groups */
-  int S, N, K, Cin, KHW, nkb, ndb, groups, Cin_out, N_out;
-  int kind;            /* 0 convolution / Linear, 1 depthwise 7x7 (N = C), < 0 nothing pending */
-  int first_block;     /* filled by kpf_wgrad_reduce_multi */
-} kpf_wgrad_reduce_desc;
-int kpf_conv2d_wgrad_deferred(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int groups, int B, int H, int W, int Cin,
-                              int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid,
-                              kpf_wgrad_reduce_desc* reduce, void* stream);
-int kpf_dwconv7_wgrad_deferred(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
-                               kpf_wgrad_reduce_desc* reduce, void* stream);
-int kpf_wgrad_reduce_multi(const kpf_wgrad_reduce_desc* descs, int n, void* stream);
+int kpf_dwconv7_wgrad(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
+                      kpf_wgrad_reduce_desc* reduce /* nullable */, void* stream);
 
 /*
  * BatchNorm with batch statistics (+ optional ReLU) on NHWC rows x [M][C], forward and backward: nn.BatchNorm2d / BatchNorm1d in
@@ -426,12 +416,10 @@ long kpf_bn_ws_floats(long M, int C);
 int kpf_bn_train_forward(const void* x, int x_dtype, const float* w, const float* b, void* y, int y_dtype, float* mean, float* invstd,
                          float* running_mean, float* running_var, float momentum, float eps, int relu, float* ws, long ws_floats, long M, int C,
                          void* stream);
+/* addend (x's type and shape; nullable): dx += addend, a second gradient of x — the skip path of a Residual block — folded in */
 int kpf_bn_train_backward(const void* dy, const void* x, const void* y, int x_dtype, int y_dtype, const float* mean, const float* invstd,
-                          const float* w, void* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C, void* stream);
-/* the same with dx += addend (x's type and shape; nullable): a second gradient of x — the skip path of a Residual block — folded in */
-int kpf_bn_train_backward_add(const void* dy, const void* x, const void* y, int x_dtype, int y_dtype, const float* mean, const float* invstd,
-                              const float* w, const void* addend, void* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C,
-                              void* stream);
+                          const float* w, const void* addend, void* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C,
+                          void* stream);
 /* Training (ABI 17): the embedding sums of a fusion block with their BatchNorms (batch statistics) inside: x [rows][n C], n = n1 + n2 <= 4 sibling Linear outputs side by
  * side (C % 4 == 0, C <= 256), out [rows][C] = relu(S1) (n2 == 0) or relu(relu(S1) + S2) with S1 / S2 the sums of the first n1 / next n2 normalised blocks
  * (model/model.py:254-259, 417-422) — one pass over the pre-activations forward, two backward; w, b, dw, db, running statistics: [n C]; stats [2][n C] = mean, invstd. */
@@ -458,11 +446,6 @@ int kpf_bn2_add_relu_forward(const float* xa, const float* xb, const float* wa, 
                              void* stream);
 int kpf_bn2_add_relu_backward(const float* dy, const float* out, const float* xa, const float* xb, const float* stats, const float* wa, const float* wb, float* dxa,
                               float* dxb, float* dwa, float* dba, float* dwb, float* dbb, float* ws, long ws_floats, long M, int C, void* stream);
-int kpf_bn_train_forward_f32(const float* x, const float* w, const float* b, float* y, float* mean, float* invstd, float* running_mean,
-                             float* running_var, float momentum, float eps, int relu, float* ws, long ws_floats, long M, int C,
-                             void* stream);
-int kpf_bn_train_backward_f32(const float* dy, const float* x, const float* y, const float* mean, const float* invstd, const float* w,
-                              float* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C, void* stream);
 
 /*
  * Training: data-movement ops of the train-mode forward with a run-to-run deterministic backward (gather form, fixed
@@ -510,11 +493,6 @@ int kpf_slices_sum_relu_backward(const float* dout, const float* out, const floa
 int kpf_group_max_train_forward(const float* x, float* y, unsigned char* arg, long rows, int group, int C, void* stream);
 int kpf_group_max_train_backward(const float* dy, int dy_ld /* floats between rows of dy: it may be a column slice of a wider matrix */, const unsigned char* arg, float* dx,
                                  long rows, int group, int C, void* stream);
-long kpf_ln_ws_floats(long rows, int C);
-int kpf_ln_train_forward(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean, float* rstd, long rows, int C, float eps,
-                         void* stream);
-int kpf_ln_train_backward(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
-                          float* db, float* ws, long ws_floats, long rows, int C, void* stream);
 int kpf_gelu_forward(const void* x, void* y, int dtype, long n, void* stream);
 int kpf_gelu_backward(const void* dy, const void* x, void* dx, int dtype, long n, void* stream);
 
@@ -523,15 +501,12 @@ int kpf_gelu_backward(const void* dy, const void* x, void* dx, int dtype, long n
  * [B*T][ld] fp32 with head h in channels [h*hd, (h+1)*hd) (the projections' own layout: no head transposes); T = 21, hd = 32.  P
  * [B][H][T][T] fp32 and the keep mask M (bytes) are kept for the backward.  p_drop > 0: masks from a hash of (rng[0] = seed, rng[1] =
  * counter advanced by the host once per forward, call_id, element); rng is a device pointer to two int64. */
-int kpf_attn21_forward(const float* q, const float* k, const float* v, float* ctx, float* P, unsigned char* M, int B, int T, int H, int hd, int ld,
+/* q / k / v (dq / dk / dv) have row stride ld, ctx (dctx) its own row stride ldc (ABI 13): the three projections may be column slices of one [rows][3C]
+ * GEMM output (ld = 3C, ldc = C); separate dense tensors pass ldc = ld. */
+int kpf_attn21_forward(const float* q, const float* k, const float* v, float* ctx, float* P, unsigned char* M, int B, int T, int H, int hd, int ld, int ldc,
                        float scale, float p_drop, const long* rng, int call_id, void* stream);
 int kpf_attn21_backward(const float* dctx, const float* q, const float* k, const float* v, const float* P, const unsigned char* M, float* dq, float* dk,
-                        float* dv, int B, int T, int H, int hd, int ld, float scale, float p_drop, void* stream);
-/* The same pair with q / k / v (dq / dk / dv) at row stride ld and ctx (dctx) at its own row stride ldc (ABI 13). */
-int kpf_attn21_forward_ld(const float* q, const float* k, const float* v, float* ctx, float* P, unsigned char* M, int B, int T, int H, int hd, int ld, int ldc,
-                          float scale, float p_drop, const long* rng, int call_id, void* stream);
-int kpf_attn21_backward_ld(const float* dctx, const float* q, const float* k, const float* v, const float* P, const unsigned char* M, float* dq, float* dk,
-                           float* dv, int B, int T, int H, int hd, int ld, int ldc, float scale, float p_drop, void* stream);
+                        float* dv, int B, int T, int H, int hd, int ld, int ldc, float scale, float p_drop, void* stream);
 
 /* Training: dX[b] (P x C) = A[b]^T (P x J) @ dOut[b] (J x C) for small J (<= 64; J = 21 joints): the operand gradient of the per-sample
  * products of model/model.py:318-320 and 336-341 (a K = J batched GEMM the library handles badly).  fp32, C % 4 == 0, J * C * 4 B <= 64 KB. */
@@ -541,14 +516,6 @@ int kpf_bmm_small_k_dx(const float* A, const float* dOut, float* dX, int B, int 
    their autograd backward; fixed summation order. */
 int kpf_bmm_small_k_fwd(const float* A, const float* X, float* out, int B, int J, int P, int C, void* stream);
 int kpf_bmm_small_k_da(const float* dOut, const float* X, float* dA, int B, int J, int P, int C, void* stream);
-
-/* Training: layer scale + residual of the ConvNeXt block, out = x + gamma * y (convNeXT/convnext.py:48-51): x / out / g fp32 [rows][C], y / dy in
- * y_dtype (fp32 or the 16-bit GEMM storage type), gamma / dgamma [C].  backward: dy = g * gamma, dgamma = column sums of g * y added in a
- * fixed order through ws (>= kpf_layer_scale_ws_floats(rows, C) floats); C % 4 == 0, C <= 1024. */
-long kpf_layer_scale_ws_floats(long rows, int C);
-int kpf_layer_scale_forward(const float* x, const void* y, int y_dtype, const float* gamma, float* out, long rows, int C, void* stream);
-int kpf_layer_scale_backward(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
-                             long rows, int C, void* stream);
 
 /* Training: the dense-stage loss (train.py:211-224 with GFM.joint2offset / offset2joint_weight, util/generateFeature.py:59-84,166-195, and
  * model/loss.py's SmoothL1): pd [B][5J][F][F] fp32 NCHW (3J unit offsets (j, xyz), J heat maps, J weight logits), img [B][1][S][S], uvd_gt
@@ -633,7 +600,7 @@ int kpf_loss_scale_update(float* scale_dev, float* inv_scale_dev, int* tracker_d
  * dw[N][K] = dy[M][N]^T x[M][K], db[N] = column sums of dy (db nullable), fp32, N % 4 == K % 4 == 0, rows contiguous.  A workgroup owns a
  * 64 x 64 tile of one problem and walks all M rows (no split, no reduce launch) — meant for M up to ~1000 (the 21-token stacks of the
  * fusion head: M = 21 B), where a launch pair per layer costs more than the arithmetic; the row range is still summed in the splits of
- * kpf_conv2d_wgrad_f32 and the split sums in split order, so both forms return the same bits.  descs: HOST array. */
+ * kpf_conv2d_wgrad and the split sums in split order, so both forms return the same bits.  descs: HOST array. */
 #define KPF_WGRAD_GROUP_BATCH 64
 typedef struct kpf_wgrad_group_desc {
   const float* dy;
@@ -645,10 +612,11 @@ typedef struct kpf_wgrad_group_desc {
 } kpf_wgrad_group_desc;
 int kpf_linear_wgrad_grouped(const kpf_wgrad_group_desc* descs, int n, void* stream);
 
-/* Training: the column-sum reduce behind every LayerNorm / layer-scale backward (d gamma, d beta) for many layers in one launch.  The
- * _partial forms of kpf_ln_train_backward / kpf_layer_scale_backward run everything but that reduce, leave the per-workgroup partial sums
- * in `ws` (which must stay alive) and fill `desc`; kpf_colsum_reduce_grouped(descs: HOST array) performs them KPF_COLSUM_BATCH per
- * launch with the arithmetic of the immediate form (same bits). */
+/* Training: the column-sum reduce behind every LayerNorm / layer-scale backward (d gamma, d beta) for many layers in one launch.
+ * kpf_ln_train_backward / kpf_layer_scale_backward / kpf_drop_add_ln_backward with desc != NULL run everything but that reduce, leave the
+ * per-workgroup partial sums in `ws` (which must stay alive) and fill `desc`: dw / db (dgamma) are UNWRITTEN until
+ * kpf_colsum_reduce_grouped(descs: HOST array) performs the reduces, KPF_COLSUM_BATCH per launch, with the arithmetic of the immediate form
+ * (same bits).  desc == NULL: the call launches its own reduce. */
 #define KPF_COLSUM_BATCH 96
 typedef struct kpf_colsum_desc {
   const float* part; /* [nblk][2][C] */
@@ -659,34 +627,35 @@ typedef struct kpf_colsum_desc {
                         embedding table [L][C] written as the table's whole gradient: part = the [B][T*C] tensor read as [B][2][T*C/2], dw = the table's gradient,
                         db = dw + T*C/2, reserved = (L - T) * C (model/model.py:84 position embeddings; model/transfusion_head.py:150-152) */
 } kpf_colsum_desc;
-int kpf_ln_train_backward_partial(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
-                                  float* db, float* ws, long ws_floats, long rows, int C, kpf_colsum_desc* desc, void* stream);
+int kpf_colsum_reduce_grouped(const kpf_colsum_desc* descs, int n, void* stream);
 
-/* LayerNorm with G parameter sets (ABI 13): row r is normalised with set r % G, i.e. w, b, dw, db hold [G][C] — what a LayerNorm over each of
- * the G channel groups of a [pixels][G*C] tensor is when that tensor is read as [pixels*G][C] rows (the paired backbones of the training
- * step).  G in {1, 2, 4}, rows % G == 0; G = 1 is kpf_ln_train_forward / _backward.  ws_floats >= kpf_ln_ws_floats(rows, G*C).
- * desc != NULL: the column-sum reduce is described instead of launched (kpf_ln_train_backward_partial's contract, C -> G*C). */
-int kpf_ln_train_forward_g(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean, float* rstd, long rows, int C, int G,
-                           float eps, void* stream);
-int kpf_ln_train_backward_g(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
-                            float* db, float* ws, long ws_floats, long rows, int C, int G, kpf_colsum_desc* desc, void* stream);
+/* LayerNorm over fp32 rows of C (C % 4 == 0, C <= 1024), y in y_dtype, mean / rstd [rows] kept for the backward (dy in dy_dtype; dx fp32; dw / db summed
+ * in a fixed order through ws).  G parameter sets (ABI 13): row r is normalised with set r % G, i.e. w, b, dw, db hold [G][C] — what a LayerNorm over
+ * each of the G channel groups of a [pixels][G*C] tensor is when that tensor is read as [pixels*G][C] rows (the paired backbones of the training
+ * step).  G in {1, 2, 4}, rows % G == 0; G = 1 is the plain LayerNorm.  ws_floats >= kpf_ln_ws_floats(rows, G*C).  desc: nullable, see above (C -> G*C). */
+long kpf_ln_ws_floats(long rows, int C);
+int kpf_ln_train_forward(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean, float* rstd, long rows, int C, int G,
+                         float eps, void* stream);
+int kpf_ln_train_backward(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
+                          float* db, float* ws, long ws_floats, long rows, int C, int G, kpf_colsum_desc* desc, void* stream);
 
 /* y = LayerNorm(h + dropout(o)) in one launch each way (ABI 13; model/model.py:30-126: dense -> dropout -> residual add -> LayerNorm, both halves of a
  * BERT layer).  fp32 rows of C (C % 4 == 0, C <= 1024); xs = h + dropout(o) [rows][C], the keep mask [rows][C] bytes (NULL when p_drop == 0) and
  * mean / rstd [rows] are kept for the backward; rng: the device-resident (seed, counter) pair of kpf_attn21_forward, call_id a per-site constant.
- * backward: dh = d xs, d_o = d xs * mask / (1 - p), dw / db [C]; ws_floats >= kpf_ln_ws_floats(rows, C); desc as kpf_ln_train_backward_partial. */
+ * backward: dh = d xs, d_o = d xs * mask / (1 - p), dw / db [C]; ws_floats >= kpf_ln_ws_floats(rows, C); desc as kpf_ln_train_backward. */
 int kpf_drop_add_ln_forward(const float* o, const float* h, const float* w, const float* b, float* xs, float* y, unsigned char* mask, float* mean, float* rstd,
                             long rows, int C, float eps, float p_drop, const long* rng, int call_id, void* stream);
 int kpf_drop_add_ln_backward(const float* dy, const float* xs, const float* mean, const float* rstd, const float* w, const unsigned char* mask, float* dh,
                              float* d_o, float* dw, float* db, float* ws, long ws_floats, long rows, int C, float p_drop, kpf_colsum_desc* desc, void* stream);
-/* The layer-scale backward with G parameter sets (same row-view convention as kpf_ln_train_backward_g: rows counts [rows][C] rows of a
- * [rows / G][G*C] tensor, gamma / dgamma hold [G][C]); ws_floats >= kpf_layer_scale_ws_floats(rows, G*C).  The forward needs no twin
- * (kpf_layer_scale_forward with C := G*C). */
-int kpf_layer_scale_backward_g(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
-                               long rows, int C, int G, kpf_colsum_desc* desc /* nullable: as kpf_layer_scale_backward_partial */, void* stream);
-int kpf_layer_scale_backward_partial(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
-                                     long rows, int C, kpf_colsum_desc* desc, void* stream);
-int kpf_colsum_reduce_grouped(const kpf_colsum_desc* descs, int n, void* stream);
+/* Layer scale + residual of the ConvNeXt block, out = x + gamma * y (convNeXT/convnext.py:48-51): x / out / g fp32 [rows][C], y / dy in
+ * y_dtype (fp32 or the 16-bit GEMM storage type), gamma / dgamma [C]; C % 4 == 0, C <= 1024.  backward: dy = g * gamma, dgamma = column sums of
+ * g * y added in a fixed order through ws.  G parameter sets (G in {1, 2, 4}, rows % G == 0; same row-view convention as kpf_ln_train_backward:
+ * rows counts [rows][C] rows of a [rows / G][G*C] tensor, gamma / dgamma hold [G][C]); ws_floats >= kpf_layer_scale_ws_floats(rows, G*C).
+ * The forward needs no G (call it with C := G*C).  desc: nullable, see above. */
+long kpf_layer_scale_ws_floats(long rows, int C);
+int kpf_layer_scale_forward(const float* x, const void* y, int y_dtype, const float* gamma, float* out, long rows, int C, void* stream);
+int kpf_layer_scale_backward(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
+                             long rows, int C, int G, kpf_colsum_desc* desc, void* stream);
 
 /* Training (ABI 16): the four BERT layers of a KP_Interaction_TR stack (21 tokens x 128, 4 heads x 32, intermediate 16, GELU-erf, post-LN eps 1e-12,
  * hidden / attention dropout p_drop) as ONE launch per direction — replaces model/model.py:30-126 (transformers' BertEncoder under .train()) between the
@@ -783,7 +752,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 18
+#define KPF_ABI_VERSION 19
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -693,7 +693,7 @@ constexpr int LN_MAXQ = 4;  // channel quads per lane: C <= 64 * 4 * LN_MAXQ = 1
 template <typename TY>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, TY* __restrict__ y,
                                                      float* __restrict__ mean, float* __restrict__ rstd, long rows, int C4, float eps, int G) {
-  // G > 1 (kpf_ln_train_forward_g): row r is normalised with parameter set r % G (w, b hold G sets of C) — channel-stacked groups seen as rows
+  // G > 1 (kpf_ln_train_forward): row r is normalised with parameter set r % G (w, b hold G sets of C) — channel-stacked groups seen as rows
   const int lane = threadIdx.x & 63;
   const float invC = 1.0f / (float)(4 * C4);
   const int po = (int)(((long)blockIdx.x * 4 + (threadIdx.x >> 6)) % G) * 4 * C4;  // (the row stride is a multiple of 4: one parameter set per wave)
@@ -898,10 +898,10 @@ inline int ln_blocks(long rows) {  // one row per wave for the small (B x 21)-ro
 
 extern "C" long kpf_ln_ws_floats(long rows, int C) { return (long)ln_blocks(rows) * 2 * C; }
 
-extern "C" int kpf_ln_train_forward_g(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean, float* rstd, long rows, int C, int G,
-                                      float eps, void* stream) {
+extern "C" int kpf_ln_train_forward(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean, float* rstd, long rows, int C, int G,
+                                    float eps, void* stream) {
   KPF_REQUIRE(x && w && b && y && mean && rstd && rows > 0 && C > 0 && C % 4 == 0 && C <= 256 * LN_MAXQ, "kpf_ln_train_forward: bad arguments (C %% 4 == 0, C <= 1024)");
-  KPF_REQUIRE((G == 1 || G == 2 || G == 4) && rows % G == 0, "kpf_ln_train_forward_g: G must be 1, 2 or 4 and divide the row count");
+  KPF_REQUIRE((G == 1 || G == 2 || G == 4) && rows % G == 0, "kpf_ln_train_forward: G must be 1, 2 or 4 and divide the row count");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid(grid_for(rows, 4, 256 * 16));
   if (y_dtype == KPF_DT_F32) hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, dim3(256), 0, st, x, w, b, static_cast<float*>(y), mean, rstd, rows, C / 4, eps, G);
@@ -914,16 +914,11 @@ extern "C" int kpf_ln_train_forward_g(const float* x, const float* w, const floa
   return kpf_check_launch("kpf_ln_train_forward");
 }
 
-extern "C" int kpf_ln_train_forward(const float* x, const float* w, const float* b, void* y, int y_dtype, float* mean, float* rstd, long rows, int C, float eps,
-                                    void* stream) {
-  return kpf_ln_train_forward_g(x, w, b, y, y_dtype, mean, rstd, rows, C, 1, eps, stream);
-}
-
 static int ln_train_backward_impl(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
                                   float* db, float* ws, long ws_floats, long rows, int C, void* stream, kpf_colsum_desc* defer, int G = 1) {
   // G > 1: w, dw, db hold G parameter sets of C; row r belongs to set r % G
   KPF_REQUIRE(dy && x && mean && rstd && w && dx && dw && db && ws && rows > 0 && C > 0 && C % 4 == 0 && C <= 256 * LN_MAXQ, "kpf_ln_train_backward: bad arguments");
-  KPF_REQUIRE((G == 1 || G == 2 || G == 4) && rows % G == 0, "kpf_ln_train_backward_g: G must be 1, 2 or 4 and divide the row count");
+  KPF_REQUIRE((G == 1 || G == 2 || G == 4) && rows % G == 0, "kpf_ln_train_backward: G must be 1, 2 or 4 and divide the row count");
   const int nblk = ln_blocks(rows);
   KPF_REQUIRE(ws_floats >= (long)nblk * 2 * C * G, "kpf_ln_train_backward: workspace too small");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -945,20 +940,9 @@ static int ln_train_backward_impl(const void* dy, int dy_dtype, const float* x, 
   return kpf_check_launch("kpf_ln_train_backward (reduce)");
 }
 
-extern "C" int kpf_ln_train_backward_g(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
-                                       float* db, float* ws, long ws_floats, long rows, int C, int G, kpf_colsum_desc* desc, void* stream) {
-  return ln_train_backward_impl(dy, dy_dtype, x, mean, rstd, w, dx, dw, db, ws, ws_floats, rows, C, stream, desc, G);
-}
-
 extern "C" int kpf_ln_train_backward(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
-                                     float* db, float* ws, long ws_floats, long rows, int C, void* stream) {
-  return ln_train_backward_impl(dy, dy_dtype, x, mean, rstd, w, dx, dw, db, ws, ws_floats, rows, C, stream, nullptr);
-}
-
-extern "C" int kpf_ln_train_backward_partial(const void* dy, int dy_dtype, const float* x, const float* mean, const float* rstd, const float* w, float* dx, float* dw,
-                                             float* db, float* ws, long ws_floats, long rows, int C, kpf_colsum_desc* desc, void* stream) {
-  KPF_REQUIRE(desc, "kpf_ln_train_backward_partial: desc missing");
-  return ln_train_backward_impl(dy, dy_dtype, x, mean, rstd, w, dx, dw, db, ws, ws_floats, rows, C, stream, desc);
+                                     float* db, float* ws, long ws_floats, long rows, int C, int G, kpf_colsum_desc* desc, void* stream) {
+  return ln_train_backward_impl(dy, dy_dtype, x, mean, rstd, w, dx, dw, db, ws, ws_floats, rows, C, stream, desc, G);
 }
 
 extern "C" int kpf_colsum_reduce_grouped(const kpf_colsum_desc* descs, int n, void* stream) {
@@ -1140,34 +1124,19 @@ __global__ __launch_bounds__(AT_NT) void attn21_bwd_kernel(const float* __restri
 }
 }  // namespace
 
+/* q / k / v (and dq / dk / dv) with row stride ld, ctx (and dctx) with its own row stride ldc: the three projections may be column slices of ONE
+ * [rows][3C] GEMM output (training.SelfAttention21: one projection launch, one data-gradient launch per layer instead of three each). */
 extern "C" int kpf_attn21_forward(const float* q, const float* k, const float* v, float* ctx, float* P, unsigned char* M, int B, int T, int H, int hd, int ld,
-                                  float scale, float p_drop, const long* rng, int call_id, void* stream) {
-  KPF_REQUIRE(q && k && v && ctx && P && M && B > 0 && T == AT_T && hd == AT_HD && H > 0 && ld >= H * hd, "kpf_attn21_forward: needs 21 tokens and 32-wide heads");
+                                  int ldc, float scale, float p_drop, const long* rng, int call_id, void* stream) {
+  KPF_REQUIRE(q && k && v && ctx && P && M && B > 0 && T == AT_T && hd == AT_HD && H > 0 && ld >= H * hd && ldc >= H * hd, "kpf_attn21_forward: needs 21 tokens and 32-wide heads");
   KPF_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || rng), "kpf_attn21_forward: dropout needs 0 <= p < 1 and the rng state");
-  hipLaunchKernelGGL(attn21_fwd_kernel, dim3(B * H), dim3(AT_NT), 0, reinterpret_cast<hipStream_t>(stream), q, k, v, ctx, P, M, H, ld, scale, p_drop, rng, call_id, ld);
+  hipLaunchKernelGGL(attn21_fwd_kernel, dim3(B * H), dim3(AT_NT), 0, reinterpret_cast<hipStream_t>(stream), q, k, v, ctx, P, M, H, ld, scale, p_drop, rng, call_id, ldc);
   return kpf_check_launch("kpf_attn21_forward");
 }
-
-/* q / k / v (and dq / dk / dv) with row stride ld, ctx (and dctx) with its own row stride ldc: the three projections as column slices of ONE
- * [rows][3C] GEMM output (training.SelfAttention21: one projection launch, one data-gradient launch per layer instead of three each). */
-extern "C" int kpf_attn21_forward_ld(const float* q, const float* k, const float* v, float* ctx, float* P, unsigned char* M, int B, int T, int H, int hd, int ld,
-                                     int ldc, float scale, float p_drop, const long* rng, int call_id, void* stream) {
-  KPF_REQUIRE(q && k && v && ctx && P && M && B > 0 && T == AT_T && hd == AT_HD && H > 0 && ld >= H * hd && ldc >= H * hd, "kpf_attn21_forward_ld: needs 21 tokens and 32-wide heads");
-  KPF_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || rng), "kpf_attn21_forward_ld: dropout needs 0 <= p < 1 and the rng state");
-  hipLaunchKernelGGL(attn21_fwd_kernel, dim3(B * H), dim3(AT_NT), 0, reinterpret_cast<hipStream_t>(stream), q, k, v, ctx, P, M, H, ld, scale, p_drop, rng, call_id, ldc);
-  return kpf_check_launch("kpf_attn21_forward_ld");
-}
-extern "C" int kpf_attn21_backward_ld(const float* dctx, const float* q, const float* k, const float* v, const float* P, const unsigned char* M, float* dq, float* dk,
-                                      float* dv, int B, int T, int H, int hd, int ld, int ldc, float scale, float p_drop, void* stream) {
-  KPF_REQUIRE(dctx && q && k && v && P && M && dq && dk && dv && B > 0 && T == AT_T && hd == AT_HD && H > 0 && ld >= H * hd && ldc >= H * hd, "kpf_attn21_backward_ld: bad arguments");
-  hipLaunchKernelGGL(attn21_bwd_kernel, dim3(B * H), dim3(AT_NT), 0, reinterpret_cast<hipStream_t>(stream), dctx, q, k, v, P, M, dq, dk, dv, H, ld, scale, p_drop, ldc);
-  return kpf_check_launch("kpf_attn21_backward_ld");
-}
-
 extern "C" int kpf_attn21_backward(const float* dctx, const float* q, const float* k, const float* v, const float* P, const unsigned char* M, float* dq, float* dk,
-                                   float* dv, int B, int T, int H, int hd, int ld, float scale, float p_drop, void* stream) {
-  KPF_REQUIRE(dctx && q && k && v && P && M && dq && dk && dv && B > 0 && T == AT_T && hd == AT_HD && H > 0 && ld >= H * hd, "kpf_attn21_backward: bad arguments");
-  hipLaunchKernelGGL(attn21_bwd_kernel, dim3(B * H), dim3(AT_NT), 0, reinterpret_cast<hipStream_t>(stream), dctx, q, k, v, P, M, dq, dk, dv, H, ld, scale, p_drop, ld);
+                                   float* dv, int B, int T, int H, int hd, int ld, int ldc, float scale, float p_drop, void* stream) {
+  KPF_REQUIRE(dctx && q && k && v && P && M && dq && dk && dv && B > 0 && T == AT_T && hd == AT_HD && H > 0 && ld >= H * hd && ldc >= H * hd, "kpf_attn21_backward: bad arguments");
+  hipLaunchKernelGGL(attn21_bwd_kernel, dim3(B * H), dim3(AT_NT), 0, reinterpret_cast<hipStream_t>(stream), dctx, q, k, v, P, M, dq, dk, dv, H, ld, scale, p_drop, ldc);
   return kpf_check_launch("kpf_attn21_backward");
 }
 
@@ -1439,7 +1408,7 @@ __global__ __launch_bounds__(256) void layer_scale_bwd_kernel(const float* __res
   extern __shared__ float ls_lds[];  // [4 waves][C]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int C = 4 * C4;
-  gamma += (wave % G) * C;  // G > 1 (kpf_layer_scale_backward_g): row r uses parameter set r % G; a wave's rows are all of one set (see ln_bwd_kernel)
+  gamma += (wave % G) * C;  // G > 1 (kpf_layer_scale_backward): row r uses parameter set r % G; a wave's rows are all of one set (see ln_bwd_kernel)
   f32x4 acc[LN_MAXQ], gm[LN_MAXQ];
 #pragma unroll
   for (int i = 0; i < LN_MAXQ; ++i) {
@@ -1511,30 +1480,12 @@ extern "C" int kpf_layer_scale_forward(const float* x, const void* y, int y_dtyp
 }
 
 extern "C" int kpf_layer_scale_backward(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
-                                        long rows, int C, void* stream) {
+                                        long rows, int C, int G, kpf_colsum_desc* desc, void* stream) {
   KPF_REQUIRE(g && y && gamma && dy && dgamma && ws && rows > 0 && C > 0 && C % 4 == 0 && C <= 256 * LN_MAXQ, "kpf_layer_scale_backward: bad arguments (C <= 1024)");
-  KPF_REQUIRE(ws_floats >= kpf_layer_scale_ws_floats(rows, C), "kpf_layer_scale_backward: workspace too small");
-#define CALL(T) layer_scale_bwd_launch<T>(g, y, gamma, dy, dgamma, ws, rows, C, stream)
-  KPF_DISPATCH_DT(y_dtype, "kpf_layer_scale_backward", CALL);
-#undef CALL
-}
-
-extern "C" int kpf_layer_scale_backward_g(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
-                                          long rows, int C, int G, kpf_colsum_desc* desc, void* stream) {
-  KPF_REQUIRE(g && y && gamma && dy && dgamma && ws && rows > 0 && C > 0 && C % 4 == 0 && C <= 256 * LN_MAXQ, "kpf_layer_scale_backward_g: bad arguments (C <= 1024)");
-  KPF_REQUIRE((G == 1 || G == 2 || G == 4) && rows % G == 0, "kpf_layer_scale_backward_g: G must be 1, 2 or 4 and divide the row count");
-  KPF_REQUIRE(ws_floats >= kpf_layer_scale_ws_floats(rows, G * C), "kpf_layer_scale_backward_g: workspace too small");
+  KPF_REQUIRE((G == 1 || G == 2 || G == 4) && rows % G == 0, "kpf_layer_scale_backward: G must be 1, 2 or 4 and divide the row count");
+  KPF_REQUIRE(ws_floats >= kpf_layer_scale_ws_floats(rows, G * C), "kpf_layer_scale_backward: workspace too small");
 #define CALL(T) layer_scale_bwd_launch<T>(g, y, gamma, dy, dgamma, ws, rows, C, stream, desc, G)
-  KPF_DISPATCH_DT(y_dtype, "kpf_layer_scale_backward_g", CALL);
-#undef CALL
-}
-
-extern "C" int kpf_layer_scale_backward_partial(const float* g, const void* y, int y_dtype, const float* gamma, void* dy, float* dgamma, float* ws, long ws_floats,
-                                                long rows, int C, kpf_colsum_desc* desc, void* stream) {
-  KPF_REQUIRE(g && y && gamma && dy && dgamma && ws && desc && rows > 0 && C > 0 && C % 4 == 0 && C <= 256 * LN_MAXQ, "kpf_layer_scale_backward_partial: bad arguments");
-  KPF_REQUIRE(ws_floats >= kpf_layer_scale_ws_floats(rows, C), "kpf_layer_scale_backward_partial: workspace too small");
-#define CALL(T) layer_scale_bwd_launch<T>(g, y, gamma, dy, dgamma, ws, rows, C, stream, desc)
-  KPF_DISPATCH_DT(y_dtype, "kpf_layer_scale_backward_partial", CALL);
+  KPF_DISPATCH_DT(y_dtype, "kpf_layer_scale_backward", CALL);
 #undef CALL
 }
 

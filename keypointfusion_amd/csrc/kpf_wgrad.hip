@@ -11,7 +11,7 @@
 //     (split-K); partial tiles go to a workspace and wgrad_reduce_kernel sums them in a fixed order (deterministic, no atomics)
 //     while permuting (ky,kx,c) -> the reference's OIHW weight layout.  db = sum_m dY[m][n] falls out of the dY fragments.
 //     With 16-bit dY / X (mixed-precision step) the same kernel stages through registers instead (16-byte loads of 8 values in
-//     flight under the previous tile's MFMAs, widened to fp32 on the way into LDS): kpf_conv2d_wgrad_h16.
+//     flight under the previous tile's MFMAs, widened to fp32 on the way into LDS): kpf_conv2d_wgrad.
 // (2) dwconv7_wgrad_kernel — depthwise 7x7: 49 x C outputs, HBM/L2-bound; thread = (4 channels, tap row ky), sliding 14-pixel
 //     window in registers, partial sums per (image, row band) chunk, same fixed-order reduce.
 // (3) bn_*_kernel — train-mode BatchNorm (+ ReLU) forward / backward on NHWC rows, fp32 or 16-bit storage on either side
@@ -38,7 +38,7 @@ struct WgradArgs {
   int is1x1;
   int xcd;       // wgrad_h16s_kernel: XCD-aware tile order (xcd_slab_remap)
   int emul_sps;  // grouped form only: stages per split of the split + reduce form whose summation order it reproduces
-  // channel-grouped launch (kpf_conv2d_wgrad_groups, grid.z = group): group g reads dy + g*g_dy / x + g*g_x (elements) and writes part + g*g_part,
+  // channel-grouped launch (kpf_conv2d_wgrad, grid.z = group): group g reads dy + g*g_dy / x + g*g_x (elements) and writes part + g*g_part,
   // dbpart + g*g_db (floats).  All zero for an ordinary launch (blockIdx.z is 0 there).
   int groups, g_dy, g_x;
   long g_part, g_db;
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256) void wgrad_r16_kernel(const WgradArgs a) {  //
 // iteration cost 8 us + a 6-us reduce launch EACH as separate launches, for 0.1 GFLOP in all.  Here one launch carries up to
 // KPF_WGRAD_GROUP_BATCH problems (descriptors by value, read from the kernel-argument segment); a workgroup owns one 64 x 64 tile of
 // one problem, walks all its pixel stages (no split, no reduce: for a 1x1 the tile IS a piece of dW) and every problem's tiles run side
-// by side.  Issued once after backward by training.GroupedLinearWgrad with the (dY, X) pairs it kept alive.
+// by side.  Issued once after backward by training.DeferredParamGrads with the (dY, X) pairs it kept alive.
 struct WgradGroupBatch {
   kpf_wgrad_group_desc d[KPF_WGRAD_GROUP_BATCH];
   const float* zero;
@@ -1263,20 +1263,20 @@ static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw
   KPF_REQUIRE(cin_valid <= Cin && n_valid <= N, "kpf_conv2d_wgrad: cin_valid / n_valid exceed Cin / N");
   const bool trimmed = cin_valid != Cin || n_valid != N;
   KPF_REQUIRE(groups >= 1 && (long)groups * Cin <= ldx && (long)groups * N <= ldy, "kpf_conv2d_wgrad: %d groups of %d / %d channels exceed the pixel strides %d / %d", groups, Cin, N, ldx, ldy);
-  KPF_REQUIRE(dy && x && dw && ws, "kpf_conv2d_wgrad_f32: null pointer");
+  KPF_REQUIRE(dy && x && dw && ws, "kpf_conv2d_wgrad: null pointer");
   int r16 = 0;  // KPF_DT_F32_MMA_BF16 / _F16: fp32 operands, products on their 16-bit roundings
   if (dtype == KPF_DT_F32_MMA_BF16 || dtype == KPF_DT_F32_MMA_F16) r16 = dtype == KPF_DT_F32_MMA_BF16 ? 1 : 2, dtype = KPF_DT_F32;
   KPF_REQUIRE(dtype == KPF_DT_F32 || dtype == KPF_DT_BF16 || dtype == KPF_DT_F16, "kpf_conv2d_wgrad: unknown dtype %d", dtype);
   if (dtype != KPF_DT_F32)
-    KPF_REQUIRE(Cin % 8 == 0 && ldx % 8 == 0 && N % 8 == 0 && ldy % 8 == 0, "kpf_conv2d_wgrad_h16: Cin, N, ldx, ldy must be multiples of 8");
-  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && KH > 0 && KW > 0 && sh > 0 && sw > 0, "kpf_conv2d_wgrad_f32: bad shape");
-  KPF_REQUIRE(Cin > 0 && Cin % 4 == 0 && ldx % 4 == 0 && ldx >= Cin, "kpf_conv2d_wgrad_f32: Cin and ldx must be multiples of 4 (got %d, %d)", Cin, ldx);
-  KPF_REQUIRE(N > 0 && N % 4 == 0 && ldy % 4 == 0 && ldy >= N, "kpf_conv2d_wgrad_f32: N and ldy must be multiples of 4 (got %d, %d)", N, ldy);
-  KPF_REQUIRE(kpf_aligned16(dy) && kpf_aligned16(x) && kpf_aligned16(ws), "kpf_conv2d_wgrad_f32: dy, x, ws must be 16-byte aligned");
-  KPF_REQUIRE(OH == (H + 2 * ph - KH) / sh + 1 && OW == (W + 2 * pw - KW) / sw + 1, "kpf_conv2d_wgrad_f32: output size %dx%d does not match the convolution", OH, OW);
+    KPF_REQUIRE(Cin % 8 == 0 && ldx % 8 == 0 && N % 8 == 0 && ldy % 8 == 0, "kpf_conv2d_wgrad: Cin, N, ldx, ldy must be multiples of 8");
+  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && KH > 0 && KW > 0 && sh > 0 && sw > 0, "kpf_conv2d_wgrad: bad shape");
+  KPF_REQUIRE(Cin > 0 && Cin % 4 == 0 && ldx % 4 == 0 && ldx >= Cin, "kpf_conv2d_wgrad: Cin and ldx must be multiples of 4 (got %d, %d)", Cin, ldx);
+  KPF_REQUIRE(N > 0 && N % 4 == 0 && ldy % 4 == 0 && ldy >= N, "kpf_conv2d_wgrad: N and ldy must be multiples of 4 (got %d, %d)", N, ldy);
+  KPF_REQUIRE(kpf_aligned16(dy) && kpf_aligned16(x) && kpf_aligned16(ws), "kpf_conv2d_wgrad: dy, x, ws must be 16-byte aligned");
+  KPF_REQUIRE(OH == (H + 2 * ph - KH) / sh + 1 && OW == (W + 2 * pw - KW) / sw + 1, "kpf_conv2d_wgrad: output size %dx%d does not match the convolution", OH, OW);
   const long M = (long)B * OH * OW;
   const long K = (long)KH * KW * Cin;
-  KPF_REQUIRE(M < (1L << 31) && K < (1L << 24) && (long)B * H * W < (1L << 31), "kpf_conv2d_wgrad_f32: problem too large");
+  KPF_REQUIRE(M < (1L << 31) && K < (1L << 24) && (long)B * H * W < (1L << 31), "kpf_conv2d_wgrad: problem too large");
   static const int h16_widen = []() { const char* e = getenv("KPF_WGRAD_H16_WIDEN"); return e ? atoi(e) : 0; }();  // tuning aid: the old widening kernel
   // 16-bit operands: the 64-tile form (wgrad_h16s_kernel, two buffers = two workgroups per CU) — GEMM + reduce of a ConvNeXt-T iteration
   // 3.01 ms against 3.51 for the 128-tile form (a quarter of the partial-sum traffic, no split at all for the layers whose tiles fill the
@@ -1293,13 +1293,13 @@ static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw
   if (big) p.S = 1, p.sps = (int)((M + RB - 1) / RB);
   const bool direct = one && p.S == 1 && !trimmed;  // the single partial array is dW
   const long wsg = (long)p.S * N * K + (long)p.S * N;  // one group's workspace
-  KPF_REQUIRE(ws_floats >= groups * wsg, "kpf_conv2d_wgrad_f32: workspace too small (%ld floats, need %ld)", ws_floats, groups * wsg);
+  KPF_REQUIRE(ws_floats >= groups * wsg, "kpf_conv2d_wgrad: workspace too small (%ld floats, need %ld)", ws_floats, groups * wsg);
   WgradArgs a;
   a.dy = dy, a.x = x, a.part = direct ? dw : ws, a.dbpart = db ? (direct ? db : ws + (size_t)p.S * N * K) : nullptr;
   a.groups = groups, a.g_dy = groups > 1 ? N : 0, a.g_x = groups > 1 ? Cin : 0;
   a.g_part = groups > 1 ? (direct ? (long)N * K : wsg) : 0, a.g_db = groups > 1 ? (direct ? (long)N : wsg) : 0;
   a.zero = zero_page();
-  KPF_REQUIRE(a.zero, "kpf_conv2d_wgrad_f32: cannot resolve the zero page");
+  KPF_REQUIRE(a.zero, "kpf_conv2d_wgrad: cannot resolve the zero page");
   a.H = H, a.W = W, a.Cin = Cin, a.ldx = ldx, a.OH = OH, a.OW = OW, a.N = N, a.ldy = ldy, a.KH = KH, a.KW = KW;
   a.sh = sh, a.sw = sw, a.ph = ph, a.pw = pw, a.M = (int)M, a.K = (int)K, a.tilesK = p.tilesK, a.stages_per_split = p.sps;
   a.is1x1 = KH == 1 && KW == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && OH == H && OW == W;
@@ -1317,13 +1317,13 @@ static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw
       if (dtype == KPF_DT_BF16) hipLaunchKernelGGL((wgrad_h16s_kernel<bf16_t, 2>), grid, dim3(256), 2 * WB + 1024, st, a);
       else hipLaunchKernelGGL((wgrad_h16s_kernel<f16_t, 2>), grid, dim3(256), 2 * WB + 1024, st, a);
     } else if (dtype == KPF_DT_BF16) {
-      KPF_REQUIRE(kpf_raise_lds_limit(reinterpret_cast<const void*>(&wgrad_h16s_kernel<bf16_t, 3>), lds_ok[0]), "kpf_conv2d_wgrad_h16: cannot raise the LDS limit");
+      KPF_REQUIRE(kpf_raise_lds_limit(reinterpret_cast<const void*>(&wgrad_h16s_kernel<bf16_t, 3>), lds_ok[0]), "kpf_conv2d_wgrad: cannot raise the LDS limit");
       hipLaunchKernelGGL((wgrad_h16s_kernel<bf16_t, 3>), grid, dim3(256), 3 * WB + 1024, st, a);
     } else {
-      KPF_REQUIRE(kpf_raise_lds_limit(reinterpret_cast<const void*>(&wgrad_h16s_kernel<f16_t, 3>), lds_ok[1]), "kpf_conv2d_wgrad_h16: cannot raise the LDS limit");
+      KPF_REQUIRE(kpf_raise_lds_limit(reinterpret_cast<const void*>(&wgrad_h16s_kernel<f16_t, 3>), lds_ok[1]), "kpf_conv2d_wgrad: cannot raise the LDS limit");
       hipLaunchKernelGGL((wgrad_h16s_kernel<f16_t, 3>), grid, dim3(256), 3 * WB + 1024, st, a);
     }
-    rc = kpf_check_launch("kpf_conv2d_wgrad_h16");
+    rc = kpf_check_launch("kpf_conv2d_wgrad");
   } else if (h16) {
     static const int ring = []() { const char* e = getenv("KPF_WG16_RING"); return e ? atoi(e) : 3; }();  // tuning aid: 3 or 4 stages
     const dim3 grid(p.tilesN * p.tilesK, p.S, groups);
@@ -1334,7 +1334,7 @@ static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw
       if (dtype == KPF_DT_BF16) hipLaunchKernelGGL((wgrad_h16_kernel<bf16_t, 3>), grid, dim3(256), 3 * 2 * RB * 256, st, a);
       else hipLaunchKernelGGL((wgrad_h16_kernel<f16_t, 3>), grid, dim3(256), 3 * 2 * RB * 256, st, a);
     }
-    rc = kpf_check_launch("kpf_conv2d_wgrad_h16");
+    rc = kpf_check_launch("kpf_conv2d_wgrad");
   } else {
     rc = dtype == KPF_DT_F32 ? launch_wgrad_any<float>(a, p, st, r16)
                              : (dtype == KPF_DT_BF16 ? launch_wgrad_any<bf16_t>(a, p, st) : launch_wgrad_any<f16_t>(a, p, st));
@@ -1350,31 +1350,13 @@ static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw
   }
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nkb + ndb, groups), dim3(256), 0, st, ws, a.dbpart, dw, db, p.S, N, (int)K, Cin,
                      KH * KW, nkb, wsg, cin_valid, n_valid);
-  return kpf_check_launch("kpf_conv2d_wgrad_f32 (reduce)");
+  return kpf_check_launch("kpf_conv2d_wgrad (reduce)");
 }
 
-int kpf_conv2d_wgrad_f32(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int Cin,
-                         int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, void* stream) {
-  return conv2d_wgrad_impl(dy, x, KPF_DT_F32, dw, db, ws, ws_floats, B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, sh, sw, ph, pw, stream);
-}
-
-int kpf_conv2d_wgrad_h16(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int Cin,
-                         int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, void* stream) {
-  KPF_REQUIRE(dtype == KPF_DT_BF16 || dtype == KPF_DT_F16, "kpf_conv2d_wgrad_h16: dtype must be KPF_DT_BF16 or KPF_DT_F16");
-  return conv2d_wgrad_impl(dy, x, dtype, dw, db, ws, ws_floats, B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, sh, sw, ph, pw, stream);
-}
-
-int kpf_conv2d_wgrad_groups(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int groups, int B, int H, int W, int Cin,
-                            int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid, void* stream) {
-  KPF_REQUIRE(groups >= 1 && groups <= 64, "kpf_conv2d_wgrad_groups: 1..64 groups");
-  return conv2d_wgrad_impl(dy, x, dtype, dw, db, ws, ws_floats, B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, sh, sw, ph, pw, stream, groups, cin_valid, n_valid);
-}
-
-int kpf_conv2d_wgrad_deferred(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int groups, int B, int H, int W, int Cin,
-                              int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid,
-                              kpf_wgrad_reduce_desc* reduce, void* stream) {
-  KPF_REQUIRE(groups >= 1 && groups <= 64, "kpf_conv2d_wgrad_deferred: 1..64 groups");
-  KPF_REQUIRE(reduce, "kpf_conv2d_wgrad_deferred: null descriptor");
+int kpf_conv2d_wgrad(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int groups, int B, int H, int W, int Cin,
+                     int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid,
+                     kpf_wgrad_reduce_desc* reduce, void* stream) {
+  KPF_REQUIRE(groups >= 1 && groups <= 64, "kpf_conv2d_wgrad: 1..64 groups");
   return conv2d_wgrad_impl(dy, x, dtype, dw, db, ws, ws_floats, B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, sh, sw, ph, pw, stream, groups, cin_valid, n_valid, reduce);
 }
 
@@ -1442,9 +1424,9 @@ long kpf_dwconv7_wgrad_ws_floats(int B, int H, int C) {
 static int dwconv7_wgrad_impl(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
                               kpf_wgrad_reduce_desc* defer, void* stream) {
   if (defer) defer->kind = -1;
-  KPF_REQUIRE(dy && x && dw && ws, "kpf_dwconv7_wgrad_f32: null pointer");
-  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "kpf_dwconv7_wgrad_f32: bad shape (C %% 4 == 0)");
-  KPF_REQUIRE(kpf_aligned16(dy) && kpf_aligned16(x) && kpf_aligned16(ws), "kpf_dwconv7_wgrad_f32: dy, x, ws must be 16-byte aligned");
+  KPF_REQUIRE(dy && x && dw && ws, "kpf_dwconv7_wgrad: null pointer");
+  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "kpf_dwconv7_wgrad: bad shape (C %% 4 == 0)");
+  KPF_REQUIRE(kpf_aligned16(dy) && kpf_aligned16(x) && kpf_aligned16(ws), "kpf_dwconv7_wgrad: dy, x, ws must be 16-byte aligned");
   static const int lds_form = []() { const char* e = getenv("KPF_DW7_WGRAD_LDS"); return e ? atoi(e) : 1; }();  // tuning aid: 0 = the register-window kernel
   const DwlGeom gm = dwl_geom(W, C);
   bool use_lds = lds_form && gm.CQ >= 1 && (size_t)gm.lds_f4 * 16 <= 80 * 1024 && W * gm.CQ <= 512;  // (80 KB: two workgroups per CU)
@@ -1454,14 +1436,14 @@ static int dwconv7_wgrad_impl(const float* dy, const float* x, float* dw, float*
   }
   const int rpc = use_lds ? dwl_chunk_rows(B, H, C) : dw_chunk_rows(B, H, C);
   const int S = (int)(((long)B * H + rpc - 1) / rpc);
-  KPF_REQUIRE(ws_floats >= (long)S * 50 * C, "kpf_dwconv7_wgrad_f32: workspace too small");
+  KPF_REQUIRE(ws_floats >= (long)S * 50 * C, "kpf_dwconv7_wgrad: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   float* dbpart = ws + (size_t)S * 49 * C;
   if (use_lds)
     hipLaunchKernelGGL(dwconv7_wgrad_lds_kernel, dim3(((C >> 2) + gm.CQ - 1) / gm.CQ, S), dim3(256), (size_t)gm.lds_f4 * 16, st, dy, x, ws, dbpart, B, H, W, C, rpc);
   else
     hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3((7 * (C / 4) + 255) / 256, S), dim3(256), 0, st, dy, x, ws, dbpart, B, H, W, C, rpc);
-  int rc = kpf_check_launch("kpf_dwconv7_wgrad_f32");
+  int rc = kpf_check_launch("kpf_dwconv7_wgrad");
   if (rc != KPF_OK) return rc;
   const int nkb = reduce_blocks(49L * C, S), ndb = db ? reduce_blocks(C, S) : 0;
   if (defer) {
@@ -1471,17 +1453,11 @@ static int dwconv7_wgrad_impl(const float* dy, const float* x, float* dw, float*
     return KPF_OK;
   }
   hipLaunchKernelGGL(dwconv7_wgrad_reduce_kernel, dim3(nkb + ndb), dim3(256), 0, st, ws, dbpart, dw, db, S, C, nkb);
-  return kpf_check_launch("kpf_dwconv7_wgrad_f32 (reduce)");
+  return kpf_check_launch("kpf_dwconv7_wgrad (reduce)");
 }
 
-int kpf_dwconv7_wgrad_f32(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
-                          void* stream) {
-  return dwconv7_wgrad_impl(dy, x, dw, db, ws, ws_floats, B, H, W, C, nullptr, stream);
-}
-
-int kpf_dwconv7_wgrad_deferred(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
-                               kpf_wgrad_reduce_desc* reduce, void* stream) {
-  KPF_REQUIRE(reduce, "kpf_dwconv7_wgrad_deferred: null descriptor");
+int kpf_dwconv7_wgrad(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
+                      kpf_wgrad_reduce_desc* reduce, void* stream) {
   return dwconv7_wgrad_impl(dy, x, dw, db, ws, ws_floats, B, H, W, C, reduce, stream);
 }
 
@@ -2234,26 +2210,9 @@ static int bn_train_backward_any(const void* dy, const void* x, const void* y, i
 }
 
 int kpf_bn_train_backward(const void* dy, const void* x, const void* y, int x_dtype, int y_dtype, const float* mean, const float* invstd,
-                          const float* w, void* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C, void* stream) {
-  return bn_train_backward_any(dy, x, y, x_dtype, y_dtype, mean, invstd, w, dx, dw, db, relu, ws, ws_floats, M, C, stream, nullptr);
-}
-
-int kpf_bn_train_backward_add(const void* dy, const void* x, const void* y, int x_dtype, int y_dtype, const float* mean, const float* invstd,
-                              const float* w, const void* addend, void* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C,
-                              void* stream) {
+                          const float* w, const void* addend, void* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C,
+                          void* stream) {
   return bn_train_backward_any(dy, x, y, x_dtype, y_dtype, mean, invstd, w, dx, dw, db, relu, ws, ws_floats, M, C, stream, addend);
-}
-
-int kpf_bn_train_forward_f32(const float* x, const float* w, const float* b, float* y, float* mean, float* invstd, float* running_mean,
-                             float* running_var, float momentum, float eps, int relu, float* ws, long ws_floats, long M, int C,
-                             void* stream) {
-  return kpf_bn_train_forward(x, KPF_DT_F32, w, b, y, KPF_DT_F32, mean, invstd, running_mean, running_var, momentum, eps, relu, ws, ws_floats, M, C,
-                              stream);
-}
-
-int kpf_bn_train_backward_f32(const float* dy, const float* x, const float* y, const float* mean, const float* invstd, const float* w,
-                              float* dx, float* dw, float* db, int relu, float* ws, long ws_floats, long M, int C, void* stream) {
-  return kpf_bn_train_backward(dy, x, y, KPF_DT_F32, KPF_DT_F32, mean, invstd, w, dx, dw, db, relu, ws, ws_floats, M, C, stream);
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ KPF_RELU_AFTER_RES = 16
 KPF_RES_GELU_GRAD = 1024
 KPF_ACT_GELU_SAVE = 2048
 KPF_PRO_LN = 4096
-KPF_DT_F32_MMA_BF16, KPF_DT_F32_MMA_F16 = 8, 9  # weight gradients of fp32 operands on their 16-bit roundings (kpf_conv2d_wgrad_groups / _deferred)
+KPF_DT_F32_MMA_BF16, KPF_DT_F32_MMA_F16 = 8, 9  # weight gradients of fp32 operands on their 16-bit roundings (kpf_conv2d_wgrad)
 KPF_MMA_BF16, KPF_MMA_F16 = 8192, 16384  # kpf_conv2d_f32: fp32 storage, products on operands rounded to 16 bits in registers (ABI 17)
 KPF_OUT_NCHW = 32
 KPF_ACT_LEAKY = 64
@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 18  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 19  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -111,18 +111,12 @@ _SIGS = {
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],
     "kpf_xattn_weight_floats": [],
-    "kpf_conv2d_wgrad_f32": [_P] * 5 + [C.c_long] + [C.c_int] * 15 + [_P],
     "kpf_bn_train_forward": [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_float, C.c_float, C.c_int, _P, C.c_long, C.c_long, C.c_int, _P],
-    "kpf_bn_train_backward": [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_long, C.c_long, C.c_int, _P],
-    "kpf_bn_train_backward_add": [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_long, C.c_long, C.c_int, _P],
-    "kpf_bn_train_forward_f32": [_P] * 8 + [C.c_float, C.c_float, C.c_int, _P, C.c_long, C.c_long, C.c_int, _P],
-    "kpf_bn_train_backward_f32": [_P] * 9 + [C.c_int, _P, C.c_long, C.c_long, C.c_int, _P],
+    "kpf_bn_train_backward": [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_long, C.c_long, C.c_int, _P],
     "kpf_dwconv7_f32": [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_dwconv7_add_f32": [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
-    "kpf_conv2d_wgrad_h16": [_P, _P, C.c_int] + [_P] * 3 + [C.c_long] + [C.c_int] * 15 + [_P],
-    "kpf_conv2d_wgrad_groups": [_P, _P, C.c_int] + [_P] * 3 + [C.c_long] + [C.c_int] * 18 + [_P],
-    "kpf_conv2d_wgrad_deferred": [_P, _P, C.c_int] + [_P] * 3 + [C.c_long] + [C.c_int] * 18 + [C.POINTER(WgradReduceDesc), _P],
-    "kpf_dwconv7_wgrad_deferred": [_P] * 5 + [C.c_long] + [C.c_int] * 4 + [C.POINTER(WgradReduceDesc), _P],
+    "kpf_conv2d_wgrad": [_P, _P, C.c_int] + [_P] * 3 + [C.c_long] + [C.c_int] * 18 + [C.POINTER(WgradReduceDesc), _P],
+    "kpf_dwconv7_wgrad": [_P] * 5 + [C.c_long] + [C.c_int] * 4 + [C.POINTER(WgradReduceDesc), _P],
     "kpf_wgrad_reduce_multi": [C.POINTER(WgradReduceDesc), C.c_int, _P],
     "kpf_row_gather_cols_f32": [_P, C.c_long, C.c_long, C.c_long, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_bn_ssr_forward": [_P] * 7 + [C.c_float, C.c_float, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, _P],
@@ -139,9 +133,6 @@ _SIGS = {
     "kpf_gate_mix_backward": [_P] * 11 + [C.c_int] * 3 + [_P],
     "kpf_pad_rows": [_P, C.c_int, _P, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, _P],
     "kpf_pose_tokens_f32": [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P],
-    "kpf_ln_train_forward_g": [_P, _P, _P, _P, C.c_int, _P, _P, C.c_long, C.c_int, C.c_int, C.c_float, _P],
-    "kpf_ln_train_backward_g": [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(ColsumDesc), _P],
-    "kpf_dwconv7_wgrad_f32": [_P] * 5 + [C.c_long] + [C.c_int] * 4 + [_P],
     "kpf_upsample2x_bwd": [_P, _P] + [C.c_int] * 5 + [_P],
     "kpf_maxpool3x3s2_fwd": [_P, _P, _P] + [C.c_int] * 5 + [_P],
     "kpf_maxpool3x3s2_bwd": [_P, _P, _P] + [C.c_int] * 5 + [_P],
@@ -159,20 +150,17 @@ _SIGS = {
     "kpf_adamw_step_multi_scaled": [C.POINTER(AdamwDesc), C.c_int, _P, C.c_float, _P, C.c_double, C.c_double, C.c_float, C.c_float, _P, _P, _P],
     "kpf_grad_finite_check_multi": [C.POINTER(AdamwDesc), C.c_int, _P, _P],
     "kpf_loss_scale_update": [_P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_int, _P],
-    "kpf_ln_train_forward": [_P, _P, _P, _P, C.c_int, _P, _P, C.c_long, C.c_int, C.c_float, _P],
-    "kpf_ln_train_backward": [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, _P],
+    "kpf_ln_train_forward": [_P, _P, _P, _P, C.c_int, _P, _P, C.c_long, C.c_int, C.c_int, C.c_float, _P],
+    "kpf_ln_train_backward": [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(ColsumDesc), _P],
     "kpf_gelu_forward": [_P, _P, C.c_int, C.c_long, _P],
     "kpf_dense_loss_forward": [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P],
     "kpf_dense_loss_backward": [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P],
     "kpf_loss_tail_forward": [_P] * 11 + [C.c_int] * 3 + [_P],
     "kpf_loss_tail_backward": [_P] * 11 + [C.c_int] * 3 + [_P],
     "kpf_layer_scale_forward": [_P, _P, C.c_int, _P, _P, C.c_long, C.c_int, _P],
-    "kpf_layer_scale_backward": [_P, _P, C.c_int, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, _P],
+    "kpf_layer_scale_backward": [_P, _P, C.c_int, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(ColsumDesc), _P],
     "kpf_drop_add_ln_forward": [_P] * 9 + [C.c_long, C.c_int, C.c_float, C.c_float, _P, C.c_int, _P],
     "kpf_drop_add_ln_backward": [_P] * 11 + [C.c_long, C.c_long, C.c_int, C.c_float, C.c_void_p, _P],
-    "kpf_layer_scale_backward_g": [_P, _P, C.c_int, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p, _P],
-    "kpf_layer_scale_backward_partial": [_P, _P, C.c_int, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, C.POINTER(ColsumDesc), _P],
-    "kpf_ln_train_backward_partial": [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, C.c_long, C.c_int, C.POINTER(ColsumDesc), _P],
     "kpf_colsum_reduce_grouped": [C.POINTER(ColsumDesc), C.c_int, _P],
     "kpf_tr_stack_set_stamps": [_P],
     "kpf_xattn_train_forward": [_P, _P, _P, _P, C.c_long, C.c_int, C.c_float, _P, C.c_int, C.c_int, _P],
@@ -182,10 +170,8 @@ _SIGS = {
     "kpf_bmm_small_k_dx": [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_bmm_small_k_fwd": [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_bmm_small_k_da": [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
-    "kpf_attn21_forward": [_P] * 6 + [C.c_int] * 5 + [C.c_float, C.c_float, _P, C.c_int, _P],
-    "kpf_attn21_backward": [_P] * 9 + [C.c_int] * 5 + [C.c_float, C.c_float, _P],
-    "kpf_attn21_forward_ld": [_P] * 6 + [C.c_int] * 6 + [C.c_float, C.c_float, _P, C.c_int, _P],
-    "kpf_attn21_backward_ld": [_P] * 9 + [C.c_int] * 6 + [C.c_float, C.c_float, _P],
+    "kpf_attn21_forward": [_P] * 6 + [C.c_int] * 6 + [C.c_float, C.c_float, _P, C.c_int, _P],
+    "kpf_attn21_backward": [_P] * 9 + [C.c_int] * 6 + [C.c_float, C.c_float, _P],
     "kpf_gelu_backward": [_P, _P, _P, C.c_int, C.c_long, _P],
     "kpf_row_gather_invert": [_P, _P, C.c_long] + [C.c_int] * 4 + [_P],
     "kpf_row_gather_accum_f32": [_P] * 5 + [C.c_int] * 5 + [_P],

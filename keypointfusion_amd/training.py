@@ -13,7 +13,7 @@ What exists here
                         stepping all parameters in ~14 launches (kpf_adamw_step_multi), learning rate and step count on the device.
   * `Conv2dNHWC`        torch.autograd.Function: forward and data-gradient on kpf_conv2d_f32 / _h16 (dgrad = the forward kernel on
                         flipped / transposed weights, of the stride-dilated dY for strided convolutions; patchify convolutions: a
-                        GEMM + pixel un-shuffle), weight and bias gradient on kpf_conv2d_wgrad_f32 / _h16 (fp32 MFMA, or the 16-bit MFMA
+                        GEMM + pixel un-shuffle), weight and bias gradient on kpf_conv2d_wgrad (fp32 MFMA, or the 16-bit MFMA
                         fed by transposed LDS reads for 16-bit dY / X; pixel index as the reduction dimension, fixed-order split
                         reduction, fp32 accumulation either way).
   * `DwConv7NHWC`, `BatchNormReLU`, `Upsample2xNHWC`, `MaxPool3x3s2NHWC`, `RowGather`: depthwise 7x7, train-mode BatchNorm(+ReLU),
@@ -28,6 +28,7 @@ north_star puts it).  Mixed precision ("bf16"): 16-bit GEMM operands, fp32 maste
 Still on torch autograd: the residual / gate arithmetic of the fusion head, hidden dropout, zero-padding of odd channel
 counts, gradient accumulation at fan-outs.
 """
+import collections
 import ctypes as C
 
 import os
@@ -202,24 +203,13 @@ class _LayerScaleResidual(torch.autograd.Function):
         nws = lib.kpf_layer_scale_ws_floats(rows * ctx.groups, Cc)  # (grouped: the kernel walks rows * G rows of C / G)
         ws = torch.empty(nws, device=y.device, dtype=torch.float32)
         st = torch.cuda.current_stream().cuda_stream
-        if ctx.groups > 1:
-            G = ctx.groups
-            grp = DeferredParamGrads.wants_colsum(gm)
-            desc = L.ColsumDesc() if grp is not None else None
-            L.check(lib.kpf_layer_scale_backward_g(g.data_ptr(), y.data_ptr(), _KDT[y.dtype], gm.data_ptr(), dy.data_ptr(), dgamma.data_ptr(), ws.data_ptr(), nws,
-                                                   rows * G, Cc // G, G, C.byref(desc) if desc is not None else None, st), "kpf_layer_scale_backward_g")
-            if grp is not None:
-                grp.add_colsum(gm, desc, ws, dgamma)
-            return g, dgamma, dy, None
-        grp = DeferredParamGrads.wants_colsum(gm)
-        if grp is not None:  # d gamma: reduced with every other layer's after backward
-            desc = L.ColsumDesc()
-            L.check(lib.kpf_layer_scale_backward_partial(g.data_ptr(), y.data_ptr(), _KDT[y.dtype], gm.data_ptr(), dy.data_ptr(), dgamma.data_ptr(), ws.data_ptr(), nws,
-                                                         rows, Cc, C.byref(desc), st), "kpf_layer_scale_backward_partial")
+        G = ctx.groups
+        grp = DeferredParamGrads.wants_colsum(gm)  # d gamma: reduced with every other layer's after backward
+        desc = L.ColsumDesc() if grp is not None else None
+        L.check(lib.kpf_layer_scale_backward(g.data_ptr(), y.data_ptr(), _KDT[y.dtype], gm.data_ptr(), dy.data_ptr(), dgamma.data_ptr(), ws.data_ptr(), nws,
+                                             rows * G, Cc // G, G, C.byref(desc) if grp is not None else None, st), "kpf_layer_scale_backward")
+        if grp is not None:
             grp.add_colsum(gm, desc, ws, dgamma)
-        else:
-            L.check(lib.kpf_layer_scale_backward(g.data_ptr(), y.data_ptr(), _KDT[y.dtype], gm.data_ptr(), dy.data_ptr(), dgamma.data_ptr(), ws.data_ptr(), nws, rows, Cc,
-                                                 st), "kpf_layer_scale_backward")
         return g, dgamma, dy, None
 
 
@@ -891,15 +881,18 @@ def _grouped_pack(cache, key, weight, bias, G, mode, prec, **kw):
 
 
 class DeferredParamGrads:
-    """Weight gradients of the small Linear layers of one backward pass in ONE launch per 80 layers after it (kpf_linear_wgrad_grouped)
-    instead of a GEMM launch + a reduce launch behind each of ~80 layers of 21 B rows.  While active, Conv2dNHWC.backward of an fp32 1x1 /
-    Linear over at most MAX_ROWS rows whose weight IS a parameter (or a stride-preserving view of one: PackCache key without ':')
-    keeps (dY, X) alive, returns dW / db tensors that are still UNWRITTEN and registers them; autograd only moves those tensors
-    (AccumulateGrad adopts a parameter's first gradient without reading it), `flush()` fills them.  Anything that would read such a
-    gradient earlier must not take this path: a second use of the same weight in one forward is refused here, slices / pads /
-    concatenations of weights never pass a plain key, gradient hooks are not used by GraphedTrainStep (the only caller).  flush()
-    checks on every eager pass that each dW became the parameter's .grad itself (a parameter outside the optimiser whose stale .grad
-    made autograd add instead of adopt is how the `live_parameters` name bug of round 3 surfaced)."""
+    """Parameter gradients of one backward pass whose last launch is shared with other layers' instead of issued per layer.  Three kinds, one rule:
+      * the weight / bias gradients of the small Linear layers: ONE launch per 80 layers after backward (kpf_linear_wgrad_grouped) instead of a GEMM
+        launch + a reduce launch behind each of ~80 layers of 21 B rows.  Conv2dNHWC.backward of an fp32 1x1 / Linear over at most MAX_ROWS rows whose
+        weight IS a parameter (or a stride-preserving view of one: PackCache key without ':') keeps (dY, X) alive (wants / add / add_rows);
+      * the d gamma / d beta column sums behind LayerNorm / layer scale: one launch per 96 layers after backward (wants_colsum / add_colsum);
+      * the fixed-order reduces behind the split weight-gradient GEMMs: one launch per REDUCE_BATCH calls during backward (wants_reduce / add_reduce).
+    The rule: the backward node returns dW / db tensors that are still UNWRITTEN; autograd only moves them (AccumulateGrad adopts a parameter's first
+    gradient without reading it); the shared launch fills them through their recorded addresses.  Anything that would read such a gradient earlier
+    must not take this path: a second gradient for the same parameter in one pass is refused (_claim), slices / pads / concatenations of weights never
+    pass a plain key, gradient hooks are not used by GraphedTrainStep (the only caller).  Every tensor handed over is a promise in one ledger, and
+    flush() verifies on every eager pass that each became the parameter's .grad itself before anything is written (a parameter outside the optimiser
+    whose stale .grad made autograd add instead of adopt is how the `live_parameters` name bug of round 3 surfaced)."""
     active = None
     MAX_ROWS = 1024
 
@@ -912,49 +905,91 @@ class DeferredParamGrads:
             raise TypeError("DeferredParamGrads needs the {name: Parameter} map of the parameters it may defer (None defers nothing safely)")
         self.named = dict(named_params)
         self.by_ptr = {p.data_ptr(): p for p in self.named.values()}
-        self.items, self.colsums, self.biases, self.seen = [], [], [], set()
-        self.reduces, self.reduce_checks, self.stream, self.n_reduces = [], [], None, 0
+        self.stream, self.n_reduces = None, 0
+        self._reset()
+
+    def _reset(self):
+        # launch records: (dY, X, ...) per problem of the grouped Linear launch; (descriptor, workspace) per column sum / per pending reduce
+        self.items, self.colsums, self.reduces = [], [], []
+        self.promises, self.seen = [], set()  # the ledger: every tensor handed to autograd unwritten; the parameters that received a gradient in this pass
 
     def __enter__(self):
         assert DeferredParamGrads.active is None
         DeferredParamGrads.active = self
-        self.stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
+        self.stream = self._current_stream()
         return self
+
+    @staticmethod
+    def _current_stream():
+        return torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
 
     def __exit__(self, et, ev, tb):
         DeferredParamGrads.active = None
         if et is None:
             self.flush()
         else:
-            self.items, self.colsums, self.biases, self.seen = [], [], [], set()
-            self.reduces, self.reduce_checks = [], []
+            self._reset()
         return False
 
+    # ---- the ledger ----
+    # One promise per tensor that was handed to autograd UNWRITTEN: by flush() it must have become the .grad of the parameter(s) at `pptr` itself (address
+    # `optr`, n fp32 elements), because the pending launch writes through that address.  late: written only by flush(), after backward (last_deferred).
+    Promise = collections.namedtuple("Promise", "what pptr optr n late")
+
+    def _walk(self, ptr, n):
+        """[(parameter, byte offset)] of the whole fp32 parameters that make up n elements of storage from `ptr` on: one parameter, or the adjacent
+        parameters of a paired / grouped tensor (training.pair_params: the parts of the gradient are adopted as views of the one deferred tensor);
+        None when that range is not made of whole parameters this object knows."""
+        out, got = [], 0
+        while got < n:
+            q = self.by_ptr.get(ptr + 4 * got)
+            if q is None or q.dtype != torch.float32 or got + q.numel() > n:
+                return None
+            out.append((q, 4 * got))
+            got += q.numel()
+        return out
+
+    def _free(self, ptr, n):
+        """_walk, and none of the parameters holds a gradient yet (one that does would make AccumulateGrad ADD the still-unwritten tensor: not deferred)"""
+        ps = self._walk(ptr, n)
+        return ps is not None and all(q.grad is None for q, _ in ps)
+
+    def _claim(self, kind, ptr_or_key):
+        """At most one gradient per parameter and pass: a second one would be written (or summed by autograd) while the first is still unwritten."""
+        ptr = self.named[ptr_or_key].data_ptr() if isinstance(ptr_or_key, str) else ptr_or_key
+        if ptr in self.seen:
+            raise RuntimeError("DeferredParamGrads: %s %r receives a second gradient in one backward pass" % (kind, ptr_or_key))
+        self.seen.add(ptr)
+
+    def _promise(self, what, pptr, out_ptr, n, late=True):
+        self.promises.append(self.Promise(what, pptr, out_ptr, n, late))  # (of the output only the address: a second reference would make AccumulateGrad copy it)
+
+    def _verify(self, promises):
+        """Adoption is verified BEFORE anything is written: the recorded addresses are only valid while the tensors handed to autograd
+        live on as the parameters' .grad.  If one was copied instead (hook, second reference) its storage may already belong to
+        someone else: raise without launching."""
+        for pr in promises:
+            for p, off in self._walk(pr.pptr, pr.n) or [(None, 0)]:
+                if p is None or p.grad is None or p.grad.data_ptr() != pr.optr + off:
+                    raise RuntimeError("DeferredParamGrads: the gradient of %s was copied before it was written (autograd did not adopt the tensor: is the parameter "
+                                       "hooked, referenced twice, or used twice in one forward?); nothing was written" % pr.what)
+
+    # ---- the d gamma / d beta column sums behind a LayerNorm / layer-scale backward: one launch per KPF_COLSUM_BATCH layers (kpf_colsum_reduce_grouped) ----
     @staticmethod
     def wants_colsum(weight, bias_ptr=None):
-        """The d gamma / d beta column sums behind a LayerNorm / layer-scale backward (kpf_colsum_reduce_grouped): deferred when `weight`
-        (and the bias at `bias_ptr`, for a LayerNorm: its gradient is the second row of the same deferred tensor) is a whole parameter of
-        the model (same storage address and size) that holds no gradient yet."""
+        """Deferred when `weight` (and the bias at `bias_ptr`, for a LayerNorm: its gradient is the second row of the same deferred tensor) is made of
+        whole parameters of the model (same storage address and size) that hold no gradient yet."""
         g = DeferredParamGrads.active
-        if g is None:
-            return None
-
-        if g._whole(weight.data_ptr(), weight.numel()) is None or (bias_ptr is not None and g._whole(bias_ptr, weight.numel()) is None):
+        if g is None or not g._free(weight.data_ptr(), weight.numel()) or (bias_ptr is not None and not g._free(bias_ptr, weight.numel())):
             return None
         return g
 
-    def _whole(self, ptr, n):
-        """the parameter(s) that make up n fp32 elements from `ptr` on: one parameter, or the adjacent parameters of a paired tensor
-        (training.pair_params: the halves of the gradient are adopted as views of the one deferred tensor) — all without a gradient yet"""
-        got, ps = 0, []
-        while got < n:
-            q = self.by_ptr.get(ptr + 4 * got)
-            # (a parameter that already holds a gradient would make AccumulateGrad ADD the still-unwritten tensor: not deferred)
-            if q is None or q.grad is not None or q.dtype != torch.float32 or got + q.numel() > n:
-                return None
-            ps.append(q)
-            got += q.numel()
-        return ps
+    def add_colsum(self, weight, desc, ws, out, bias_ptr=None, bias_out_ptr=None):
+        self._claim("normalisation parameter", weight.data_ptr())
+        self.colsums.append((desc, ws))  # (ws stays referenced)
+        self._promise("a %s normalisation parameter" % (tuple(weight.shape),), weight.data_ptr(), out.data_ptr(), weight.numel())
+        if bias_ptr is not None:
+            self._promise("the bias of a %s LayerNorm" % (tuple(weight.shape),), bias_ptr, bias_out_ptr, weight.numel())
 
     # ---- the fixed-order reduces behind the split weight-gradient GEMMs of the backbones: one launch per REDUCE_BATCH calls (kpf_wgrad_reduce_multi) ----
     REDUCE_DEFER = os.environ.get("KPF_REDUCE_DEFER", "1") != "0"  # (tuning aid: 0 = every weight-gradient call launches its own reduce)
@@ -963,26 +998,25 @@ class DeferredParamGrads:
     @staticmethod
     def wants_reduce(weight, n_bias=0, bias_ptr=None):
         """The active object when the reduce behind `weight`'s gradient may wait for a batched launch: the weight (and the bias at bias_ptr, n_bias
-        elements) is made of whole parameters that hold no gradient yet and receive none twice in this pass — AccumulateGrad then only adopts
-        the still-unwritten tensor — and the call runs on the stream the pass was opened on (the batched launch is issued there)."""
+        elements) is made of whole parameters that hold no gradient yet — AccumulateGrad then only adopts the still-unwritten tensor — and the call
+        runs on the stream the pass was opened on (the batched launch is issued there).  Claims the weight: a second call for it in one pass raises."""
         g = DeferredParamGrads.active
-        if g is None or not g.REDUCE_DEFER or torch.cuda.current_stream().cuda_stream != g.stream:
+        if g is None or not g.REDUCE_DEFER or g._current_stream() != g.stream:
             return None
-        key = ("reduce", weight.data_ptr())
-        if key in g.seen or g._whole(weight.data_ptr(), weight.numel()) is None or (bias_ptr is not None and g._whole(bias_ptr, n_bias) is None):
+        if not g._free(weight.data_ptr(), weight.numel()) or (bias_ptr is not None and not g._free(bias_ptr, n_bias)):
             return None
-        g.seen.add(key)
+        g._claim("convolution weight", weight.data_ptr())
         return g
 
     def add_reduce(self, desc, ws, weight, dw, bias_ptr=None, db=None):
-        """desc: the kpf_wgrad_reduce_desc a *_deferred call filled; ws stays referenced until the batched launch has been issued."""
+        """desc: the kpf_wgrad_reduce_desc a weight-gradient call filled; ws stays referenced until the batched launch has been issued."""
         if desc.kind < 0:  # (the call wrote the gradient itself)
             return
         self.reduces.append((desc, ws))
         self.n_reduces += 1
-        self.reduce_checks.append(("a convolution weight", weight.data_ptr(), dw.data_ptr(), dw.numel()))
+        self._promise("a %s convolution weight" % (tuple(weight.shape),), weight.data_ptr(), dw.data_ptr(), dw.numel(), late=False)
         if db is not None:
-            self.reduce_checks.append(("a convolution bias", bias_ptr, db.data_ptr(), db.numel()))
+            self._promise("the bias of a %s convolution" % (tuple(weight.shape),), bias_ptr, db.data_ptr(), db.numel(), late=False)
         if len(self.reduces) >= self.REDUCE_BATCH:
             self.flush_reduces()
 
@@ -997,33 +1031,21 @@ class DeferredParamGrads:
         self.reduces = []
         L.check(L.load().kpf_wgrad_reduce_multi(arr, len(arr), self.stream), "kpf_wgrad_reduce_multi")
 
-    def _parts(self, ptr, n):
-        """[(parameter, byte offset)] covering n fp32 elements of parameter storage from ptr on (see wants_colsum)."""
-        out, got = [], 0
-        while got < n:
-            q = self.by_ptr[ptr + 4 * got]
-            out.append((q, 4 * got))
-            got += q.numel()
-        return out
-
-    def add_colsum(self, weight, desc, ws, out, bias_ptr=None, bias_out_ptr=None):
-        key = ("colsum", weight.data_ptr())
-        if key in self.seen:
-            raise RuntimeError("DeferredParamGrads: a normalisation parameter receives a second gradient in one backward pass")
-        self.seen.add(key)
-        self.colsums.append((desc, ws, weight.data_ptr(), out.data_ptr(), weight.numel()))  # (ws stays referenced; of the output only the address)
-        if bias_ptr is not None:
-            for q, off in self._parts(bias_ptr, weight.numel()):  # (adoption of the bias row is verified like a Linear's bias; a paired bias: per half)
-                self.biases.append(("a LayerNorm", q.data_ptr(), bias_out_ptr + off))
-
+    # ---- the weight / bias gradients of the small Linear layers: one launch per KPF_WGRAD_GROUP_BATCH layers after backward (kpf_linear_wgrad_grouped) ----
     @staticmethod
-    def wants(key, cache, dy, x, kh, kw, stride, pad):
+    def wants(key, cache, dy, x, kh, kw, stride, pad, bias_ptr=None, n_bias=0):
+        """bias_ptr (+ n_bias): the layer's bias gradient is handed over unwritten too — the bias must be a parameter this object knows, of n_bias
+        elements, without a gradient yet."""
         g = DeferredParamGrads.active
         if g is None or cache is None or not isinstance(key, str) or ":" in key:
             return None
         p = g.named.get(key)
         if p is None or p.grad is not None:  # unknown to the map, or AccumulateGrad would add instead of adopt: the per-layer kernels
             return None
+        if bias_ptr is not None:
+            bp = g.by_ptr.get(bias_ptr)
+            if bp is None or bp.numel() != n_bias or bp.grad is not None:
+                return None
         rows = x.numel() // x.shape[-1]
         ok = (kh == 1 and kw == 1 and stride == 1 and pad == 0 and rows <= g.MAX_ROWS and dy.dtype == torch.float32 and x.dtype == torch.float32
               and x.shape[-1] % 4 == 0 and dy.shape[-1] % 4 == 0)
@@ -1031,63 +1053,34 @@ class DeferredParamGrads:
 
     def add(self, key, dy, x, dw, db, bias_ptr=None, ldy=0):
         """ldy: floats between the rows of dy when it is a column slice of a wider matrix (0: dense)."""
-        if key in self.seen:
-            raise RuntimeError("DeferredParamGrads: parameter %r receives a second gradient in one backward pass" % (key,))
-        self.seen.add(key)
-        # (dY, X) stay referenced until flush; of dW / db only the addresses are kept — a second reference would make AccumulateGrad
-        # copy the unwritten tensor instead of adopting it
-        self.items.append((key, dy, x, dw.data_ptr(), None if db is None else db.data_ptr(), x.numel() // x.shape[-1], dy.shape[-1], x.shape[-1], int(ldy), dw.data_ptr()))
-        if db is not None:
-            self.biases.append((key, bias_ptr, db.data_ptr()))
+        self.add_rows(key, [(0, dy, x)], dw, db, bias_ptr, ldy)
 
     def add_rows(self, key, parts, dw, db, bias_ptr=None, ldy=0):
         """ONE parameter whose gradient is several row blocks with different X operands (the packed in_proj of nn.MultiheadAttention: rows 0-127 multiply
         query + qpos, rows 128-383 key + kpos): parts = [(first row, dY block, X)], each its own problem of the grouped launch, written into its rows of dw / db."""
-        if key in self.seen:
-            raise RuntimeError("DeferredParamGrads: parameter %r receives a second gradient in one backward pass" % (key,))
-        self.seen.add(key)
-        K = dw.shape[-1] if dw.dim() == 2 else dw[0].numel()
-        for r0, dy, x in parts:
-            self.items.append((key, dy, x, dw.data_ptr() + 4 * r0 * K, None if db is None else db.data_ptr() + 4 * r0, x.numel() // x.shape[-1], dy.shape[-1], x.shape[-1], int(ldy),
-                               dw.data_ptr()))
+        self._claim("parameter", key)
+        K = dw.numel() // dw.shape[0]
+        for r0, dy, x in parts:  # (dY, X) stay referenced until flush
+            self.items.append((dy, x, dw.data_ptr() + 4 * r0 * K, None if db is None else db.data_ptr() + 4 * r0, x.numel() // x.shape[-1], dy.shape[-1], x.shape[-1], int(ldy)))
+        self._promise(repr(key), self.named[key].data_ptr(), dw.data_ptr(), dw.numel())
         if db is not None:
-            self.biases.append((key, bias_ptr, db.data_ptr()))
+            self._promise("the bias beside %r" % (key,), bias_ptr, db.data_ptr(), db.numel())
 
     def flush(self):
         from . import lib as L
+        items, colsums, reduces, promises = self.items, self.colsums, self.reduces, self.promises
+        self._reset()
+        # the parameters whose gradients this pass fills only now (GraphedTrainStep keeps them out of the buckets that are reduced DURING backward)
+        self.last_deferred = list({id(q): q for pr in promises if pr.late for q, _ in self._walk(pr.pptr, pr.n) or []}.values())
+        self._verify(promises)  # (before each of the launches below: backward is over, every tensor has been adopted or never will be)
+        self.reduces = reduces
         self.flush_reduces()
-        checks, self.reduce_checks = self.reduce_checks, []
-        for what, pptr, optr, n in checks:  # (the reduces have been issued by now; a gradient that autograd copied before that holds garbage: say so)
-            for q, off in self._parts(pptr, n):
-                if q.grad is None or q.grad.data_ptr() != optr + off:
-                    raise RuntimeError("DeferredParamGrads: the gradient of %s %s was copied before its reduce had run (autograd did not adopt the tensor)" % (what, tuple(q.shape)))
-        items, colsums, biases, self.items, self.colsums, self.biases, self.seen = self.items, self.colsums, self.biases, [], [], [], set()
-        # the parameters whose gradients this pass deferred (GraphedTrainStep keeps them out of the buckets that are reduced DURING backward)
-        self.last_deferred = (list({id(self.named[k]): self.named[k] for k, *_ in items if k in self.named}.values()) + [q for c in colsums if c[2] in self.by_ptr for q, _ in self._parts(c[2], c[4])] +
-                              [self.by_ptr[b[1]] for b in biases if b[1] in self.by_ptr])
         if not items and not colsums:
             return
-        # Adoption is verified BEFORE anything is written: the recorded addresses are only valid while the tensors handed to autograd
-        # live on as the parameters' .grad.  If one was copied instead (hook, second reference) its storage may already belong to
-        # someone else: raise without launching.
-        msg = ("DeferredParamGrads: the gradient of %s was copied before it was written (autograd did not adopt the tensor: is the parameter "
-               "hooked, referenced twice, or used twice in one forward?); nothing was written")
-        for key, _, _, _, _, _, _, _, _, pbase in items:
-            p = self.named.get(key)
-            if p is None or p.grad is None or p.grad.data_ptr() != pbase:
-                raise RuntimeError(msg % repr(key))
-        for _, _, wptr, optr, n in colsums:
-            for p, off in (self._parts(wptr, n) if wptr in self.by_ptr else [(None, 0)]):
-                if p is None or p.grad is None or p.grad.data_ptr() != optr + off:
-                    raise RuntimeError(msg % ("a normalisation parameter" if p is None else "a %s normalisation parameter" % (tuple(p.shape),)))
-        for key, bptr, optr in biases:
-            p = self.by_ptr.get(bptr)
-            if p is None or p.grad is None or p.grad.data_ptr() != optr:
-                raise RuntimeError(msg % ("the bias beside %r" % (key,)))
         st = torch.cuda.current_stream().cuda_stream
         if items:
             arr = (L.WgradGroupDesc * len(items))()
-            for d, (key, dy, x, pw, pb, M, N, K, ldy, _) in zip(arr, items):
+            for d, (dy, x, pw, pb, M, N, K, ldy) in zip(arr, items):
                 d.dy, d.x, d.dw, d.db, d.M, d.N, d.K, d.ldy = dy.data_ptr(), x.data_ptr(), pw, pb, M, N, K, ldy
             L.check(L.load().kpf_linear_wgrad_grouped(arr, len(items), st), "kpf_linear_wgrad_grouped")
         if colsums:
@@ -1095,77 +1088,57 @@ class DeferredParamGrads:
             L.check(L.load().kpf_colsum_reduce_grouped(arr, len(colsums), st), "kpf_colsum_reduce_grouped")
 
 
-GroupedLinearWgrad = DeferredParamGrads  # (the name the first form of this class had)
-
-
-def _wgrad_groups(lib, dy_ptr, x_ptr, dt, dw, db, ws, nws, groups, dims, st, weight=None, bias_ptr=None):
-    """kpf_conv2d_wgrad_groups(dy, x, dt, dw, db, ws, nws, groups, *dims, stream) — or, inside a DeferredParamGrads pass and for a gradient that goes to whole
-    parameters (`weight`, and the bias at `bias_ptr`), kpf_conv2d_wgrad_deferred with the reduce joining a batched launch: dw / db are then still UNWRITTEN."""
-    from . import lib as L
-    dbp = db.data_ptr() if db is not None else None
-    grp = DeferredParamGrads.wants_reduce(weight, 0 if db is None else db.numel(), bias_ptr if db is not None else None) if weight is not None else None
-    if grp is not None and (db is None or bias_ptr is not None):
-        desc = L.WgradReduceDesc()
-        L.check(lib.kpf_conv2d_wgrad_deferred(dy_ptr, x_ptr, dt, dw.data_ptr(), dbp, ws.data_ptr(), nws, groups, *dims, C.byref(desc), st), "kpf_conv2d_wgrad_deferred")
-        grp.add_reduce(desc, ws, weight, dw, bias_ptr if db is not None else None, db)
-    else:
-        L.check(lib.kpf_conv2d_wgrad_groups(dy_ptr, x_ptr, dt, dw.data_ptr(), dbp, ws.data_ptr(), nws, groups, *dims, st), "kpf_conv2d_wgrad_groups")
-
-
-def conv_wgrad_hip(dy, x, wshape, stride, pad, want_db=True, groups=1, weight=None, bias_ptr=None):
-    """(dW in OIHW, db or None) of a convolution from NHWC dY [B,OH,OW,N] and X [B,H,W,Cin]: kpf_conv2d_wgrad_f32 / _h16 (f32 MFMA GEMM
-    with the pixel index as the reduction dimension, split over workgroups, fixed-order reduce).  weight (+ bias_ptr): the parameter
-    tensor the gradient is for — inside a DeferredParamGrads pass its reduce may then join a batched launch (wants_reduce): dW / db are
-    returned UNWRITTEN."""
+def conv_wgrad_hip(dy, x, wshape, stride, pad, want_db=True, groups=1, weight=None, bias_ptr=None, ld=None, valid=None):
+    """(dW in OIHW, db or None) of a convolution from NHWC dY [B,OH,OW,N] and X [B,H,W,Cin]: kpf_conv2d_wgrad (MFMA GEMM with the pixel
+    index as the reduction dimension, split over workgroups, fixed-order reduce) — the one place that allocates its workspace and outputs,
+    decides whether the reduce is deferred, and calls it.  weight (+ bias_ptr): the parameter tensor the gradient is for — inside a
+    DeferredParamGrads pass its reduce may then join a batched launch (wants_reduce): dW / db are returned UNWRITTEN.
+    ld = (ldx, ldy): the operands are views into wider rows (a column slice, zero-padded channels) and are read where they are, at these
+    pixel strides — no copy, no type change.  valid = (cin_valid, n_valid): the operands carry zero channels up to whole channel groups
+    (the odd-width Linears); dW (wshape) and db are written without them."""
     from . import lib as L
     lib = L.load()
     B, H, W, Cin = x.shape
     _, OH, OW, N = dy.shape
-    KH, KW = int(wshape[2]), int(wshape[3])
-    ldx, ldy = Cin, N
-    Cin, N = Cin // groups, N // groups  # (groups > 1: channel-stacked operands, wshape = [G*N, Cin, KH, KW]: kpf_conv2d_wgrad_groups)
-    # both operands in the same 16-bit storage type (mixed-precision step) and whole 8-element granules: kpf_conv2d_wgrad_h16 reads them
-    # as they are (fp32 products and sums); anything else is widened to fp32 first
-    h16 = dy.dtype == x.dtype and dy.dtype in (torch.bfloat16, torch.float16) and Cin % 8 == 0 and N % 8 == 0
-    if not h16:
-        dy, x = dy.float(), x.float()
-    if groups == 1 and H == 1 and W == 1 and not x.is_contiguous() and x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) > Cin and x.data_ptr() % 16 == 0 and not h16:
-        ldx = x.stride(0)  # (rows that are a column slice of a wider matrix: read in place)
+    KH, KW = (int(wshape[2]), int(wshape[3])) if len(wshape) == 4 else (1, 1)  # (a Linear's [N, K] weight: 1 x 1)
+    Cin, N = Cin // groups, N // groups  # (groups > 1: channel-stacked operands, wshape = [G*N, Cin, KH, KW])
+    if ld is not None:
+        (ldx, ldy), h16 = ld, dy.dtype != torch.float32
     else:
-        x = x.contiguous()
-    dy = dy.contiguous()
+        ldx, ldy = x.shape[-1], dy.shape[-1]
+        # both operands in the same 16-bit storage type (mixed-precision step) and whole 8-element granules: the kernel reads them
+        # as they are (fp32 products and sums); anything else is widened to fp32 first
+        h16 = dy.dtype == x.dtype and dy.dtype in (torch.bfloat16, torch.float16) and Cin % 8 == 0 and N % 8 == 0
+        if not h16:
+            dy, x = dy.float(), x.float()
+        if groups == 1 and H == 1 and W == 1 and not x.is_contiguous() and x.stride(-1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) > Cin and x.data_ptr() % 16 == 0 and not h16:
+            ldx = x.stride(0)  # (rows that are a column slice of a wider matrix: read in place)
+        else:
+            x = x.contiguous()
+        dy = dy.contiguous()
+    cin_valid, n_valid = valid or (0, 0)
     nws = lib.kpf_conv2d_wgrad_ws_floats(B * OH * OW, N, KH * KW * Cin) * groups
     ws = torch.empty(nws, device=x.device, dtype=torch.float32)
     dw = torch.empty(tuple(wshape), device=x.device, dtype=torch.float32)
-    db = torch.empty(N * groups, device=x.device, dtype=torch.float32) if want_db else None
-    st = torch.cuda.current_stream().cuda_stream
-    dt = (L.KPF_DT_BF16 if dy.dtype == torch.bfloat16 else L.KPF_DT_F16) if h16 else L.KPF_DT_F32
+    db = torch.empty((n_valid or N) * groups, device=x.device, dtype=torch.float32) if want_db else None
+    dt = _KDT[dy.dtype] if h16 else L.KPF_DT_F32
     if not h16 and _HEAD_MMA[0]:  # (inside a head_mma block: the layer's forward multiplied rounded operands, its weight gradient does too)
         dt = L.KPF_DT_F32_MMA_BF16 if _HEAD_MMA[0] == L.KPF_MMA_BF16 else L.KPF_DT_F32_MMA_F16
-    grp = DeferredParamGrads.wants_reduce(weight, N * groups, bias_ptr if want_db else None) if weight is not None and tuple(weight.shape) == tuple(wshape) else None
+    grp = None
+    if weight is not None and tuple(weight.shape) == tuple(wshape) and (not want_db or bias_ptr is not None):
+        grp = DeferredParamGrads.wants_reduce(weight, 0 if db is None else db.numel(), bias_ptr if want_db else None)
+    desc = L.WgradReduceDesc() if grp is not None else None
+    L.check(lib.kpf_conv2d_wgrad(dy.data_ptr(), x.data_ptr(), dt, dw.data_ptr(), db.data_ptr() if want_db else None, ws.data_ptr(), nws, groups,
+                                 B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, stride, stride, pad, pad, cin_valid, n_valid,
+                                 C.byref(desc) if grp is not None else None, torch.cuda.current_stream().cuda_stream), "kpf_conv2d_wgrad")
     if grp is not None:
-        desc = L.WgradReduceDesc()
-        L.check(lib.kpf_conv2d_wgrad_deferred(dy.data_ptr(), x.data_ptr(), dt, dw.data_ptr(), db.data_ptr() if want_db else None, ws.data_ptr(), nws, groups,
-                                              B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, stride, stride, pad, pad, 0, 0, C.byref(desc), st), "kpf_conv2d_wgrad_deferred")
         grp.add_reduce(desc, ws, weight, dw, bias_ptr if want_db else None, db)
-        return dw, db
-    if groups > 1:
-        L.check(lib.kpf_conv2d_wgrad_groups(dy.data_ptr(), x.data_ptr(), dt, dw.data_ptr(), db.data_ptr() if want_db else None, ws.data_ptr(), nws, groups,
-                                            B, H, W, Cin, ldx, OH, OW, N, ldy, KH, KW, stride, stride, pad, pad, 0, 0, st), "kpf_conv2d_wgrad_groups")
-        return dw, db
-    if h16:
-        L.check(lib.kpf_conv2d_wgrad_h16(dy.data_ptr(), x.data_ptr(), L.KPF_DT_BF16 if dy.dtype == torch.bfloat16 else L.KPF_DT_F16, dw.data_ptr(),
-                                         db.data_ptr() if want_db else None, ws.data_ptr(), nws, B, H, W, Cin, Cin, OH, OW, N, N, KH, KW,
-                                         stride, stride, pad, pad, st), "kpf_conv2d_wgrad_h16")
-    else:
-        L.check(lib.kpf_conv2d_wgrad_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr() if want_db else None, ws.data_ptr(), nws,
-                                         B, H, W, Cin, ldx, OH, OW, N, N, KH, KW, stride, stride, pad, pad, st), "kpf_conv2d_wgrad_f32")
     return dw, db
 
 
 class DwConv7NHWC(torch.autograd.Function):
     """Depthwise 7x7 (pad 3) + bias on NHWC fp32 [B,H,W,C] (convNeXT/convnext.py:41), weight in the reference's [C,1,7,7] layout.
-    forward kpf_dwconv7_f32; backward: dX = the same kernel on dY with mirrored taps, dW / db = kpf_dwconv7_wgrad_f32."""
+    forward kpf_dwconv7_f32; backward: dX = the same kernel on dY with mirrored taps, dW / db = kpf_dwconv7_wgrad."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, key=None, cache=None, alias=False):
@@ -1211,14 +1184,11 @@ class DwConv7NHWC(torch.autograd.Function):
             dw = torch.empty(Cc, 1, 7, 7, device=x.device, dtype=torch.float32)
             db = torch.empty(Cc, device=x.device, dtype=torch.float32)
             grp = DeferredParamGrads.wants_reduce(weight, Cc, ctx.bias_ptr)
+            desc = L.WgradReduceDesc() if grp is not None else None
+            L.check(lib.kpf_dwconv7_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nws, B, H, W, Cc,
+                                          C.byref(desc) if grp is not None else None, st), "kpf_dwconv7_wgrad")
             if grp is not None:
-                desc = L.WgradReduceDesc()
-                L.check(lib.kpf_dwconv7_wgrad_deferred(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nws, B, H, W, Cc, C.byref(desc), st),
-                        "kpf_dwconv7_wgrad_deferred")
                 grp.add_reduce(desc, ws, weight, dw, ctx.bias_ptr, db)
-            else:
-                L.check(lib.kpf_dwconv7_wgrad_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nws, B, H, W, Cc, st),
-                        "kpf_dwconv7_wgrad_f32")
         return dx, dw, db, None, None, None
 
 
@@ -1313,7 +1283,7 @@ class BatchNormReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, out_dtype=None, alias=False):
         """alias: also return x itself as a second output.  A Residual block feeds x to this BatchNorm AND to its skip path; routing the
-        skip path through the alias hands its gradient to THIS backward, where kpf_bn_train_backward_add folds it into dx — otherwise
+        skip path through the alias hands its gradient to THIS backward, where kpf_bn_train_backward folds it into dx (addend) — otherwise
         autograd adds the two gradients of x with a separate launch over the whole activation."""
         from . import lib as L
         lib = L.load()
@@ -1350,10 +1320,10 @@ class BatchNormReLU(torch.autograd.Function):
         dwb = torch.empty(2, Cc, device=x.device, dtype=torch.float32)
         nws = lib.kpf_bn_ws_floats(M, Cc)
         ws = torch.empty(nws, device=x.device, dtype=torch.float32)
-        L.check(lib.kpf_bn_train_backward_add(dy.data_ptr(), x.data_ptr(), y.data_ptr() if ctx.relu else None, _KDT[x.dtype], _KDT[ctx.out_dtype],
-                                              stats[0].data_ptr(), stats[1].data_ptr(), weight.detach().contiguous().data_ptr(),
-                                              None if add is None else add.data_ptr(), dx.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr(), int(ctx.relu),
-                                              ws.data_ptr(), nws, M, Cc, torch.cuda.current_stream().cuda_stream), "kpf_bn_train_backward_add")
+        L.check(lib.kpf_bn_train_backward(dy.data_ptr(), x.data_ptr(), y.data_ptr() if ctx.relu else None, _KDT[x.dtype], _KDT[ctx.out_dtype],
+                                          stats[0].data_ptr(), stats[1].data_ptr(), weight.detach().contiguous().data_ptr(),
+                                          None if add is None else add.data_ptr(), dx.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr(), int(ctx.relu),
+                                          ws.data_ptr(), nws, M, Cc, torch.cuda.current_stream().cuda_stream), "kpf_bn_train_backward")
         return dx, dwb[0], dwb[1], None, None, None, None, None, None, None
 
 
@@ -1510,7 +1480,7 @@ class LayerNormRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, out_dtype=None, groups=1):
         """groups = G > 1: x [..., G*C] holds G channel groups, each normalised on its own with its own parameter set (weight, bias [G*C]
-        group-major: the paired backbones' LayerNorms, pair_params) — kpf_ln_train_forward_g on the [rows*G, C] view."""
+        group-major: the paired backbones' LayerNorms, pair_params) — the kernels walk the [rows*G, C] view."""
         from . import lib as L
         x = x.float().contiguous()
         Cc = x.shape[-1] // groups
@@ -1519,8 +1489,8 @@ class LayerNormRows(torch.autograd.Function):
         y = torch.empty(x.shape, device=x.device, dtype=out_dtype)
         stats = torch.empty(2, rows, device=x.device, dtype=torch.float32)
         w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-        L.check(L.load().kpf_ln_train_forward_g(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), _KDT[out_dtype], stats[0].data_ptr(), stats[1].data_ptr(),
-                                                rows, Cc, groups, float(eps), torch.cuda.current_stream().cuda_stream), "kpf_ln_train_forward_g")
+        L.check(L.load().kpf_ln_train_forward(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), _KDT[out_dtype], stats[0].data_ptr(), stats[1].data_ptr(),
+                                              rows, Cc, groups, float(eps), torch.cuda.current_stream().cuda_stream), "kpf_ln_train_forward")
         ctx.save_for_backward(x, stats, w)
         ctx.groups = groups
         ctx.bias_ptr = b.data_ptr()  # (identifies the bias PARAMETER for DeferredParamGrads: its gradient is deferred together with the weight's)
@@ -1542,25 +1512,13 @@ class LayerNormRows(torch.autograd.Function):
         nws = lib.kpf_ln_ws_floats(rows, G * Cc)
         ws = torch.empty(nws, device=x.device, dtype=torch.float32)
         st = torch.cuda.current_stream().cuda_stream
-        if G > 1:
-            grp = DeferredParamGrads.wants_colsum(w, ctx.bias_ptr)  # (paired parameters: both halves are checked and adopted)
-            desc = L.ColsumDesc() if grp is not None else None
-            L.check(lib.kpf_ln_train_backward_g(dy.data_ptr(), _KDT[dy.dtype], x.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), w.data_ptr(), dx.data_ptr(),
-                                                dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(), nws, rows, Cc, G, C.byref(desc) if desc is not None else None, st),
-                    "kpf_ln_train_backward_g")
-            if grp is not None:
-                grp.add_colsum(w, desc, ws, dwb, ctx.bias_ptr, dwb[1].data_ptr())
-            return dx, dwb[0], dwb[1], None, None, None
-        grp = DeferredParamGrads.wants_colsum(w, ctx.bias_ptr)
-        if grp is not None:  # d gamma / d beta: reduced with every other layer's after backward
-            desc = L.ColsumDesc()
-            L.check(lib.kpf_ln_train_backward_partial(dy.data_ptr(), _KDT[dy.dtype], x.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), w.data_ptr(),
-                                                      dx.data_ptr(), dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(), nws, rows, Cc, C.byref(desc), st),
-                    "kpf_ln_train_backward_partial")
+        grp = DeferredParamGrads.wants_colsum(w, ctx.bias_ptr)  # d gamma / d beta: reduced with every other layer's after backward (paired parameters: both halves are checked and adopted)
+        desc = L.ColsumDesc() if grp is not None else None
+        L.check(lib.kpf_ln_train_backward(dy.data_ptr(), _KDT[dy.dtype], x.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), w.data_ptr(), dx.data_ptr(),
+                                          dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(), nws, rows, Cc, G, C.byref(desc) if grp is not None else None, st),
+                "kpf_ln_train_backward")
+        if grp is not None:
             grp.add_colsum(w, desc, ws, dwb, ctx.bias_ptr, dwb[1].data_ptr())
-        else:
-            L.check(lib.kpf_ln_train_backward(dy.data_ptr(), _KDT[dy.dtype], x.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), w.data_ptr(), dx.data_ptr(),
-                                              dwb[0].data_ptr(), dwb[1].data_ptr(), ws.data_ptr(), nws, rows, Cc, st), "kpf_ln_train_backward")
         return dx, dwb[0], dwb[1], None, None, None
 
 
@@ -1601,7 +1559,7 @@ class Attn21(torch.autograd.Function):
         out = torch.empty_like(q)
         P = torch.empty(B, heads, T, T, device=q.device, dtype=torch.float32)
         M = torch.empty(B, heads, T, T, device=q.device, dtype=torch.uint8)
-        L.check(L.load().kpf_attn21_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), P.data_ptr(), M.data_ptr(), B, T, heads, hd, Cc,
+        L.check(L.load().kpf_attn21_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), P.data_ptr(), M.data_ptr(), B, T, heads, hd, Cc, Cc,
                                             float(scale), float(p_drop), rng.data_ptr() if rng is not None else None, int(call_id),
                                             torch.cuda.current_stream().cuda_stream), "kpf_attn21_forward")
         ctx_.save_for_backward(q, k, v, P, M)
@@ -1617,7 +1575,7 @@ class Attn21(torch.autograd.Function):
         dctx = dctx.float().contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         L.check(L.load().kpf_attn21_backward(dctx.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), P.data_ptr(), M.data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                                             dv.data_ptr(), B, T, heads, Cc // heads, Cc, scale, p_drop, torch.cuda.current_stream().cuda_stream),
+                                             dv.data_ptr(), B, T, heads, Cc // heads, Cc, Cc, scale, p_drop, torch.cuda.current_stream().cuda_stream),
                 "kpf_attn21_backward")
         return dq, dk, dv, None, None, None, None, None
 
@@ -1629,9 +1587,9 @@ def attn21(q, k, v, heads, scale, p_drop=0.0, rng=None, call_id=0):
 class SelfAttention21(torch.autograd.Function):
     """The self-attention of a BERT layer of the 21-token stacks (model/model.py:30-70) from its input: q | k | v as ONE projection GEMM
     (N = 3C; the three parameters packed into one operand by PackCache.get_stacked), the attention core reading the three column slices
-    where that GEMM left them (kpf_attn21_forward_ld), and in the backward ONE data-gradient GEMM over [dq | dk | dv].  The three weight /
+    where that GEMM left them (kpf_attn21_forward: ld = 3C), and in the backward ONE data-gradient GEMM over [dq | dk | dv].  The three weight /
     bias gradients join the grouped launch after backward (DeferredParamGrads, dy = a column slice: kpf_wgrad_group_desc::ldy) or take
-    kpf_conv2d_wgrad_f32 with ldy = 3C.  7 launches per layer and direction fewer than three Linears + Attn21, and the input's gradient
+    conv_wgrad_hip with ldy = 3C.  7 launches per layer and direction fewer than three Linears + Attn21, and the input's gradient
     arrives as one tensor instead of three to add."""
 
     @staticmethod
@@ -1646,9 +1604,9 @@ class SelfAttention21(torch.autograd.Function):
         P = torch.empty(B, heads, T, T, device=h.device, dtype=torch.float32)
         Mk = torch.empty(B, heads, T, T, device=h.device, dtype=torch.uint8)
         q = qkv.data_ptr()
-        L.check(L.load().kpf_attn21_forward_ld(q, q + 4 * Cc, q + 8 * Cc, out.data_ptr(), P.data_ptr(), Mk.data_ptr(), B, T, heads, Cc // heads, 3 * Cc, Cc,
-                                               float(scale), float(p_drop), rng.data_ptr() if rng is not None else None, int(call_id),
-                                               torch.cuda.current_stream().cuda_stream), "kpf_attn21_forward_ld")
+        L.check(L.load().kpf_attn21_forward(q, q + 4 * Cc, q + 8 * Cc, out.data_ptr(), P.data_ptr(), Mk.data_ptr(), B, T, heads, Cc // heads, 3 * Cc, Cc,
+                                            float(scale), float(p_drop), rng.data_ptr() if rng is not None else None, int(call_id),
+                                            torch.cuda.current_stream().cuda_stream), "kpf_attn21_forward")
         ctx.save_for_backward(hc, qkv, P, Mk, wq, wk, wv)
         ctx.conf = (sp, names, cache, heads, float(scale), float(p_drop), tuple(b.data_ptr() for b in (bq, bk, bv)))
         ctx.set_materialize_grads(False)
@@ -1670,8 +1628,8 @@ class SelfAttention21(torch.autograd.Function):
         dctx = dctx.float().contiguous()
         dqkv = torch.empty(M, 3 * Cc, device=hc.device, dtype=torch.float32)
         q, dq = qkv.data_ptr(), dqkv.data_ptr()
-        L.check(lib.kpf_attn21_backward_ld(dctx.data_ptr(), q, q + 4 * Cc, q + 8 * Cc, P.data_ptr(), Mk.data_ptr(), dq, dq + 4 * Cc, dq + 8 * Cc, B, T, heads, Cc // heads,
-                                           3 * Cc, Cc, scale, p_drop, st), "kpf_attn21_backward_ld")
+        L.check(lib.kpf_attn21_backward(dctx.data_ptr(), q, q + 4 * Cc, q + 8 * Cc, P.data_ptr(), Mk.data_ptr(), dq, dq + 4 * Cc, dq + 8 * Cc, B, T, heads, Cc // heads,
+                                        3 * Cc, Cc, scale, p_drop, st), "kpf_attn21_backward")
         dh = None
         if ctx.needs_input_grad[0]:
             ga = None if g_alias is None else g_alias.float().contiguous().view(M, 1, 1, Cc)
@@ -1679,20 +1637,13 @@ class SelfAttention21(torch.autograd.Function):
         grads = []
         for i, (w, name) in enumerate(zip((wq, wk, wv), names)):
             dyi = dqkv[:, i * Cc:(i + 1) * Cc]
-            grp = DeferredParamGrads.wants(name, cache, dyi, hc, 1, 1, 1, 0)
+            grp = DeferredParamGrads.wants(name, cache, dyi, hc, 1, 1, 1, 0, bias_ptrs[i], Cc)
             if grp is not None:
-                bp = grp.by_ptr.get(bias_ptrs[i])
-                if bp is None or bp.numel() != Cc or bp.grad is not None:
-                    grp = None
-            dw = torch.empty(tuple(w.shape), device=hc.device, dtype=torch.float32)
-            db = torch.empty(Cc, device=hc.device, dtype=torch.float32)
-            if grp is not None:
+                dw = torch.empty(tuple(w.shape), device=hc.device, dtype=torch.float32)
+                db = torch.empty(Cc, device=hc.device, dtype=torch.float32)
                 grp.add(name, dyi, hc, dw, db, bias_ptrs[i], ldy=3 * Cc)
             else:
-                nws = lib.kpf_conv2d_wgrad_ws_floats(M, Cc, Cc)
-                ws = torch.empty(nws, device=hc.device, dtype=torch.float32)
-                L.check(lib.kpf_conv2d_wgrad_f32(dyi.data_ptr(), hc.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nws, M, 1, 1, Cc, Cc, 1, 1, Cc, 3 * Cc,
-                                                 1, 1, 1, 1, 0, 0, st), "kpf_conv2d_wgrad_f32")
+                dw, db = conv_wgrad_hip(dyi[:, None, None], hc.view(M, 1, 1, Cc), w.shape, 1, 0, ld=(Cc, 3 * Cc))
             grads += [dw, db]
         return (dh,) + tuple(grads) + (None,) * 7
 
@@ -1798,11 +1749,7 @@ class BertStack21(torch.autograd.Function):
                 dy = dyfull[:, coff:coff + N] if ldy else dyfull
                 dw = torch.empty(tuple(w.shape), device=dev, dtype=torch.float32)
                 db = torch.empty(N, device=dev, dtype=torch.float32)
-                grp = DeferredParamGrads.wants(name, cache, dy, x, 1, 1, 1, 0)
-                if grp is not None:
-                    bp = grp.by_ptr.get(bias.data_ptr())
-                    if bp is None or bp.numel() != N or bp.grad is not None:
-                        grp = None
+                grp = DeferredParamGrads.wants(name, cache, dy, x, 1, 1, 1, 0, bias.data_ptr(), N)
                 if grp is not None:
                     grp.add(name, dy, x, dw, db, bias.data_ptr(), ldy=ldy)
                 else:
@@ -1893,11 +1840,7 @@ class XAttnLayer21(torch.autograd.Function):
         now_w, now_c = [], []
         # in_proj: one parameter, two problems (different X): two row blocks of one deferred gradient (add_rows), or two problems of the launch below
         dwin, dbin = new(384, 128), new(384)
-        grp = DeferredParamGrads.wants(names[0], cache, dqkv[:, :128], X(0, 128), 1, 1, 1, 0)
-        if grp is not None:
-            bp = grp.by_ptr.get(params[1].data_ptr())
-            if bp is None or bp.numel() != 384 or bp.grad is not None:
-                grp = None
+        grp = DeferredParamGrads.wants(names[0], cache, dqkv[:, :128], X(0, 128), 1, 1, 1, 0, params[1].data_ptr(), 384)
         if grp is not None:
             grp.add_rows(names[0], [(0, dqkv[:, :128], X(0, 128)), (128, dqkv[:, 128:], X(1, 128))], dwin, dbin, params[1].data_ptr(), ldy=384)
         else:
@@ -1908,11 +1851,7 @@ class XAttnLayer21(torch.autograd.Function):
             w, bias, name = params[wi], params[wi + 1], names[wi]
             x, dy = X(xw, 128), DY(yw)
             dw, db = new(128, 128), new(128)
-            grp = DeferredParamGrads.wants(name, cache, dy, x, 1, 1, 1, 0)
-            if grp is not None:
-                bp = grp.by_ptr.get(bias.data_ptr())
-                if bp is None or bp.numel() != 128 or bp.grad is not None:
-                    grp = None
+            grp = DeferredParamGrads.wants(name, cache, dy, x, 1, 1, 1, 0, bias.data_ptr(), 128)
             if grp is not None:
                 grp.add(name, dy, x, dw, db, bias.data_ptr())
             else:
@@ -2448,7 +2387,7 @@ class LinearSlices(torch.autograd.Function):
     """n independent Linear layers with an ODD input width (DESA's Conv2d(3 -> 128) on the offsets of each radius, model/model.py:176-179) over the column blocks
     of one channel-stacked input: y[:, N i : N i + N] = x[:, Kp i : Kp i + K] W_i^T + b_i, written by n launches into ONE [rows, n N] tensor (so that the
     BatchNorm behind it is one 3-launch pass over n N channels instead of n passes).  x [rows, n * Kp] with Kp = K rounded up to 4 (the pad columns zero) and no
-    gradient (the offsets are not differentiated); backward = the n weight gradients from dY's column blocks in place (kpf_conv2d_wgrad_groups: ldx, ldy, trim)."""
+    gradient (the offsets are not differentiated); backward = the n weight gradients from dY's column blocks in place (conv_wgrad_hip: ld, valid)."""
 
     @staticmethod
     def forward(ctx, x, keys, cache, *wb):
@@ -2472,22 +2411,15 @@ class LinearSlices(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import lib as L
-        lib = L.load()
         xc, *ws = ctx.saved_tensors
         n, N, K, Kp, has_b = ctx.meta
         rows = xc.shape[0]
         dy = dy.float().contiguous()
-        st = torch.cuda.current_stream().cuda_stream
+        dy4, x4 = dy.view(1, 1, rows, n * N), xc.view(1, 1, rows, n * Kp)
         grads = []
-        nws = lib.kpf_conv2d_wgrad_ws_floats(rows, N, Kp)
-        for i in range(n):
-            wsb = torch.empty(nws, device=xc.device, dtype=torch.float32)
-            dw = torch.empty(tuple(ws[i].shape), device=xc.device, dtype=torch.float32)
-            db = torch.empty(N, device=xc.device, dtype=torch.float32) if has_b[i] else None
-            _wgrad_groups(lib, dy.data_ptr() + 4 * N * i, xc.data_ptr() + 4 * Kp * i, L.KPF_DT_F32, dw, db, wsb, nws, 1,
-                          (1, 1, rows, Kp, n * Kp, 1, rows, N, n * N, 1, 1, 1, 1, 0, 0, K, N), st, weight=ws[i], bias_ptr=ctx.bias_ptrs[i])
-            grads += [dw, db]
+        for i in range(n):  # column block i of both operands, where it is
+            grads += conv_wgrad_hip(dy4[..., N * i:N * (i + 1)], x4[..., Kp * i:Kp * (i + 1)], ws[i].shape, 1, 0, has_b[i], weight=ws[i], bias_ptr=ctx.bias_ptrs[i],
+                                    ld=(n * Kp, n * N), valid=(K, N))
         return (None, None, None) + tuple(grads)
 
 
@@ -2528,14 +2460,11 @@ class LinearCat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import lib as L
         from .engine import Act, conv
-        lib = L.load()
         n, N, kps, has_b, keys, cache = ctx.meta
         xcs, ws = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
         rows = xcs[0].shape[0]
         dy = dy.float().contiguous()
-        st = torch.cuda.current_stream().cuda_stream
         dxs, grads = [], []
         for i in range(n):
             K, Kp = kps[i]
@@ -2549,12 +2478,8 @@ class LinearCat(torch.autograd.Function):
             dxs.append(dx)
             dw = db = None
             if ctx.needs_input_grad[3 + n + 2 * i]:
-                nws = lib.kpf_conv2d_wgrad_ws_floats(rows, N, Kp)
-                wsb = torch.empty(nws, device=dy.device, dtype=torch.float32)
-                dw = torch.empty(tuple(ws[i].shape), device=dy.device, dtype=torch.float32)
-                db = torch.empty(N, device=dy.device, dtype=torch.float32) if has_b[i] else None
-                _wgrad_groups(lib, dy.data_ptr() + 4 * N * i, xcs[i].data_ptr(), L.KPF_DT_F32, dw, db, wsb, nws, 1,
-                              (1, 1, rows, Kp, Kp, 1, rows, N, n * N, 1, 1, 1, 1, 0, 0, K, N), st, weight=ws[i], bias_ptr=ctx.bias_ptrs[i])
+                dw, db = conv_wgrad_hip(dy.view(1, 1, rows, n * N)[..., N * i:N * (i + 1)], xcs[i].view(1, 1, rows, Kp), ws[i].shape, 1, 0, has_b[i], weight=ws[i],
+                                        bias_ptr=ctx.bias_ptrs[i], ld=(Kp, n * N), valid=(K, N))
             grads += [dw, db]
         return (None, None, None) + tuple(dxs) + tuple(grads)
 
@@ -2817,7 +2742,6 @@ class Conv2dNHWC(torch.autograd.Function):
         G = ctx.groups
         dres = dy.to(ctx.res_dtype) if (getattr(ctx, "res_dtype", None) is not None and ctx.needs_input_grad[10]) else None
         if ctx.odd is not None:  # odd-width Linear (see forward): x is the padded operand [M, 1, 1, cpad]
-            from . import lib as L
             cin_given, cpad, npad = ctx.odd
             Cw = weight.shape[1]
             tdt = torch.float32 if prec == "f32" else _TDT[prec]
@@ -2827,15 +2751,9 @@ class Conv2dNHWC(torch.autograd.Function):
                 # that padded x itself never reads them back — concatenations slice their own columns out)
                 dx = _conv_any(_dgrad_pack(ctx, weight.detach(), 1, prec, pad=0, n_pad=npad), dyp, prec, out_ld=cin_given).view(B, H, W, cin_given).to(ctx.x_dtype)
             if ctx.needs_input_grad[1]:
-                lib = L.load()
-                want_db = has_bias and ctx.needs_input_grad[2]
-                M = B * H * W
-                nws = lib.kpf_conv2d_wgrad_ws_floats(M, npad, cpad)
-                ws = torch.empty(nws, device=x.device, dtype=torch.float32)
-                dw = torch.empty(tuple(weight.shape), device=x.device, dtype=torch.float32)
-                db = torch.empty(N, device=x.device, dtype=torch.float32) if want_db else None
-                _wgrad_groups(lib, dyp.data_ptr(), x.data_ptr(), _KDT[tdt], dw, db, ws, nws, 1, (B, H, W, cpad, cpad, H, W, npad, npad, 1, 1, 1, 1, 0, 0, Cw, N),
-                              torch.cuda.current_stream().cuda_stream, weight=weight, bias_ptr=ctx.bias_ptr)
+                # (both operands at their padded widths, in the step's storage type; dW / db without the zero channels)
+                dw, db = conv_wgrad_hip(dyp.view(B, H, W, npad), x, weight.shape, 1, 0, has_bias and ctx.needs_input_grad[2], weight=weight, bias_ptr=ctx.bias_ptr,
+                                        ld=(cpad, npad), valid=(Cw, N))
             return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
         if G > 1:  # channel-stacked groups: the same three GEMMs, one launch each for all groups
             key, cache = ctx.pack
@@ -2881,11 +2799,8 @@ class Conv2dNHWC(torch.autograd.Function):
             # hand-written split-K weight gradient (fp32 products and accumulation in every precision mode: the master weight's
             # gradient is not rounded to 16 bits; 16-bit dY / X are read as stored), bias gradient from the same pass
             want_db = has_bias and ctx.needs_input_grad[2]
-            grp = DeferredParamGrads.wants(ctx.pack[0], ctx.pack[1], dy, x, KH, KW, stride, pad)
-            if grp is not None and want_db:  # the bias gradient is handed over unwritten too: same conditions as for the weight
-                bp = grp.by_ptr.get(ctx.bias_ptr)
-                if bp is None or bp.numel() != N or bp.grad is not None:
-                    grp = None
+            # (the bias gradient is handed over unwritten too: same conditions as for the weight)
+            grp = DeferredParamGrads.wants(ctx.pack[0], ctx.pack[1], dy, x, KH, KW, stride, pad, ctx.bias_ptr if want_db else None, N)
             if grp is not None:  # small Linear layer: its weight gradient joins the grouped launch after backward
                 dyc, xc = dy.contiguous(), x.contiguous()
                 dw = torch.empty(tuple(weight.shape), device=x.device, dtype=torch.float32)

@@ -1,4 +1,4 @@
-"""Weight-gradient kernels of the training step (kpf_conv2d_wgrad_f32, kpf_dwconv7_wgrad_f32, kpf_dwconv7_f32) against
+"""Weight-gradient kernels of the training step (kpf_conv2d_wgrad, kpf_dwconv7_wgrad, kpf_dwconv7_f32) against
 torch's CPU float64 convolution_backward on the same seeded inputs.  fp32 tolerance: 2e-5 of the gradient's range
 (sums of up to 1.3e5 products, different summation order)."""
 import pytest
@@ -127,7 +127,7 @@ def test_batchnorm_relu_rows_matches_torch(M, Cc, relu):
                                   (2, 9, 9, 264, 136, 1, 1, 0), (2, 14, 14, 8, 64, 7, 2, 3), (1, 3, 3, 8, 8, 1, 1, 0),
                                   (2, 4, 4, 768, 1536, 1, 1, 0), (1, 5, 5, 1096, 1032, 1, 1, 0)])  # (the last two: >= 256 tiles of 64 x 64 -> the unsplit 64-tile form)
 def test_conv_wgrad_16bit_operands_match_fp64_on_the_rounded_values(case, tdt):
-    """kpf_conv2d_wgrad_h16: dY and X in 16-bit storage, fp32 products and sums — equal to the fp64 gradient of the ROUNDED operands to
+    """kpf_conv2d_wgrad, 16-bit operands: dY and X in 16-bit storage, fp32 products and sums — equal to the fp64 gradient of the ROUNDED operands to
     fp32 accumulation accuracy (nothing else is rounded)."""
     from keypointfusion_amd.training import conv_wgrad_hip
     B, H, W, Cin, N, k, stride, pad = case
@@ -573,7 +573,7 @@ def test_fused_adamw_matches_torch_adamw_and_exchanges_state():
 
 
 def test_grouped_linear_weight_gradients_after_backward():
-    """training.GroupedLinearWgrad (kpf_linear_wgrad_grouped): the weight / bias gradients of many small Linear layers in one launch per 80
+    """training.DeferredParamGrads, Linear half (kpf_linear_wgrad_grouped): the weight / bias gradients of many small Linear layers in one launch per 80
     layers after backward, against fp64 — more layers than one launch carries, ragged row counts (1, 21, 672, 1000), widths that are not
     whole tiles, layers without bias; every dW must have been ADOPTED as the parameter's .grad (no copy of the unwritten tensor); layers
     outside the rule (too many rows, sliced weight key) take the immediate path inside the same pass; a weight used twice is refused."""
@@ -596,7 +596,7 @@ def test_grouped_linear_weight_gradients_after_backward():
             w.grad = x.grad = None
             if b is not None:
                 b.grad = None
-        ctx = T.GroupedLinearWgrad(named) if grouped else __import__("contextlib").nullcontext()
+        ctx = T.DeferredParamGrads(named) if grouped else __import__("contextlib").nullcontext()
         with ctx as grp:
             tot = 0
             for i, (w, b, x) in enumerate(layers):
@@ -622,13 +622,13 @@ def test_grouped_linear_weight_gradients_after_backward():
             assert float((b.grad.cpu().double() - rb).abs().max()) <= 2e-5 * max(float(rb.abs().max()), 1.0), i
         assert float((x.grad.cpu().double() - dy @ wr).abs().max()) <= 2e-5 * float((dy @ wr).abs().max()), i
     with pytest.raises(RuntimeError, match="second gradient"):
-        with T.GroupedLinearWgrad(named):
+        with T.DeferredParamGrads(named):
             w, b, x = layers[0]
             w.grad = None  # (a parameter that still holds a gradient is not deferred at all: autograd would add to it)
             if b is not None:
                 b.grad = None
             (T.linear_hip(x, w, b, "f32", None, "l0", cache).sum() + T.linear_hip(x, w, b, "f32", None, "l0", cache).sum()).backward()
-    assert T.GroupedLinearWgrad.active is None
+    assert T.DeferredParamGrads.active is None
     w, b, x = layers[0]
     # a stale gradient: autograd would ADD the still-unwritten tensor to it instead of adopting it -> such a parameter is not deferred at all (ADVICE
     # r03: decided before anything is handed to autograd, not detected afterwards); it takes the per-layer kernels and accumulates correctly
@@ -637,14 +637,14 @@ def test_grouped_linear_weight_gradients_after_backward():
     if b is not None:
         b.grad = None
     x.grad = None
-    with T.GroupedLinearWgrad(named) as grp:
+    with T.DeferredParamGrads(named) as grp:
         T.linear_hip(x, w, b, "f32", None, "l0", cache).square().sum().backward()
         assert len(grp.items) == 0
     assert torch.equal(w.grad, want + 1.0)
 
 
 def test_deferred_layernorm_and_layer_scale_parameter_sums_are_bit_identical():
-    """training.DeferredParamGrads, column-sum half (kpf_ln_train_backward_partial / kpf_layer_scale_backward_partial +
+    """training.DeferredParamGrads, column-sum half (kpf_ln_train_backward / kpf_layer_scale_backward with a descriptor +
     kpf_colsum_reduce_grouped): d gamma / d beta of many LayerNorm and layer-scale layers reduced in grouped launches after backward —
     same bits as the per-layer reduce, more layers than one launch carries, both storage types; parameters the model does not own
     (not in the name map) keep the immediate path."""
@@ -690,7 +690,7 @@ def test_deferred_layernorm_and_layer_scale_parameter_sums_are_bit_identical():
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_batched_weight_gradient_reduces_are_bit_identical(dt):
-    """training.DeferredParamGrads, reduce half (kpf_conv2d_wgrad_deferred / kpf_dwconv7_wgrad_deferred + kpf_wgrad_reduce_multi): the fixed-order
+    """training.DeferredParamGrads, reduce half (kpf_conv2d_wgrad / kpf_dwconv7_wgrad with a descriptor + kpf_wgrad_reduce_multi): the fixed-order
     reduces behind the split weight-gradient GEMMs of a backward pass issued in one launch per 24 calls — same bits as a reduce launch per
     call; dense / 3x3 / strided / grouped / depthwise layers, more calls than one launch carries, a paired parameter (two parameters side by
     side behind one weight tensor) and a parameter outside the name map (keeps its own reduce)."""
@@ -782,7 +782,7 @@ def test_joint_heatmap_and_geometry_gate_match_torch():
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_skip_path_gradient_is_folded_into_the_producing_backward_kernel(dt):
     """BatchNormReLU / DwConv7NHWC with alias=True return their input a second time; the gradient that reaches the alias (the skip path of a
-    Residual / ConvNeXt block) is added to dx by kpf_bn_train_backward_add / kpf_dwconv7_add_f32 inside the backward kernel.  Against
+    Residual / ConvNeXt block) is added to dx by kpf_bn_train_backward (addend) / kpf_dwconv7_add_f32 inside the backward kernel.  Against
     torch in float64 on the same (rounded) operands: y, dx = layer gradient + skip gradient, parameter gradients; alias unused or used
     alone also work."""
     from keypointfusion_amd import training as T
@@ -821,8 +821,8 @@ def test_skip_path_gradient_is_folded_into_the_producing_backward_kernel(dt):
         assert rel(y3, yr2) <= 3e-5 and rel(xd3.grad, xr2.grad) <= 3e-5 and rel(wd3.grad, wr2.grad) <= 1e-4 and rel(bd3.grad, br2.grad) <= 1e-4
 
 
-# ---- round 4: channel-stacked groups (the paired backbones of the training step: kpf_conv_desc::groups, kpf_conv2d_wgrad_groups,
-# kpf_ln_train_*_g, kpf_layer_scale_backward_g).  Same kernels, tile choice and summation order per group as the ungrouped calls on the
+# ---- round 4: channel-stacked groups (the paired backbones of the training step: kpf_conv_desc::groups, the groups / G arguments of kpf_conv2d_wgrad,
+# kpf_ln_train_*, kpf_layer_scale_backward).  Same kernels, tile choice and summation order per group as the ungrouped calls on the
 # channel slices, so the comparison is BIT-EXACT, forward and every gradient (16-bit weight gradients: to rounding, see the test).
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("case", [(4, 16, 16, 96, 384, 1, 1, 0), (4, 16, 16, 384, 96, 1, 1, 0), (3, 8, 8, 64, 64, 3, 1, 1), (2, 16, 16, 96, 192, 2, 2, 0),

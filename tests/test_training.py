@@ -114,6 +114,63 @@ def test_host_side_of_the_fused_optimizer_and_deferred_gradients_without_a_gpu()
         assert T.DeferredParamGrads.wants("k", object(), x, x, 3, 3, 1, 1) is None and T.DeferredParamGrads.wants("k", object(), x.half(), x.half(), 1, 1, 1, 0) is None
         assert T.DeferredParamGrads.wants("k", object(), x, x, 1, 1, 1, 0) is d
     assert T.DeferredParamGrads.active is None  # (nothing was registered: flush() had nothing to launch)
+    # ---- the ledger: one claim per parameter and pass, the bias rule inside wants(), adoption verified before anything is launched ----
+    bias, wide = torch.nn.Parameter(torch.zeros(8)), torch.nn.Parameter(torch.zeros(12))
+    named = {"w": w, "k": k, "k.bias": bias, "wide": wide}
+    dw, db = torch.empty(8, 8), torch.empty(8)
+    with pytest.raises(RuntimeError, match="second gradient"):
+        with T.DeferredParamGrads(named) as d:
+            assert T.DeferredParamGrads.wants_reduce(k, 8, bias.data_ptr()) is d
+            T.DeferredParamGrads.wants_reduce(k, 8, bias.data_ptr())  # (returned None before: the second gradient was then written while the first was pending)
+    assert T.DeferredParamGrads.active is None
+    with pytest.raises(RuntimeError, match="second gradient"):
+        with T.DeferredParamGrads(named) as d:
+            d.add("k", x, x, dw, None)
+            d.add("k", x, x, dw, None)
+    with pytest.raises(RuntimeError, match="second gradient"):
+        with T.DeferredParamGrads(named) as d:
+            d.add_colsum(w, None, None, db)
+            d.add_colsum(w, None, None, db)
+    with pytest.raises(RuntimeError, match="second gradient"):  # (one claim per parameter, whichever path makes it)
+        with T.DeferredParamGrads(named) as d:
+            d.add("k", x, x, dw, None)
+            T.DeferredParamGrads.wants_reduce(k)
+    with T.DeferredParamGrads(named) as d:
+        want = lambda ptr, n: T.DeferredParamGrads.wants("k", object(), x, x, 1, 1, 1, 0, ptr, n)
+        assert want(bias.data_ptr(), 8) is d
+        assert want(torch.zeros(8).data_ptr(), 8) is None  # a bias the map does not know
+        assert want(wide.data_ptr(), 8) is None  # a known parameter of another width
+        bias.grad = torch.zeros(8)
+        assert want(bias.data_ptr(), 8) is None  # a bias that already holds a gradient
+        bias.grad = None
+    # a promise whose parameter's .grad is another tensor: flush() raises before any library call (there is no GPU here: a call would fail differently)
+    cases = ((lambda d: d.add("k", x, x, dw, db, bias.data_ptr()), dict(k=dw, bias=db.clone())),  # the weight adopted its tensor, the bias holds a copy
+             (lambda d: d.add_colsum(w, None, None, db), dict(w=db.clone())),
+             (lambda d: d._promise("a convolution weight", k.data_ptr(), dw.data_ptr(), dw.numel(), late=False), dict(k=None)))  # never received it at all
+    for hand_over, grads in cases:
+        with pytest.raises(RuntimeError, match="copied before it was written"):
+            with T.DeferredParamGrads(named) as d:
+                hand_over(d)
+                k.grad, bias.grad, w.grad = grads.get("k"), grads.get("bias"), grads.get("w")  # (what autograd left behind)
+        assert d.items == [] and d.colsums == [] and d.promises == [] and d.reduces == []  # (nothing stays pending after the refusal)
+    with T.DeferredParamGrads(named) as d:  # adopted: verified and, with no launch pending, done (the reduce behind it was issued during backward)
+        d._promise("a convolution weight", k.data_ptr(), dw.data_ptr(), dw.numel(), late=False)
+        k.grad = dw
+    assert d.last_deferred == []  # (only gradients that flush() itself fills are reported to GraphedTrainStep)
+    k.grad = bias.grad = w.grad = None
+    # the adjacent-parameter walk: a paired storage is accepted as a whole, part of it (or a range that ends inside a parameter) is not
+    pa, pb = torch.nn.Parameter(torch.ones(8)), torch.nn.Parameter(torch.ones(8))
+    both = T.pair_storage({}, "p", pa, pb)
+    with T.DeferredParamGrads({"a": pa, "b": pb}) as d:
+        assert [(q is pa or q is pb, off) for q, off in d._walk(both.data_ptr(), 16)] == [(True, 0), (True, 32)]
+        assert T.DeferredParamGrads.wants_colsum(both.view(16)) is d and T.DeferredParamGrads.wants_colsum(pa) is d
+        assert d._walk(both.data_ptr(), 12) is None and d._walk(both.data_ptr() + 16, 8) is None and d._walk(both.data_ptr(), 20) is None
+        assert T.DeferredParamGrads.wants_colsum(both.view(16)[:12]) is None
+        pb.grad = torch.zeros(8)
+        assert T.DeferredParamGrads.wants_colsum(both.view(16)) is None and T.DeferredParamGrads.wants_colsum(pa) is d  # (one half already holds a gradient)
+        pb.grad = None
+    with T.DeferredParamGrads({"a": pa}) as d:  # (the second half is not a parameter this pass knows)
+        assert T.DeferredParamGrads.wants_colsum(both.view(16)) is None
 
 
 def _ddp_worker(rank, world, port, q):

@@ -1,4 +1,4 @@
-"""Weight-gradient kernels on the training step's own shapes (B = 32, 128^2 ConvNeXt-T): the 16-bit-MFMA form (kpf_conv2d_wgrad_h16:
+"""Weight-gradient kernels on the training step's own shapes (B = 32, 128^2 ConvNeXt-T): the 16-bit-MFMA form (kpf_conv2d_wgrad on 16-bit operands:
 wgrad_h16_kernel + reduce), the round-2 widening form (KPF_WGRAD_H16_WIDEN=1: run this script twice) and the fp32 form, timed with HIP
 events over 5 replays of a captured graph of 20 calls; algorithmic bytes = dY + X read once + dW written once, FLOP = 2 M N K.
   python3 tools/wgrad_bench.py > profiles/r03_wgrad_bench.txt"""
