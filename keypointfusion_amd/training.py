@@ -606,6 +606,31 @@ class StackedPack(Pack):
 _TDT = {"bf16": torch.bfloat16, "f16": torch.float16}
 
 
+class _Operand:
+    """One registered operand of a PackCache: `desc`, its filled kpf_pack_desc (lib.PackDesc: fields by name; first_block is assigned when a
+    table is built), and what keeps it valid — the source address(es), shape and precision it was registered with, the Pack the layers
+    launch with and the source tensor kept alive."""
+    __slots__ = ("desc", "src", "shape", "prec", "pc", "keep")
+
+    def __init__(self, keep, dst, N, Cin, KH, KW, mode, n_pad, Kp, rows, src_dtype=0, dst_dtype=0, reserved=0, src=None, shape=None, prec=None, pc=None):
+        from . import lib as L
+        self.desc = L.PackDesc(keep.data_ptr(), dst, N, Cin, KH, KW, mode, n_pad, Kp, rows, src_dtype, dst_dtype, 0, reserved)
+        self.src, self.shape, self.prec, self.pc, self.keep = src, shape, prec, pc, keep
+
+
+def _desc_table(ops):
+    """Operands -> (ctypes array of their kpf_pack_desc with first_block assigned in order, total blocks of the one launch that packs them all)."""
+    from . import lib as L
+    blocks = L.load().kpf_pack_desc_blocks  # (the kernel's own rule: LDS-staged forms per operand geometry, csrc/kpf_train.hip)
+    arr = (L.PackDesc * len(ops))()
+    blk = 0
+    for i, op in enumerate(ops):
+        op.desc.first_block = blk
+        arr[i] = op.desc
+        blk += int(blocks(C.byref(arr[i])))
+    return arr, blk
+
+
 class PackCache:
     """Persistent kernel-layout operands of the training step's convolutions / Linears, refreshed from the parameters by ONE launch per
     iteration (kpf_pack_conv_weights_multi): the state dict keeps the reference's OIHW layout and fp32 master values, the kernels read
@@ -615,7 +640,7 @@ class PackCache:
     copies) are packed per use.  Mixed precision: the fp32 master is rounded to the 16-bit operand by the same kernel."""
 
     def __init__(self):
-        self.entries = {}
+        self.entries = {}  # key -> _Operand
         self.table = None
         self.total_blocks = 0
         self.dirty = False
@@ -623,16 +648,15 @@ class PackCache:
     def get(self, key, weight, bias, mode, prec, **kw):
         w = weight.detach()
         ent = self.entries.get(key)
-        if ent is not None and ent["src"] == w.data_ptr() and ent["shape"] == tuple(w.shape) and ent["prec"] == prec:
-            pc = ent["pc"]
+        if ent is not None and ent.src == w.data_ptr() and ent.shape == tuple(w.shape) and ent.prec == prec:
+            pc = ent.pc
         else:
             assert w.is_contiguous(), "PackCache: a registered source must be a contiguous view of parameter storage"
             pc = DevPack.packed(w, None, mode, prec, **kw)
-            w4 = _oihw(w)
+            N, Cin, KH, KW = _oihw(w).shape
             buf = pc.w if pc.w is not None else pc.w16
-            self.entries[key] = {"src": w.data_ptr(), "shape": tuple(w.shape), "prec": prec, "pc": pc, "keep": w,
-                                 "desc": (w.data_ptr(), buf.data_ptr(), w4.shape[0], w4.shape[1], w4.shape[2], w4.shape[3], mode,
-                                          kw.get("n_pad") or w4.shape[0], buf.shape[1], buf.shape[0], _KDT[w.dtype], _KDT[buf.dtype])}
+            self.entries[key] = _Operand(w, buf.data_ptr(), N, Cin, KH, KW, mode, kw.get("n_pad") or N, buf.shape[1], buf.shape[0], _KDT[w.dtype], _KDT[buf.dtype],
+                                         src=w.data_ptr(), shape=tuple(w.shape), prec=prec, pc=pc)
             self.dirty = True
         pc.b = _fp32_bias(bias)
         return pc
@@ -645,8 +669,8 @@ class PackCache:
         key = ("stack",) + tuple(names)
         srcs = tuple(t.detach().data_ptr() for t in list(weights) + list(biases))
         ent = self.entries.get(key + (0, 0))
-        if ent is not None and ent["srcs"] == srcs:
-            return ent["sp"]
+        if ent is not None and ent.src == srcs:
+            return ent.pc
         assert not torch.cuda.is_current_stream_capturing(), "PackCache.get_stacked: register the operand in an eager iteration, before a capture"
         n, (Cn, K) = len(weights), weights[0].shape
         dev = weights[0].device
@@ -657,47 +681,39 @@ class PackCache:
         buf1 = torch.zeros(K, n * Cn, device=dev)
         bufb = torch.zeros(n * Cn, device=dev)
         sp = StackedPack(geom, buf0, bufb, Pack(ConvGeom.plain(K, n * Cn, 1, 1), w=buf1))  # (Cn % 32 == 0: the data-gradient rows need no padding)
-        new = []
+        new = {}
         for i, (w, b) in enumerate(zip(weights, biases)):
             w, b = w.detach(), b.detach()
-            new.append((key + (0, i), {"srcs": srcs, "sp": sp, "keep": w, "desc": (w.data_ptr(), buf0.data_ptr() + i * Cn * kp * 4, Cn, K, 1, 1, 0, Cn, kp, Cn, 0, 0)}))
-            new.append((key + (1, i), {"keep": w, "desc": (w.data_ptr(), buf1.data_ptr() + i * Cn * 4, Cn, K, 1, 1, 1, Cn, Cn, K, 0, 0, n * Cn)}))
-            new.append((key + (4, i), {"keep": b, "desc": (b.data_ptr(), bufb.data_ptr() + i * Cn * 4, Cn, 1, 1, 1, 4, Cn, Cn, 1, 0, 0)}))
+            new[key + (0, i)] = _Operand(w, buf0.data_ptr() + i * Cn * kp * 4, Cn, K, 1, 1, 0, Cn, kp, Cn, src=srcs, pc=sp)  # rows i Cn .. of the forward operand
+            new[key + (1, i)] = _Operand(w, buf1.data_ptr() + i * Cn * 4, Cn, K, 1, 1, 1, Cn, Cn, K, reserved=n * Cn, src=srcs, pc=sp)  # columns; reserved: the row stride there
+            new[key + (4, i)] = _Operand(b, bufb.data_ptr() + i * Cn * 4, Cn, 1, 1, 1, 4, Cn, Cn, 1, src=srcs, pc=sp)  # its slot of the bias vector
         # fill them now (one launch from a temporary table), then they are part of every refresh
-        arr = (L.PackDesc * len(new))()
-        blk = 0
-        for a, (_, e) in zip(arr, new):
-            d = e["desc"]
-            a.src, a.dst = d[0], d[1]
-            a.N, a.Cin, a.KH, a.KW, a.mode, a.n_pad, a.Kp, a.rows = d[2:10]
-            a.src_dtype, a.dst_dtype, a.first_block, a.reserved = d[10], d[11], blk, (d[12] if len(d) > 12 else 0)
-            blk += int(L.load().kpf_pack_desc_blocks(C.byref(a)))
+        arr, blk = _desc_table(list(new.values()))
         table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
         L.check(L.load().kpf_pack_conv_weights_multi(table.data_ptr(), len(new), blk, torch.cuda.current_stream().cuda_stream), "kpf_pack_conv_weights_multi")
         sp._table = table  # (alive until the launch has run)
-        for k, e in new:
-            self.entries[k] = e
+        self.entries.update(new)
         self.dirty = True
         return sp
+
+    def rehome(self, homes):
+        """{key: tensor}: these registered operands now live at these addresses (GroupedPack needs G > 2 of them equally spaced) — the Pack the layers
+        hold and the refresh launch's destination move together."""
+        for key, buf in homes.items():
+            op = self.entries[key]
+            setattr(op.pc, "w" if op.pc.w is not None else "w16", buf)
+            op.desc.dst = buf.data_ptr()
+        self.dirty = True
 
     def build_table(self):
         """(Re)build the device-resident descriptor table when operands were registered since the last one — a host -> device upload, so not
         inside a graph capture (TrainGraph calls this at the end of every eager forward; a capture then starts with a current table)."""
         if not self.dirty or not self.entries or torch.cuda.is_current_stream_capturing():
             return
-        from . import lib as L
-        arr = (L.PackDesc * len(self.entries))()
-        blk = 0
-        for i, ent in enumerate(self.entries.values()):
-            d = ent["desc"]
-            arr[i].src, arr[i].dst = d[0], d[1]
-            arr[i].N, arr[i].Cin, arr[i].KH, arr[i].KW, arr[i].mode, arr[i].n_pad, arr[i].Kp, arr[i].rows = d[2:10]
-            arr[i].src_dtype, arr[i].dst_dtype, arr[i].first_block = d[10], d[11], blk
-            arr[i].reserved = d[12] if len(d) > 12 else 0  # (destination row stride of an operand that is a column range of a stacked matrix)
-            blk += int(L.load().kpf_pack_desc_blocks(C.byref(arr[i])))  # (the kernel's own rule: LDS-staged forms per operand geometry, csrc/kpf_train.hip)
-        dev = next(iter(self.entries.values()))["keep"].device
-        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        self.total_blocks, self.dirty = blk, False
+        ops = list(self.entries.values())
+        arr, self.total_blocks = _desc_table(ops)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(ops[0].keep.device)
+        self.dirty = False
 
     def refresh(self):
         """Rewrite every registered operand from the current parameter values (call at the start of a forward)."""
@@ -710,10 +726,10 @@ class PackCache:
         if self.dirty:
             if torch.cuda.is_current_stream_capturing():  # no host -> device table upload inside a capture: one launch per operand
                 for ent in self.entries.values():
-                    d = ent["desc"]
-                    if len(d) > 12 or d[6] == 4:
+                    d = ent.desc
+                    if d.mode == 4 or d.reserved != 0:  # (a bias slot or a column range of a stacked matrix: forms only the table launch has)
                         raise RuntimeError("PackCache: a stacked operand was registered during a graph capture (run one eager iteration first)")
-                    L.check(lib.kpf_pack_conv_weight(d[0], d[10], d[1], d[11], d[2], d[3], d[4], d[5], d[6], d[7], d[8], st), "kpf_pack_conv_weight")
+                    L.check(lib.kpf_pack_conv_weight(d.src, d.src_dtype, d.dst, d.dst_dtype, d.N, d.Cin, d.KH, d.KW, d.mode, d.n_pad, d.Kp, st), "kpf_pack_conv_weight")
                 return
         L.check(lib.kpf_pack_conv_weights_multi(self.table.data_ptr(), len(self.entries), self.total_blocks, st), "kpf_pack_conv_weights_multi")
 
@@ -739,56 +755,44 @@ class head_mma:
 
 
 def _conv_any(pc, x4, prec, out_ld=None, res=None, flags=0, out2=None):
-    """engine.conv (fp32) or engine16.conv16 (bf16 / f16) on an NHWC tensor [B, H, W, C]; returns the NHWC output tensor.  A GroupedPack
-    (G convolutions over channel-stacked activations, one launch): x4 is [B, H, W, G*Cin], the result [B, OH, OW, G*N].  out_ld > N: the result
-    is [B, OH, OW, out_ld] with only the first N channels written."""
+    """engine.conv (fp32) or engine16.conv16 (bf16 / f16) on an NHWC tensor [B, H, W, C]; returns the NHWC output tensor.  Three launch forms:
+    plain (the GEMM allocates [B, OH, OW, N]); a GroupedPack (G convolutions over channel-stacked activations, one launch): x4 is [B, H, W, G*Cin],
+    the result [B, OH, OW, G*N]; out_ld > N: the result is [B, OH, OW, out_ld] with only the first N channels written (no epilogue operands)."""
     from .engine import Act, conv
     B, H, W, Cc = x4.shape
     G = pc.groups or 1
-    if prec == "f32" and _HEAD_MMA[0]:
+    narrow = out_ld is not None and out_ld != pc.N
+    if narrow:
+        assert G == 1 and pc.merge == 1 and res is None and out2 is None and not flags  # (as it always was: this form takes no product-type word either)
+    elif prec == "f32" and _HEAD_MMA[0]:
         flags |= _HEAD_MMA[0]
-    if out_ld is not None and out_ld != pc.N:
-        assert G == 1 and pc.merge == 1
-        tdt, kdt = (None, None) if prec == "f32" else __import__("keypointfusion_amd.engine16", fromlist=["DTYPES"]).DTYPES[prec]
-        xb = (x4 if prec == "f32" else x4.to(tdt)).contiguous().view(-1)
-        OH, OW = pc.geom.out_hw(H, W)
-        ob = torch.empty(B * OH * OW * out_ld, device=x4.device, dtype=xb.dtype)
-        oa = Act(ob, B, OH, OW, pc.N, ld=out_ld)
-        if prec == "f32":
-            conv(pc, Act(xb, B, H, W, Cc), out=oa)
-        else:
-            from .engine16 import conv16
-            conv16(pc.as16(tdt), Act(xb, B, H, W, Cc), kdt, out=oa)
-        return ob.view(B, OH, OW, out_ld)
     tdt = kdt = None
     if prec != "f32":
         from .engine16 import DTYPES, conv16
         tdt, kdt = DTYPES[prec]
     xld = Cc
-    if prec == "f32" and G == 1 and H == 1 and W == 1 and x4.dtype == torch.float32 and not x4.is_contiguous() and x4.stride(-1) == 1 and x4.stride(0) % 4 == 0 \
-            and x4.stride(0) > Cc and x4.data_ptr() % 16 == 0:
+    if prec == "f32" and G == 1 and not narrow and H == 1 and W == 1 and x4.dtype == torch.float32 and not x4.is_contiguous() and x4.stride(-1) == 1 \
+            and x4.stride(0) % 4 == 0 and x4.stride(0) > Cc and x4.data_ptr() % 16 == 0:
         xb, xld = x4, x4.stride(0)  # rows that are a column slice of a wider matrix (BallGroup's outputs): read in place (in_ld), no copy
     else:
         xb = (x4 if prec == "f32" else x4.to(tdt)).contiguous().view(-1)
-    if G > 1:
-        assert Cc == G * pc.Cin and pc.merge == 1, (Cc, G, pc.Cin)
+    # the four activation views, from (G, out_ld): a group reads / writes its channel block of rows that are G blocks wide
+    assert Cc == G * pc.Cin or G == 1, (Cc, G, pc.Cin)
+    xa = Act(xb, B, H, W, Cc // G, ld=xld)
+    oa = None
+    if narrow or G > 1:  # (plain: the GEMM allocates its dense output, also for the merged view of a patchify operand)
+        assert pc.merge == 1
         OH, OW = pc.geom.out_hw(H, W)
-        xa = Act(xb, B, H, W, pc.Cin, ld=Cc)
-        ob = torch.empty(B * OH * OW * G * pc.N, device=x4.device, dtype=xb.dtype)
-        oa = Act(ob, B, OH, OW, pc.N, ld=G * pc.N)
-        ra = None if res is None else Act(res.to(xb.dtype).contiguous().view(-1), B, OH, OW, pc.N, ld=G * pc.N)  # (out = conv + res: the residual epilogue)
-        o2 = None if out2 is None else Act(out2.view(-1), B, OH, OW, pc.N, ld=G * pc.N)  # (second output of a GELU epilogue: the pre-activation)
-        conv(pc, xa, out=oa, res=ra, flags=flags, out2=o2) if prec == "f32" else conv16(pc.as16(tdt), xa, kdt, out=oa, res=ra, flags=flags, out2=o2)
-        return ob.view(B, OH, OW, G * pc.N)
-    ra = None
-    if res is not None:
-        ra = Act(res.to(xb.dtype).contiguous().view(-1), res.shape[0], res.shape[1], res.shape[2], res.shape[3])
-    o2 = None if out2 is None else Act(out2.view(-1), out2.shape[0], out2.shape[1], out2.shape[2], out2.shape[3])
+        old = out_ld if narrow else G * pc.N
+        oa = Act(torch.empty(B * OH * OW * old, device=x4.device, dtype=xb.dtype), B, OH, OW, pc.N, ld=old)
+    side = lambda t: None if t is None else Act(t.view(-1), t.shape[0], t.shape[1], t.shape[2], t.shape[3] // G, ld=t.shape[3])  # (of the output's shape)
+    ra = side(None if res is None else res.to(xb.dtype).contiguous())  # (out = conv + res: the residual epilogue)
+    o2 = side(out2)  # (second output of a GELU epilogue: the pre-activation)
     if prec == "f32":
-        out = conv(pc, Act(xb, B, H, W, Cc, ld=xld), res=ra, flags=flags, out2=o2)
+        out = conv(pc, xa, out=oa, res=ra, flags=flags, out2=o2)
     else:
-        out = conv16(pc.as16(tdt), Act(xb, B, H, W, Cc), kdt, res=ra, flags=flags, out2=o2)
-    return out.buf.view(out.B, out.H, out.W, out.C)
+        out = conv16(pc.as16(tdt), xa, kdt, out=oa, res=ra, flags=flags, out2=o2)
+    return out.buf.view(out.B, out.H, out.W, out.ld)
 
 
 def pad_rows(src, width, dtype=None):
@@ -853,13 +857,16 @@ class GroupedPack(Pack):
         self.pcs = pcs  # (keeps the G operands alive)
 
 
-def _grouped_pack(cache, key, weight, bias, G, mode, prec, **kw):
-    """The GroupedPack of a paired weight [G*N, Cin, KH, KW]: one (cached) operand per group slice."""
-    n = weight.shape[0] // G
-    if cache is not None and key is not None:
-        pcs = [cache.get((key, mode, g), weight[g * n:(g + 1) * n], None, mode, prec, **kw) for g in range(G)]
-    else:
-        pcs = [DevPack.packed(weight[g * n:(g + 1) * n], None, mode, prec, **kw) for g in range(G)]
+def _operand(cache, key, weight, bias, mode, prec, groups=1, **kw):
+    """THE operand lookup of the training convolutions / Linears: the Pack of `weight` (OIHW or [N][K]) for pack mode `mode` (DevPack.packed) — the
+    persistent operand registered under (key, mode) when there is a cache AND a key, packed on the spot otherwise.  groups = G > 1: the GroupedPack
+    of a paired weight [G*N, Cin, KH, KW], one operand per group slice (registered under (key, mode, g)); `bias` is then the whole [G*N] vector."""
+    cached = cache is not None and key is not None
+    if groups == 1:
+        return cache.get((key, mode), weight, bias, mode, prec, **kw) if cached else DevPack.packed(weight, bias, mode, prec, **kw)
+    G, n = groups, weight.shape[0] // groups
+    parts = [weight[g * n:(g + 1) * n] for g in range(G)]
+    pcs = [cache.get((key, mode, g), w, None, mode, prec, **kw) if cached else DevPack.packed(w, None, mode, prec, **kw) for g, w in enumerate(parts)]
     if G > 2:  # one launch descriptor carries ONE group stride: more than two operands must be equally spaced — re-home them into one allocation (once)
         attr = "w" if pcs[0].w is not None else "w16"
         bufs = [getattr(pc, attr) for pc in pcs]
@@ -868,15 +875,13 @@ def _grouped_pack(cache, key, weight, bias, G, mode, prec, **kw):
         if any(b.data_ptr() - a.data_ptr() != step for a, b in zip(bufs, bufs[1:])) or step % (8 * es):
             assert not torch.cuda.is_current_stream_capturing(), "grouped operands must be registered in an eager iteration, before a capture"
             big = torch.empty((G,) + tuple(bufs[0].shape), device=bufs[0].device, dtype=bufs[0].dtype)
-            for g, (pc, b) in enumerate(zip(pcs, bufs)):
+            for g, b in enumerate(bufs):
                 big[g].copy_(b)
-                setattr(pc, attr, big[g])
-                if cache is not None and key is not None:
-                    ent = cache.entries[(key, mode, g)]
-                    d = list(ent["desc"])
-                    d[1] = big[g].data_ptr()  # (the refresh launch writes the operand where the kernels now read it)
-                    ent["desc"] = tuple(d)
-                    cache.dirty = True
+            if cached:
+                cache.rehome({(key, mode, g): big[g] for g in range(G)})  # (the refresh launch writes the operands where the kernels now read them)
+            else:
+                for g, pc in enumerate(pcs):
+                    setattr(pc, attr, big[g])
     return GroupedPack(pcs, bias)
 
 
@@ -1212,13 +1217,12 @@ def _dw_taps(weight, mirrored, pack=(None, None)):
     w = weight.detach().contiguous()
     Cc = w.shape[0]
     key, cache = pack
+    mode = 3 if mirrored else 2
     if cache is not None:
-        mode = 3 if mirrored else 2
-        return cache.get((key, mode), w, None, mode, "f32", n_pad=Cc).w
-    kp = Cc
-    out = torch.empty(49, kp, device=w.device, dtype=torch.float32)
-    L.check(L.load().kpf_pack_conv_weight(w.data_ptr(), 0, out.data_ptr(), 0, Cc, 1, 7, 7, 3 if mirrored else 2, Cc, kp,
-                                          torch.cuda.current_stream().cuda_stream), "kpf_pack_conv_weight")
+        return _operand(cache, key, w, None, mode, "f32", n_pad=Cc).w
+    # (not through the lookup: DevPack.packed rounds the row length up to 32, this table is [49][C] for any C % 4 == 0)
+    out = torch.empty(49, Cc, device=w.device, dtype=torch.float32)
+    L.check(L.load().kpf_pack_conv_weight(w.data_ptr(), 0, out.data_ptr(), 0, Cc, 1, 7, 7, mode, Cc, Cc, torch.cuda.current_stream().cuda_stream), "kpf_pack_conv_weight")
     return out
 
 
@@ -1695,11 +1699,12 @@ class BertStack21(torch.autograd.Function):
         key = tuple(p.data_ptr() for p in params)
         t = BertStack21._tables.get(key)
         if t is None:
+            assert not torch.cuda.is_current_stream_capturing(), "BertStack21.param_table: run one eager iteration after moving / re-homing parameters, before a capture"
             for p in params:
                 if p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16:
                     raise ValueError("BertStack21: parameters must be contiguous 16-byte-aligned fp32 tensors")
             # (never evicted: a table is 0.5 KB, holds addresses only — valid for as long as those addresses are parameters, whoever owns them — and an eviction
-            #  between a GraphedTrainStep's warm-up and its capture would make the capture build one, a host -> device copy a capture cannot contain)
+            #  between a GraphedTrainStep's warm-up and its capture would make the capture build one, a host -> device copy a capture cannot contain: the assertion)
             t = BertStack21._tables[key] = torch.tensor(key, dtype=torch.int64, device=params[0].device)
         return t
 
@@ -2402,7 +2407,7 @@ class LinearSlices(torch.autograd.Function):
         y = torch.empty(rows, n * N, device=x.device, dtype=torch.float32)
         for i in range(n):
             w2 = ws[i].reshape(N, K, 1, 1)
-            pc = cache.get((keys[i], 0), w2, bs[i], 0, "f32", stride=1, pad=0, patchify=False) if cache is not None else DevPack.packed(w2, bs[i], 0, "f32", stride=1, pad=0, patchify=False)
+            pc = _operand(cache, keys[i], w2, bs[i], 0, "f32", stride=1, pad=0, patchify=False)
             conv(_OddPack(pc, Kp), Act(xc.view(-1), 1, 1, rows, Kp, n * Kp, Kp * i), out=Act(y.view(-1), 1, 1, rows, N, n * N, N * i))
         ctx.save_for_backward(xc, *ws)
         ctx.meta = (n, N, K, Kp, [b is not None for b in bs])
@@ -2449,7 +2454,7 @@ class LinearCat(torch.autograd.Function):
             Kp = xc.shape[1]
             assert xc.shape[0] == rows and Kp % 4 == 0 and Kp >= K and Kp - K < 4 and ws[i].shape[0] == N and N % 4 == 0
             w2 = ws[i].reshape(N, K, 1, 1)
-            pc = cache.get((keys[i], 0), w2, bs[i], 0, "f32", stride=1, pad=0, patchify=False) if cache is not None else DevPack.packed(w2, bs[i], 0, "f32", stride=1, pad=0, patchify=False)
+            pc = _operand(cache, keys[i], w2, bs[i], 0, "f32", stride=1, pad=0, patchify=False)
             conv(_OddPack(pc, Kp) if Kp != K else pc, Act(xc.view(-1), 1, 1, rows, Kp), out=Act(y.view(-1), 1, 1, rows, N, n * N, N * i))
             xcs.append(xc)
             kps.append((K, Kp))
@@ -2472,7 +2477,7 @@ class LinearCat(torch.autograd.Function):
             if ctx.needs_input_grad[3 + i]:
                 assert K == Kp, "LinearCat: data gradients for whole channel groups only"
                 w2 = ws[i].detach().reshape(N, K, 1, 1)
-                pc = cache.get((keys[i], 1), w2, None, 1, "f32", pad=0, n_pad=N) if cache is not None else DevPack.packed(w2, None, 1, "f32", pad=0, n_pad=N)
+                pc = _operand(cache, keys[i], w2, None, 1, "f32", pad=0, n_pad=N)
                 dx = torch.empty(rows, K, device=dy.device, dtype=torch.float32)
                 conv(pc, Act(dy.view(-1), 1, 1, rows, N, n * N, N * i), out=Act(dx.view(-1), 1, 1, rows, K))
             dxs.append(dx)
@@ -2633,14 +2638,12 @@ class Conv2dNHWC(torch.autograd.Function):
         gelu_out: returns (z, gelu(z)) with z = x W^T + b from ONE launch (KPF_ACT_GELU_SAVE: the GEMM's epilogue stores both); gelu(z) carries no
         gradient — hand it to the following layer as g_pre together with gelu_in=True (that layer then skips its own GELU pass and returns d z)."""
         assert x.is_cuda and x.dim() == 4
-        ctx.mma16 = _HEAD_MMA[0]  # (the product type of this forward: the data-gradient GEMM of the backward takes the same)
         B, H, W, Cin = x.shape
         N, Cw, KH, KW = weight.shape
         cm = 4 if prec == "f32" else 8
         patch = stride == KH == KW and pad == 0 and stride > 1
         use16 = prec != "f32" and w16 is not None
-        ctx.groups = groups
-        ctx.odd = None
+        record = lambda saved, **kw: Conv2dNHWC._record(ctx, saved, x, bias, key, cache, groups, stride, pad, prec, **kw)
         if groups == 1 and KH == 1 and KW == 1 and stride == 1 and pad == 0 and w16 is None and (Cw % cm or N % cm):
             # A Linear whose widths are not whole channel groups (the 3-d coordinates, 105 pose channels, 131- / 149-wide inputs and 3- / 21-wide
             # outputs of the fusion head: model/model.py:99-104, 254-262, 336).  The GEMM sees the input at the padded width cpad: x either arrives
@@ -2650,30 +2653,18 @@ class Conv2dNHWC(torch.autograd.Function):
             assert Cin in (Cw, cpad), "Conv2dNHWC: input width %d matches neither the weight's %d nor its padded width %d" % (Cin, Cw, cpad)
             tdt = torch.float32 if prec == "f32" else _TDT[prec]
             xc = pad_rows(x, cpad, tdt) if Cin != cpad else (x.to(tdt).contiguous())
-            if cache is not None and key is not None:
-                pc = cache.get((key, 0), weight, bias, 0, prec, stride=1, pad=0, patchify=False)
-            else:
-                pc = DevPack.packed(weight, bias, 0, prec, stride=1, pad=0, patchify=False)
+            pc = _operand(cache, key, weight, bias, 0, prec, stride=1, pad=0, patchify=False)
             y = _conv_any(_OddPack(pc, cpad), xc, prec)
-            ctx.pack = (key, cache)
             assert res is None and not gelu_in and not alias and not gelu_out
-            ctx.odd = (Cin, cpad, npad)
-            ctx.save_for_backward(xc, weight, None)
-            ctx.alias = ctx.gelu_out = False
-            ctx.w16, ctx.x_dtype = None, x.dtype
-            ctx.conf = (stride, pad, False, bias is not None, prec)
-            ctx.bias_ptr = bias.data_ptr() if bias is not None else None
+            record((xc, weight, None), odd=(Cin, cpad, npad))
             return y
         assert Cw * groups == Cin and Cw % cm == 0, "Conv2dNHWC: input channels must match and be a multiple of 4 (8 for 16-bit)"
         if groups > 1:
             assert w16 is None and (N // groups) % cm == 0, "grouped Conv2dNHWC: whole channel groups per group"
             patch = False  # (the kx-merging GEMM view of a patchify convolution does not survive channel stacking: general strided form)
-            pc = _grouped_pack(cache, key, weight, bias, groups, 0, prec, stride=stride, pad=pad, patchify=False)
-        elif cache is not None and key is not None:  # persistent operand, refreshed once per iteration for all layers (PackCache)
-            pc = cache.get((key, 0), weight, bias, 0, prec, stride=stride, pad=pad, patchify=patch)
-        else:
-            pc = DevPack.packed(w16 if use16 else weight, bias, 0, prec, stride=stride, pad=pad, patchify=patch)
-        ctx.pack = (key, cache)
+        # (a persistent operand, refreshed once per iteration for all layers, is packed from the fp32 master; one packed per use from the 16-bit shadow)
+        wsrc = w16 if use16 and (cache is None or key is None) else weight
+        pc = _operand(cache, key, wsrc, bias, 0, prec, groups, stride=stride, pad=pad, patchify=patch)
         xc = x.float() if prec == "f32" else x.to(_TDT[prec])  # the operand as the GEMM sees it — also what the weight gradient multiplies
         z = None
         if gelu_in:
@@ -2686,51 +2677,64 @@ class Conv2dNHWC(torch.autograd.Function):
             else:
                 xc = torch.empty_like(z)
                 L.check(L.load().kpf_gelu_forward(z.data_ptr(), xc.data_ptr(), _KDT[z.dtype], z.numel(), torch.cuda.current_stream().cuda_stream), "kpf_gelu_forward")
+        w16 = w16 if use16 else None
         if gelu_out:
             from . import lib as L
-            assert KH == 1 and KW == 1 and stride == 1 and pad == 0 and res is None and groups * 0 == 0, "gelu_out: Linear layers"
+            assert KH == 1 and KW == 1 and stride == 1 and pad == 0 and res is None, "gelu_out: Linear layers"
             zo = torch.empty(B, H, W, N, device=x.device, dtype=xc.dtype)
             y = _conv_any(pc, xc, prec, flags=L.KPF_ACT_GELU, out2=zo)
-            ctx.res_dtype, ctx.alias, ctx.gelu_out = None, bool(alias), True
-            ctx.save_for_backward(xc, weight, z)
-            ctx.w16 = w16 if use16 else None
-            ctx.x_dtype = x.dtype
-            ctx.conf = (stride, pad, patch, bias is not None, prec)
-            ctx.bias_ptr = bias.data_ptr() if bias is not None else None
+            record((xc, weight, z), w16=w16, alias=alias, gelu_out=True)
             ctx.mark_non_differentiable(y)
             ctx.set_materialize_grads(False)
             return (zo, y, x.view(x.shape)) if alias else (zo, y)
-        ctx.gelu_out = False
         y = _conv_any(pc, xc, prec, res=res)
-        ctx.res_dtype = None if res is None else res.dtype
-        ctx.alias = bool(alias)
         if alias:
-            assert not gelu_in and stride == 1 and not patch and groups == 1
+            assert not gelu_in and stride == 1 and not patch
             ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xc, weight, z)
-        ctx.w16 = w16 if use16 else None
-        ctx.x_dtype = x.dtype
-        ctx.conf = (stride, pad, patch, bias is not None, prec)
-        ctx.bias_ptr = bias.data_ptr() if bias is not None else None  # (identifies the bias PARAMETER for DeferredParamGrads' adoption check)
+        record((xc, weight, z), w16=w16, alias=alias, res=res)
         return (y, x.view(x.shape)) if alias else y
+
+    # apply()'s arguments after ctx, in order: the ONE definition of where a gradient goes in backward's return tuple and of the needs_input_grad lookups
+    ARGS = ("x", "weight", "bias", "stride", "pad", "prec", "w16", "key", "cache", "groups", "res", "gelu_in", "alias", "gelu_out", "g_pre")
+
+    @staticmethod
+    def _record(ctx, saved, x, bias, key, cache, groups, stride, pad, prec, odd=None, w16=None, alias=False, gelu_out=False, res=None):
+        """Every field the backward reads, set in ONE place for the three forward exits (odd-width, gelu_out, plain).  saved: (the operand as the GEMM
+        saw it, weight, the pre-activation of gelu_in or None)."""
+        assert not alias or groups == 1, "alias: ungrouped layers"
+        ctx.save_for_backward(*saved)
+        ctx.mma16 = _HEAD_MMA[0]  # (the product type of this forward: the data-gradient GEMM of the backward takes the same)
+        ctx.groups, ctx.odd, ctx.pack = groups, odd, (key, cache)
+        ctx.alias, ctx.gelu_out = bool(alias), gelu_out
+        ctx.res_dtype = None if res is None else res.dtype
+        ctx.w16, ctx.x_dtype = w16, x.dtype
+        ctx.conf = (stride, pad, bias is not None, prec)
+        ctx.bias_ptr = bias.data_ptr() if bias is not None else None  # (identifies the bias PARAMETER for DeferredParamGrads' adoption check)
+
+    @staticmethod
+    def _grads(dx=None, dw=None, db=None, dres=None):
+        """backward's return value: the four gradients at the positions of their arguments in ARGS, None everywhere else."""
+        by_arg = {"x": dx, "weight": dw, "bias": db, "res": dres}
+        return tuple(by_arg.get(a) for a in Conv2dNHWC.ARGS)
 
     @staticmethod
     def backward(ctx, dy, g2=None, g3=None):
-        with head_mma(int(getattr(ctx, "mma16", 0))):
+        with head_mma(int(ctx.mma16)):
             return Conv2dNHWC._backward(ctx, dy, g2, g3)
 
     @staticmethod
     def _backward(ctx, dy, g2=None, g3=None):
-        g_alias = (g3 if getattr(ctx, "gelu_out", False) else g2) if ctx.alias else None  # (outputs: y [, gelu(y) without gradient] [, the alias of x])
+        need = lambda arg: ctx.needs_input_grad[Conv2dNHWC.ARGS.index(arg)]
+        g_alias = (g3 if ctx.gelu_out else g2) if ctx.alias else None  # (outputs: y [, gelu(y) without gradient] [, the alias of x])
         x, weight, z = ctx.saved_tensors
         if dy is None:  # (only the alias was used)
-            return (g_alias,) + (None,) * 14
+            return Conv2dNHWC._grads(dx=g_alias)
         if g_alias is not None:
             assert z is None
             gg_alias = dict(res=g_alias.to(x.dtype).contiguous().view(x.shape))
         else:
             gg_alias = {}
-        stride, pad, patch, has_bias, prec = ctx.conf
+        stride, pad, has_bias, prec = ctx.conf
         from . import lib as L
         gg = dict(res=z, flags=L.KPF_RES_GELU_GRAD) if z is not None else {}  # (gelu_in: the data gradient's epilogue multiplies by gelu'(z))
         B, H, W, Cin = x.shape
@@ -2740,52 +2744,38 @@ class Conv2dNHWC(torch.autograd.Function):
         dx = dw = db = None
         cmul = 4 if prec == "f32" else 8  # channel granularity of the GEMM's activation operand
         G = ctx.groups
-        dres = dy.to(ctx.res_dtype) if (getattr(ctx, "res_dtype", None) is not None and ctx.needs_input_grad[10]) else None
+        key, cache = ctx.pack
+        dres = dy.to(ctx.res_dtype) if (ctx.res_dtype is not None and need("res")) else None
         if ctx.odd is not None:  # odd-width Linear (see forward): x is the padded operand [M, 1, 1, cpad]
             cin_given, cpad, npad = ctx.odd
             Cw = weight.shape[1]
             tdt = torch.float32 if prec == "f32" else _TDT[prec]
             dyp = pad_rows(dy, npad, tdt) if npad != N else dy.to(tdt).contiguous()
-            if ctx.needs_input_grad[0]:
+            if need("x"):
                 # dX = dY W: rows of the transposed weight; written at the width the caller's x had (its zero channels receive nothing: a producer
                 # that padded x itself never reads them back — concatenations slice their own columns out)
-                dx = _conv_any(_dgrad_pack(ctx, weight.detach(), 1, prec, pad=0, n_pad=npad), dyp, prec, out_ld=cin_given).view(B, H, W, cin_given).to(ctx.x_dtype)
-            if ctx.needs_input_grad[1]:
+                dx = _conv_any(_operand(cache, key, weight.detach(), None, 1, prec, pad=0, n_pad=npad), dyp, prec, out_ld=cin_given).view(B, H, W, cin_given).to(ctx.x_dtype)
+            if need("weight"):
                 # (both operands at their padded widths, in the step's storage type; dW / db without the zero channels)
-                dw, db = conv_wgrad_hip(dyp.view(B, H, W, npad), x, weight.shape, 1, 0, has_bias and ctx.needs_input_grad[2], weight=weight, bias_ptr=ctx.bias_ptr,
+                dw, db = conv_wgrad_hip(dyp.view(B, H, W, npad), x, weight.shape, 1, 0, has_bias and need("bias"), weight=weight, bias_ptr=ctx.bias_ptr,
                                         ld=(cpad, npad), valid=(Cw, N))
-            return dx, dw, db, None, None, None, None, None, None, None, None, None, None, None, None
-        if G > 1:  # channel-stacked groups: the same three GEMMs, one launch each for all groups
-            key, cache = ctx.pack
-            n, wd = N // G, weight.detach()
-            if ctx.needs_input_grad[0]:
-                dyc = dy if prec == "f32" else dy.to(_TDT[prec])
-                if stride == KH == KW and pad == 0 and stride > 1:  # patchify: rows of dY @ W[n][(ky,kx,c)] per group, then the pixel un-shuffle
-                    g = _conv_any(_grouped_pack(cache, key, wd, None, G, 2, prec, n_pad=n), dyc, prec).view(B, OH, OW, G, KH, KW, Cin // G)
-                    # (the un-shuffle and the change to x's type in ONE strided copy)
-                    dx = torch.empty(B, OH * KH, OW * KW, Cin, device=g.device, dtype=ctx.x_dtype)
-                    dx.view(B, OH, KH, OW, KW, G, Cin // G).copy_(g.permute(0, 1, 4, 2, 5, 3, 6))
-                    if dx.shape[1] != H or dx.shape[2] != W:
-                        dx = F.pad(dx, (0, 0, 0, W - dx.shape[2], 0, H - dx.shape[1]))
-                else:
-                    assert stride == 1, "grouped Conv2dNHWC: stride 1 or patchify"
-                    dx = _conv_any(_grouped_pack(cache, key, wd, None, G, 1, prec, pad=pad, n_pad=n), dyc, prec, **gg).view(B, H, W, Cin)
-                dx = dx.to(ctx.x_dtype)
-            if ctx.needs_input_grad[1]:
-                dw, db = conv_wgrad_hip(dy, x, weight.shape, stride, pad, has_bias and ctx.needs_input_grad[2], groups=G, weight=weight, bias_ptr=ctx.bias_ptr)
-            return dx, dw, db, None, None, None, None, None, None, None, dres, None, None, None, None
-        if ctx.needs_input_grad[0]:
+            return Conv2dNHWC._grads(dx, dw, db)
+        if need("x"):  # one path for G >= 1 (channel-stacked groups: the same GEMMs, one launch for all groups)
             wsrc = ctx.w16 if ctx.w16 is not None else weight.detach()
-            npad = (N + cmul - 1) // cmul * cmul
-            dy_in = dy if npad == N else F.pad(dy, (0, npad - N))  # the kernel needs whole channel groups: zero channels on dY (and zero weight rows)
-            if patch:  # dX[b, oy*s+ky, ox*s+kx, c] = sum_n dY[b,oy,ox,n] W[n,c,ky,kx]: rows of a GEMM, then un-shuffle
-                g = _conv_any(_dgrad_pack(ctx, wsrc, 2, prec, n_pad=npad), dy_in, prec).view(B, OH, OW, KH, KW, Cin)
-                dx = torch.empty(B, OH * KH, OW * KW, Cin, device=g.device, dtype=ctx.x_dtype)  # (un-shuffle + x's type in one strided copy)
-                dx.view(B, OH, KH, OW, KW, Cin).copy_(g.permute(0, 1, 3, 2, 4, 5))
+            n = N // G
+            npad = (n + cmul - 1) // cmul * cmul  # the kernel needs whole channel groups: zero channels on dY (and zero weight rows)
+            assert npad == n or G == 1  # (grouped: whole channel groups per group, the forward's own condition)
+            dy_in = dy if npad == n else F.pad(dy, (0, npad - n))
+            if stride == KH == KW and pad == 0 and stride > 1:
+                # patchify: dX[b, oy*s+ky, ox*s+kx, c] = sum_n dY[b,oy,ox,n] W[n,c,ky,kx] — rows of dY @ W[n][(ky,kx,c)] per group, then the pixel un-shuffle
+                g = _conv_any(_operand(cache, key, wsrc, None, 2, prec, G, n_pad=npad), dy_in, prec).view(B, OH, OW, G, KH, KW, Cin // G)
+                dx = torch.empty(B, OH * KH, OW * KW, Cin, device=g.device, dtype=ctx.x_dtype)  # (the un-shuffle and the change to x's type in ONE strided copy)
+                dx.view(B, OH, KH, OW, KW, G, Cin // G).copy_(g.permute(0, 1, 4, 2, 5, 3, 6))
                 if dx.shape[1] != H or dx.shape[2] != W:  # rows / columns the strided convolution never read
                     dx = F.pad(dx, (0, 0, 0, W - dx.shape[2], 0, H - dx.shape[1]))
             else:
                 if stride != 1:
+                    assert G == 1, "grouped Conv2dNHWC: stride 1 or patchify"
                     # strided (non-patchify) convolution — ResNet's 3x3/s2 and 1x1/s2 (model/resnet.py:52-55,190-194): the data gradient
                     # is the stride-1 transposed convolution of dY dilated by the stride (zeros between its pixels), laid out so that
                     # the symmetric padding KH-1-pad yields exactly H x W rows (rows the strided convolution never read get zeros)
@@ -2793,39 +2783,35 @@ class Conv2dNHWC(torch.autograd.Function):
                     dil = dy_in.new_zeros(B, hz, wz, npad)
                     dil[:, :(OH - 1) * stride + 1:stride, :(OW - 1) * stride + 1:stride] = dy_in
                     dy_in = dil
-                dx = _conv_any(_dgrad_pack(ctx, wsrc, 1, prec, pad=pad, n_pad=npad), dy_in, prec, **gg, **gg_alias).view(B, H, W, Cin)
+                dx = _conv_any(_operand(cache, key, wsrc, None, 1, prec, G, pad=pad, n_pad=npad), dy_in, prec, **gg, **gg_alias).view(B, H, W, Cin)
             dx = dx.to(ctx.x_dtype)
-        if ctx.needs_input_grad[1] and Cin % 4 == 0 and N % 4 == 0:
+        want_db = has_bias and need("bias")
+        if G > 1:
+            if need("weight"):
+                dw, db = conv_wgrad_hip(dy, x, weight.shape, stride, pad, want_db, groups=G, weight=weight, bias_ptr=ctx.bias_ptr)
+        elif need("weight") and Cin % 4 == 0 and N % 4 == 0:
             # hand-written split-K weight gradient (fp32 products and accumulation in every precision mode: the master weight's
             # gradient is not rounded to 16 bits; 16-bit dY / X are read as stored), bias gradient from the same pass
-            want_db = has_bias and ctx.needs_input_grad[2]
             # (the bias gradient is handed over unwritten too: same conditions as for the weight)
-            grp = DeferredParamGrads.wants(ctx.pack[0], ctx.pack[1], dy, x, KH, KW, stride, pad, ctx.bias_ptr if want_db else None, N)
+            grp = DeferredParamGrads.wants(key, cache, dy, x, KH, KW, stride, pad, ctx.bias_ptr if want_db else None, N)
             if grp is not None:  # small Linear layer: its weight gradient joins the grouped launch after backward
                 dyc, xc = dy.contiguous(), x.contiguous()
                 dw = torch.empty(tuple(weight.shape), device=x.device, dtype=torch.float32)
                 db = torch.empty(N, device=x.device, dtype=torch.float32) if want_db else None
-                grp.add(ctx.pack[0], dyc, xc, dw, db, ctx.bias_ptr if want_db else None)
+                grp.add(key, dyc, xc, dw, db, ctx.bias_ptr if want_db else None)
             else:
                 dw, db = conv_wgrad_hip(dy, x, weight.shape, stride, pad, want_db, weight=weight, bias_ptr=ctx.bias_ptr)
-            return dx, dw, db, None, None, None, None, None, None, None, dres, None, None, None, None
-        if ctx.needs_input_grad[1]:
-            xw = x if prec == "f32" else x.to(_TDT[prec])  # weight gradient in the compute precision, handed to the fp32 master weight
-            dyw = dy if prec == "f32" else dy.to(_TDT[prec])
-            if KH == 1 and KW == 1 and stride == 1:
-                dw = (dyw.view(-1, N).t() @ xw.reshape(-1, Cin)).view(N, Cin, 1, 1).float()
-            else:
-                dw = torch.nn.grad.conv2d_weight(xw.permute(0, 3, 1, 2), weight.shape, dyw.permute(0, 3, 1, 2), stride=stride, padding=pad).float()
-        if has_bias and ctx.needs_input_grad[2]:
-            db = dy.float().view(-1, N).sum(0)
-        return dx, dw, db, None, None, None, None, None, None, None, dres, None, None, None, None
-
-
-def _dgrad_pack(ctx, wsrc, mode, prec, **kw):
-    key, cache = ctx.pack
-    if cache is not None and key is not None:
-        return cache.get((key, mode), wsrc, None, mode, prec, **kw)
-    return DevPack.packed(wsrc, None, mode, prec, **kw)
+        else:  # widths that are not whole groups of 4: torch
+            if need("weight"):
+                xw = x if prec == "f32" else x.to(_TDT[prec])  # weight gradient in the compute precision, handed to the fp32 master weight
+                dyw = dy if prec == "f32" else dy.to(_TDT[prec])
+                if KH == 1 and KW == 1 and stride == 1:
+                    dw = (dyw.view(-1, N).t() @ xw.reshape(-1, Cin)).view(N, Cin, 1, 1).float()
+                else:
+                    dw = torch.nn.grad.conv2d_weight(xw.permute(0, 3, 1, 2), weight.shape, dyw.permute(0, 3, 1, 2), stride=stride, padding=pad).float()
+            if want_db:
+                db = dy.float().view(-1, N).sum(0)
+        return Conv2dNHWC._grads(dx, dw, db, dres)
 
 
 def conv2d_nhwc(x, weight, bias=None, stride=1, pad=0, prec="f32", w16=None, key=None, cache=None, groups=1, res=None):

@@ -210,6 +210,7 @@ def test_conv_wgrad_full_size_properties():
     (2, 32, 32, 4, 64, 7, 2, 3),      # ResNet stem 7x7 / s2 on the channel-padded image
     (2, 15, 17, 8, 16, 3, 2, 1),      # odd sizes
     (1, 10, 9, 8, 8, 3, 2, 0),        # rows / columns the strided window never reaches
+    (1, 9, 8, 8, 8, 2, 2, 0),         # patchify with a last row the 2x2 / s2 window never reaches: the zero remainder of the pixel un-shuffle
 ])
 def test_conv2d_nhwc_autograd_matches_torch(case):
     from keypointfusion_amd.training import conv2d_nhwc
@@ -826,7 +827,8 @@ def test_skip_path_gradient_is_folded_into_the_producing_backward_kernel(dt):
 # channel slices, so the comparison is BIT-EXACT, forward and every gradient (16-bit weight gradients: to rounding, see the test).
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 @pytest.mark.parametrize("case", [(4, 16, 16, 96, 384, 1, 1, 0), (4, 16, 16, 384, 96, 1, 1, 0), (3, 8, 8, 64, 64, 3, 1, 1), (2, 16, 16, 96, 192, 2, 2, 0),
-                                  (2, 4, 4, 128, 112, 1, 1, 0), (32, 4, 4, 768, 3072, 1, 1, 0)])
+                                  (2, 4, 4, 128, 112, 1, 1, 0), (32, 4, 4, 768, 3072, 1, 1, 0),
+                                  (2, 9, 8, 8, 16, 2, 2, 0)])  # (the last: x (2, 9, 8, 16) — the un-shuffle's zero remainder row with the group axis present)
 def test_grouped_convolution_is_bit_identical_to_per_group_calls(case, prec):
     from keypointfusion_amd import training as T
     B, H, W, Cin, N, k, stride, pad = case
@@ -1303,13 +1305,13 @@ def test_operand_refresh_forms_equal_the_single_operand_kernel(prec):
         pc = cache.get(("k%d" % i, mode), w, None, mode, prec, **kw)           # registered: packed by the single-operand kernel
         refs.append((pc.w if pc.w is not None else pc.w16).clone())
     for e in cache.entries.values():                                            # poison the operands, then let the one-launch refresh rewrite them
-        d = e["desc"]
-        buf = e["pc"].w if e["pc"].w is not None else e["pc"].w16
+        buf = e.pc.w if e.pc.w is not None else e.pc.w16
+        assert e.desc.dst == buf.data_ptr() and (e.desc.rows, e.desc.Kp) == tuple(buf.shape)
         buf.fill_(float("nan"))
     cache.refresh()
     torch.cuda.synchronize()
     for (shape, mode, kw), e, r in zip(cases, cache.entries.values(), refs):
-        buf = e["pc"].w if e["pc"].w is not None else e["pc"].w16
+        buf = e.pc.w if e.pc.w is not None else e.pc.w16
         assert torch.equal(buf.view(torch.int16 if buf.dtype != torch.float32 else torch.int32), r.view(torch.int16 if r.dtype != torch.float32 else torch.int32)), (shape, mode)
 
 

@@ -1,8 +1,14 @@
 """CPU tests of the implicit GEMM's operand (packs.ConvGeom / Pack and its constructors) and of the one launch-descriptor builder (engine.conv_desc).
 Every expected tuple, descriptor field and flag word is a literal worked out by hand from the formulas the constructors replaced; nothing here calls the
-code under test to learn what to expect, and nothing touches a device."""
+code under test to learn what to expect, and nothing touches a device.  Further down: PackCache's descriptor table and pack calls (literals recorded from
+the cache as it was before its entries became named records, under the same stand-in library), its behaviour under a faked graph capture, and
+Conv2dNHWC's argument positions and autograd-context fields."""
+import ctypes as C
+import inspect
+import re
 import types
 
+import pytest
 import torch
 
 from keypointfusion_amd import lib as L
@@ -178,3 +184,227 @@ def test_descriptor_builder_fills_every_field_for_both_row_lengths():
         gp = T.GroupedPack([Pack(ConvGeom.plain(8, 32, 1, 1), **{"w" if tdt == torch.float32 else "w16": big[i]}) for i in range(2)], None)
         d, out, optr, res, mo = conv_desc(gp, Act(buf(10 * 64), 1, 1, 10, 32, ld=64), kp, out=Act(buf(10 * 16), 1, 1, 10, 8, ld=16), flags=L.KPF_ACT_RELU)
         assert _fields(d) == _desc(B=1, IH=1, IW=10, Cin=32, in_ld=64, OH=1, OW=10, N=8, KH=1, KW=1, sh=1, sw=1, Kp=kp, out_ld=16, flags=1, groups=2, w_gstride=8 * kp) and mo == (10, 1, 10)
+
+
+# --- PackCache: every descriptor field and every kpf_pack_conv_weight argument, pinned to what the cache of commit f0e96db (positional 12- / 13-tuples)
+# produced under this same stand-in library; kpf_pack_desc_blocks is host code and is served by the real library.
+PACK_CASES = [((96, 48, 3, 3), 0, {}), ((128, 256, 3, 3), 1, dict(pad=1, n_pad=128)), ((100, 40, 3, 3), 1, dict(pad=1, n_pad=104)), ((192, 96, 2, 2), 0, dict(stride=2)),
+              ((192, 96, 2, 2), 2, dict(n_pad=192)), ((384, 1, 7, 7), 2, dict(n_pad=384)), ((200, 1, 7, 7), 3, dict(n_pad=200)), ((64, 8, 4, 4), 0, dict(stride=4)),
+              ((384, 96, 1, 1), 0, {}), ((384, 96, 1, 1), 1, dict(n_pad=384)), ((3, 128, 1, 1), 1, dict(n_pad=4)), ((105, 128, 1, 1), 0, {}), ((64, 20, 5, 5), 0, dict(pad=2))]
+# (src - source.data_ptr(), dst - operand.data_ptr(), N, Cin, KH, KW, mode, n_pad, Kp, rows, src_dtype, dst_dtype, first_block, reserved): the 13 cases, q | k | v
+# stacked (forward rows, data-gradient columns, bias slot each), three re-homed group operands (group 2 was registered first)
+PACK_DESCS = {
+    "f32": (534, [(0, 0, 96, 48, 3, 3, 0, 96, 448, 96, 0, 0, 0, 0),
+                 (0, 0, 128, 256, 3, 3, 1, 128, 1152, 256, 0, 0, 42, 0),
+                 (0, 0, 100, 40, 3, 3, 1, 104, 960, 40, 0, 0, 170, 0),
+                 (0, 0, 192, 96, 2, 2, 0, 192, 384, 192, 0, 0, 190, 0),
+                 (0, 0, 192, 96, 2, 2, 2, 192, 192, 384, 0, 0, 262, 0),
+                 (0, 0, 384, 1, 7, 7, 2, 384, 384, 49, 0, 0, 334, 0),
+                 (0, 0, 200, 1, 7, 7, 3, 200, 224, 49, 0, 0, 353, 0),
+                 (0, 0, 64, 8, 4, 4, 0, 64, 128, 64, 0, 0, 364, 0),
+                 (0, 0, 384, 96, 1, 1, 0, 384, 96, 384, 0, 0, 372, 0),
+                 (0, 0, 384, 96, 1, 1, 1, 384, 384, 96, 0, 0, 408, 0),
+                 (0, 0, 3, 128, 1, 1, 1, 4, 32, 128, 0, 0, 420, 0),
+                 (0, 0, 105, 128, 1, 1, 0, 105, 128, 105, 0, 0, 422, 0),
+                 (0, 0, 64, 20, 5, 5, 0, 64, 512, 64, 0, 0, 436, 0),
+                 (0, 0, 128, 128, 1, 1, 0, 128, 128, 128, 0, 0, 468, 0),
+                 (0, 0, 128, 128, 1, 1, 1, 128, 128, 128, 0, 0, 484, 384),
+                 (0, 0, 128, 1, 1, 1, 4, 128, 128, 1, 0, 0, 488, 0),
+                 (0, 65536, 128, 128, 1, 1, 0, 128, 128, 128, 0, 0, 489, 0),
+                 (0, 512, 128, 128, 1, 1, 1, 128, 128, 128, 0, 0, 505, 384),
+                 (0, 512, 128, 1, 1, 1, 4, 128, 128, 1, 0, 0, 509, 0),
+                 (0, 131072, 128, 128, 1, 1, 0, 128, 128, 128, 0, 0, 510, 0),
+                 (0, 1024, 128, 128, 1, 1, 1, 128, 128, 128, 0, 0, 526, 384),
+                 (0, 1024, 128, 1, 1, 1, 4, 128, 128, 1, 0, 0, 530, 0),
+                 (4096, 4096, 16, 32, 1, 1, 0, 16, 32, 16, 0, 0, 531, 0),
+                 (0, 0, 16, 32, 1, 1, 0, 16, 32, 16, 0, 0, 532, 0),
+                 (2048, 2048, 16, 32, 1, 1, 0, 16, 32, 16, 0, 0, 533, 0)]),
+    "bf16": (548, [(0, 0, 96, 48, 3, 3, 0, 96, 448, 96, 0, 1, 0, 0),
+                  (0, 0, 128, 256, 3, 3, 1, 128, 1152, 256, 0, 1, 42, 0),
+                  (0, 0, 100, 40, 3, 3, 1, 104, 960, 40, 0, 1, 170, 0),
+                  (0, 0, 192, 96, 2, 2, 0, 192, 384, 192, 0, 1, 190, 0),
+                  (0, 0, 192, 96, 2, 2, 2, 192, 192, 384, 0, 1, 262, 0),
+                  (0, 0, 384, 1, 7, 7, 2, 384, 384, 49, 0, 1, 334, 0),
+                  (0, 0, 200, 1, 7, 7, 3, 200, 256, 49, 0, 1, 353, 0),
+                  (0, 0, 64, 8, 4, 4, 0, 64, 128, 64, 0, 1, 366, 0),
+                  (0, 0, 384, 96, 1, 1, 0, 384, 128, 384, 0, 1, 374, 0),
+                  (0, 0, 384, 96, 1, 1, 1, 384, 384, 96, 0, 1, 422, 0),
+                  (0, 0, 3, 128, 1, 1, 1, 4, 64, 128, 0, 1, 434, 0),
+                  (0, 0, 105, 128, 1, 1, 0, 105, 128, 105, 0, 1, 436, 0),
+                  (0, 0, 64, 20, 5, 5, 0, 64, 512, 64, 0, 1, 450, 0),
+                  (0, 0, 128, 128, 1, 1, 0, 128, 128, 128, 0, 0, 482, 0),
+                  (0, 0, 128, 128, 1, 1, 1, 128, 128, 128, 0, 0, 498, 384),
+                  (0, 0, 128, 1, 1, 1, 4, 128, 128, 1, 0, 0, 502, 0),
+                  (0, 65536, 128, 128, 1, 1, 0, 128, 128, 128, 0, 0, 503, 0),
+                  (0, 512, 128, 128, 1, 1, 1, 128, 128, 128, 0, 0, 519, 384),
+                  (0, 512, 128, 1, 1, 1, 4, 128, 128, 1, 0, 0, 523, 0),
+                  (0, 131072, 128, 128, 1, 1, 0, 128, 128, 128, 0, 0, 524, 0),
+                  (0, 1024, 128, 128, 1, 1, 1, 128, 128, 128, 0, 0, 540, 384),
+                  (0, 1024, 128, 1, 1, 1, 4, 128, 128, 1, 0, 0, 544, 0),
+                  (4096, 4096, 16, 32, 1, 1, 0, 16, 64, 16, 0, 1, 545, 0),
+                  (0, 0, 16, 32, 1, 1, 0, 16, 64, 16, 0, 1, 546, 0),
+                  (2048, 2048, 16, 32, 1, 1, 0, 16, 64, 16, 0, 1, 547, 0)]),
+}
+# (src_dtype, dst_dtype, N, Cin, KH, KW, mode, n_pad, row length) of every kpf_pack_conv_weight call, in order
+PACK_CALLS = {
+    "f32": [(0, 0, 96, 48, 3, 3, 0, 96, 448),
+            (0, 0, 128, 256, 3, 3, 1, 128, 1152),
+            (0, 0, 100, 40, 3, 3, 1, 104, 960),
+            (0, 0, 192, 96, 2, 2, 0, 192, 384),
+            (0, 0, 192, 96, 2, 2, 2, 192, 192),
+            (0, 0, 384, 1, 7, 7, 2, 384, 384),
+            (0, 0, 200, 1, 7, 7, 3, 200, 224),
+            (0, 0, 64, 8, 4, 4, 0, 64, 128),
+            (0, 0, 384, 96, 1, 1, 0, 384, 96),
+            (0, 0, 384, 96, 1, 1, 1, 384, 384),
+            (0, 0, 3, 128, 1, 1, 1, 4, 32),
+            (0, 0, 105, 128, 1, 1, 0, 105, 128),
+            (0, 0, 64, 20, 5, 5, 0, 64, 512),
+            (0, 0, 16, 32, 1, 1, 0, 16, 32),
+            (0, 0, 16, 32, 1, 1, 0, 16, 32),
+            (0, 0, 16, 32, 1, 1, 0, 16, 32)],
+    "bf16": [(0, 1, 96, 48, 3, 3, 0, 96, 448),
+             (0, 1, 128, 256, 3, 3, 1, 128, 1152),
+             (0, 1, 100, 40, 3, 3, 1, 104, 960),
+             (0, 1, 192, 96, 2, 2, 0, 192, 384),
+             (0, 1, 192, 96, 2, 2, 2, 192, 192),
+             (0, 1, 384, 1, 7, 7, 2, 384, 384),
+             (0, 1, 200, 1, 7, 7, 3, 200, 256),
+             (0, 1, 64, 8, 4, 4, 0, 64, 128),
+             (0, 1, 384, 96, 1, 1, 0, 384, 128),
+             (0, 1, 384, 96, 1, 1, 1, 384, 384),
+             (0, 1, 3, 128, 1, 1, 1, 4, 64),
+             (0, 1, 105, 128, 1, 1, 0, 105, 128),
+             (0, 1, 64, 20, 5, 5, 0, 64, 512),
+             (0, 1, 16, 32, 1, 1, 0, 16, 64),
+             (0, 1, 16, 32, 1, 1, 0, 16, 64),
+             (0, 1, 16, 32, 1, 1, 0, 16, 64)],
+}
+
+
+def _fake_pack_lib(monkeypatch):
+    packs, multis, capturing = [], [], [False]
+    fake = types.SimpleNamespace(kpf_pack_conv_weight=lambda src, sdt, dst, ddt, *a: packs.append((src, dst, (sdt, ddt) + a[:-1])) or 0,
+                                 kpf_pack_conv_weights_multi=lambda table, n, blk, st: multis.append((n, blk)) or 0,
+                                 kpf_pack_desc_blocks=L.load().kpf_pack_desc_blocks)
+    monkeypatch.setattr(L, "load", lambda: fake)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: types.SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
+    return packs, multis, capturing
+
+
+@pytest.mark.parametrize("prec", ["f32", "bf16"])
+def test_pack_cache_table_and_pack_calls_are_the_literals_of_the_tuple_era(monkeypatch, prec):
+    packs, multis, capturing = _fake_pack_lib(monkeypatch)
+    cache, bases = T.PackCache(), []
+    for i, (shape, mode, kw) in enumerate(PACK_CASES):
+        w = torch.zeros(shape)
+        pc = cache.get(("k%d" % i, mode), w, None, mode, prec, **kw)
+        bases.append((w, pc.w if pc.w is not None else pc.w16))
+    qkv, bqkv = [torch.zeros(128, 128) for _ in range(3)], [torch.zeros(128) for _ in range(3)]
+    sp = cache.get_stacked(["q", "k", "v"], qkv, bqkv)
+    assert multis == [(9, 63)] and cache.get_stacked(["q", "k", "v"], qkv, bqkv) is sp and multis == [(9, 63)]  # (filled by one launch of its own table, once)
+    for w, b in zip(qkv, bqkv):
+        bases += [(w, sp.w), (w, sp.dgrad.w), (b, sp.b)]
+    wg = torch.zeros(3 * 16, 32, 1, 1)
+    cache.get(("grp", 0, 2), wg[32:48], None, 0, prec, stride=1, pad=0, patchify=False)  # (group 2 first: the three allocations cannot come out equally spaced)
+    gp = T._operand(cache, "grp", wg, torch.zeros(48), 0, prec, 3, stride=1, pad=0, patchify=False)
+    home = gp.w if prec == "f32" else gp.w16
+    assert (gp.groups, gp.w_gstride) == (3, 16 * home.shape[1]) and all((pc.w if prec == "f32" else pc.w16).data_ptr() == home.data_ptr() + 2048 * g for g, pc in enumerate(gp.pcs))
+    bases += [(wg, home)] * 3
+    assert cache.dirty and cache.table is None
+    cache.build_table()
+    total, want = PACK_DESCS[prec]
+    arr = (L.PackDesc * len(want)).from_buffer_copy(bytes(cache.table.numpy()))
+    assert len(cache.entries) == len(want) == len(bases) == 25 and cache.table.numel() == 25 * C.sizeof(L.PackDesc) and not cache.dirty
+    got = [((d.src or 0) - s.data_ptr(), (d.dst or 0) - t.data_ptr()) + tuple(getattr(d, n) for n, _ in L.PackDesc._fields_[2:]) for d, (s, t) in zip(arr, bases)]
+    assert got == want and cache.total_blocks == total
+    assert [e.desc.first_block for e in cache.entries.values()] == [r[12] for r in want]  # (the records carry what the table holds)
+    assert [p[2] for p in packs] == PACK_CALLS[prec] and [p[:2] for p in packs[:13]] == [(s.data_ptr(), t.data_ptr()) for s, t in bases[:13]]
+    capturing[0] = True  # a current table: the refresh inside a capture is the one table launch
+    cache.refresh()
+    assert multis == [(9, 63), (25, total)] and len(packs) == 16
+
+
+def test_pack_cache_refresh_inside_a_capture_and_the_refusals(monkeypatch):
+    packs, multis, capturing = _fake_pack_lib(monkeypatch)
+    cache, regs = T.PackCache(), []
+    for i, (shape, mode, kw) in enumerate(PACK_CASES[:3]):
+        w = torch.zeros(shape)
+        regs.append((w.data_ptr(), cache.get(("k%d" % i, mode), w, None, mode, "f32", **kw).w.data_ptr()))
+    capturing[0] = True  # registered, no table yet: one kpf_pack_conv_weight per operand, the registration's own arguments again
+    cache.refresh()
+    assert multis == [] and [p[2] for p in packs[3:]] == PACK_CALLS["f32"][:3] and [p[:2] for p in packs[3:]] == regs == [p[:2] for p in packs[:3]]
+    qkv, bqkv = [torch.zeros(128, 128) for _ in range(3)], [torch.zeros(128) for _ in range(3)]
+    with pytest.raises(AssertionError, match="eager iteration"):
+        cache.get_stacked(["q", "k", "v"], qkv, bqkv)
+    capturing[0] = False
+    cache.get_stacked(["q", "k", "v"], qkv, bqkv)
+    capturing[0] = True  # a stacked operand without a table: its column-range / bias-slot forms exist in the table launch only
+    with pytest.raises(RuntimeError, match="stacked operand was registered during a graph capture"):
+        cache.refresh()
+    params = [torch.zeros(4) for _ in range(2)]
+    with pytest.raises(AssertionError, match="run one eager iteration after moving / re-homing parameters"):
+        T.BertStack21.param_table(params)
+    capturing[0] = False
+    t = T.BertStack21.param_table(params)
+    capturing[0] = True
+    assert T.BertStack21.param_table(params) is t and t.tolist() == [p.data_ptr() for p in params]  # (a table that exists is found inside a capture)
+    del T.BertStack21._tables[tuple(t.tolist())]
+    del packs[:]
+    T._dw_taps(torch.zeros(200, 1, 7, 7), True)  # the un-cached depthwise tap table keeps its own row length (C, not C rounded up to 32)
+    assert packs[0][2] == (0, 0, 200, 1, 7, 7, 3, 200, 200)
+
+
+class _OnDevice(torch.Tensor):
+    """A host tensor that passes Conv2dNHWC.forward's device check (the GEMM itself is stubbed)."""
+    is_cuda = True
+
+
+class _Ctx:
+    """What a forward does to its autograd context: attribute writes plus the three calls, recorded."""
+
+    def __init__(self, needs):
+        self.needs_input_grad = needs
+
+    def save_for_backward(self, *ts):
+        self.saved_tensors = ts
+
+    def mark_non_differentiable(self, *ts):
+        pass
+
+    def set_materialize_grads(self, on):
+        pass
+
+
+def test_conv2d_nhwc_positions_come_from_the_signature_and_every_exit_records_what_backward_reads(monkeypatch):
+    Fn = T.Conv2dNHWC
+    assert tuple(inspect.signature(Fn.forward).parameters)[1:] == Fn.ARGS  # (an argument added to forward without moving ARGS fails here)
+    assert Fn._grads() == (None,) * 15
+    assert Fn._grads("dx", "dw", "db", "dres") == ("dx", "dw", "db") + (None,) * 7 + ("dres",) + (None,) * 4
+    assert Fn._grads(dx="a") == ("a",) + (None,) * 14 and Fn._grads("dx", "dw", "db") == ("dx", "dw", "db") + (None,) * 12
+    assert [Fn.ARGS.index(a) for a in ("x", "weight", "bias", "res")] == [0, 1, 2, 10]
+    # the fields backward reads, from its source; the three forward exits, run on host tensors with the lookup and the GEMM stubbed
+    reads = set(re.findall(r"\bctx\.(\w+)", inspect.getsource(Fn.backward) + inspect.getsource(Fn._backward))) - {"needs_input_grad"}
+    assert {"saved_tensors", "mma16", "alias", "gelu_out", "res_dtype", "odd", "pack", "groups", "conf", "w16", "x_dtype", "bias_ptr"} <= reads
+    assert "getattr(ctx" not in inspect.getsource(Fn.backward) + inspect.getsource(Fn._backward)
+    monkeypatch.setattr(T, "_operand", lambda cache, key, w, b, mode, prec, groups=1, **kw: Pack(ConvGeom.plain(w.shape[0], w.shape[1], 1, 1), w=torch.zeros(1)))
+    monkeypatch.setattr(T, "_conv_any", lambda pc, x4, prec, **kw: torch.zeros(x4.shape[0], 1, 1, pc.N))
+    monkeypatch.setattr(T, "pad_rows", lambda src, width, dtype=None: torch.zeros(src.shape[:-1] + (width,), dtype=dtype))
+    x = torch.zeros(6, 1, 1, 8).as_subclass(_OnDevice)
+    w, b, res = torch.zeros(16, 8, 1, 1), torch.zeros(16), torch.zeros(6, 1, 1, 16, dtype=torch.bfloat16)
+    exits = {"odd-width": (torch.zeros(6, 1, 1, 7).as_subclass(_OnDevice), torch.zeros(3, 7, 1, 1), None, 1, 0),
+             "gelu_out": (x, w, b, 1, 0, "f32", None, "k", None, 1, None, False, True, True),
+             "plain": (x, w, b, 1, 0, "f32", None, "k", None, 1, res, False, True, False)}
+    seen = {}
+    for name, args in exits.items():
+        ctx = _Ctx((True,) * 15)
+        with T.head_mma(5):
+            Fn.forward(ctx, *args)
+        assert reads <= set(vars(ctx)), (name, reads - set(vars(ctx)))
+        seen[name] = {k: v for k, v in vars(ctx).items() if k not in ("saved_tensors", "needs_input_grad")}
+    assert seen["odd-width"] == dict(mma16=5, groups=1, odd=(7, 8, 4), pack=(None, None), alias=False, gelu_out=False, res_dtype=None, w16=None, x_dtype=torch.float32,
+                                     conf=(1, 0, False, "f32"), bias_ptr=None)
+    assert seen["gelu_out"] == dict(mma16=5, groups=1, odd=None, pack=("k", None), alias=True, gelu_out=True, res_dtype=None, w16=None, x_dtype=torch.float32,
+                                    conf=(1, 0, True, "f32"), bias_ptr=b.data_ptr())
+    assert seen["plain"] == dict(seen["gelu_out"], gelu_out=False, res_dtype=torch.bfloat16)

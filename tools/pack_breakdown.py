@@ -23,12 +23,12 @@ def timed(sub):
     torch.cuda.synchronize(); t = time.perf_counter()
     for _ in range(20): cache.refresh()
     torch.cuda.synchronize()
-    el = sum(e["desc"][8] * e["desc"][9] for e in sub.values())
+    el = sum(e.desc.Kp * e.desc.rows for e in sub.values())
     return (time.perf_counter() - t) / 20 * 1e6, len(sub), el
-kinds = {"all": lambda d: True, "mode0 1x1": lambda d: d[6] == 0 and d[4] * d[5] == 1, "mode0 kxk": lambda d: d[6] == 0 and d[4] * d[5] > 1,
-         "mode1 1x1": lambda d: d[6] == 1 and d[4] * d[5] == 1, "mode1 kxk": lambda d: d[6] == 1 and d[4] * d[5] > 1, "mode2/3": lambda d: d[6] in (2, 3), "mode4": lambda d: d[6] == 4}
+kinds = {"all": lambda d: True, "mode0 1x1": lambda d: d.mode == 0 and d.KH * d.KW == 1, "mode0 kxk": lambda d: d.mode == 0 and d.KH * d.KW > 1,
+         "mode1 1x1": lambda d: d.mode == 1 and d.KH * d.KW == 1, "mode1 kxk": lambda d: d.mode == 1 and d.KH * d.KW > 1, "mode2/3": lambda d: d.mode in (2, 3), "mode4": lambda d: d.mode == 4}
 for name, f in kinds.items():
-    sub = {k: e for k, e in ents.items() if f(e["desc"])}
+    sub = {k: e for k, e in ents.items() if f(e.desc)}
     if sub:
         us, n, el = timed(sub)
         print("%-10s %4d operands %8.2f M elements  %7.1f us" % (name, n, el / 1e6, us))
