@@ -2,6 +2,10 @@
 restatement of the same op, and the backbone / full model against the oracle (oracle/kpf_oracle.py), which is itself
 pinned to the imported reference by tests/test_oracle_golden.py.  Nothing here reads /root/reference.
 
+The per-op convolution cases here (test_conv2d_matches_torch, test_conv2d_prologue_epilogues_and_slices, test_patchify_conv) are small enough that the
+implicit GEMM's cost model gives every one of them the 32 x 64 tile (64 x 64 at most): the other tile configurations of kpf_conv2d_f32 / kpf_conv2d_h16 are
+pinned in tests/test_igemm_tiles_gpu.py.
+
 Tolerances: per-op 1e-4 relative to the tensor's max magnitude (fp32 GEMMs with K up to 3072 in a different summation
 order); end-to-end 1e-3 relative as stated by BASELINE.json north_star, and |d joint| * cube/2 <= 0.05 mm.
 """

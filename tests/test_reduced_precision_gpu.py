@@ -18,10 +18,10 @@ import torch
 import torch.nn.functional as F
 
 from conftest import synthetic_sd
+from igemm_bounds import PREC, h16_excess
 from keypointfusion_amd.weights import synthetic_batch
 
 pytestmark = pytest.mark.gpu
-PREC = {"bf16": (torch.bfloat16, 2.0 ** -8), "f16": (torch.float16, 2.0 ** -11)}
 
 
 def _dev():
@@ -98,19 +98,13 @@ def test_conv2d_h16_is_the_fp32_conv_of_the_rounded_operands(case, prec):
         out = torch.empty(B, N, OH, OW, device=dev)
         conv16(p16, xa, kdt, out_nchw=out, flags=flags)
         got = out.cpu().double()
-        tol = 2e-6  # fp32 output: only the accumulation order differs
     else:
         o = conv16(p16, xa, kdt, flags=flags, **kw)
         got = o.buf.view(B, OH, OW, N).permute(0, 3, 1, 2).float().cpu().double()
-        tol = 1.01 * eps
-    if kind == "gelu":
-        # 16-bit outputs use the 9-operation GELU (csrc/kpf_conv.hip gelu_h16): |error| <= 2.6e-5 ABSOLUTE (what reaches pwconv2's sums), on top of
-        # the output rounding — bounded as an absolute term, not against the 1e-3-of-range floor of the other epilogues
-        bad = (got - ref).abs() - (1.3 * tol * ref.abs() + 3.5e-5)
-        assert float(bad.max()) <= 0, (case, prec, float(bad.max()))
-        return
-    err = float(((got - ref).abs() / (ref.abs() + ref.abs().max() * 1e-3)).max()) if kind != "nchw" else rel(got, ref)
-    assert err < 2.5 * tol + 1e-6, (case, prec, err)  # elementwise relative (floor at 1e-3 of the range): output rounding only
+    # the bounds live in tests/igemm_bounds.py (shared with test_igemm_tiles_gpu.py): the 9-operation GELU's absolute term on top of the output rounding for
+    # "gelu", the accumulation order alone for the fp32 NCHW output, output rounding (elementwise relative, floor at 1e-3 of the range) for the rest
+    excess, bound = h16_excess(got, ref, eps, kind if kind in ("gelu", "nchw") else "rounding")
+    assert excess <= 0 if bound == "gelu" else excess < 0, (case, prec, bound, excess)
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
