@@ -747,12 +747,43 @@ int kpf_prep_set_stamps(void* stamps64 /* tuning aid: [B][8] device uint64 slots
                                             kpf_prep_crop_u16 0 start, 1 geometry, 2 gather, 3 end; kpf_prep_pcl_sample 4 start, 5 compacted, 6 sorted, 7 end;
                                             NULL = off.  Synchronises with the device: not for captured code */);
 
+/* Device-resident evaluation (ABI 20): the per-batch figures of the reference's test loop (train.py:326-399, :470-488; util/generateFeature.py:676-703;
+ * util/eval_utils.py:38-81) accumulated in device memory.  Every argument but `stages` is a device buffer, no entry synchronises or allocates, and the
+ * arithmetic order below is part of the interface: results do not depend on B, on the grid or on a graph replay.
+ *
+ * kpf_eval_errors_f32: stages = HOST array of S <= 8 device pointers, each the normalised joints [B][J][3] float of one stage (read at the call: the pointers
+ * travel to the kernel by value); gt [B][J][3] float, cube [B][3] float (mm); score_index NULL (Jsel == J) or Jsel int joint indices in [0, J) (NYU: 14 of 23).
+ * One wave64 per (sample, stage), one lane per joint, J <= 64; all arithmetic in double from the float inputs, no contraction:
+ *   plain:   e_j = sqrt(dx^2 + dy^2 + dz^2), d = (p_j - g_j) * (cube / 2), summed left to right, rounded ONCE to float (the crop centre cancels and is not added);
+ *   aligned: the same formula after the Umeyama similarity alignment of p onto g over ALL J joints (selection comes after the alignment, as in the
+ *            reference): centroids = sum / J, H = A0^T B0 / J, var = |A0|^2 / J, 3 x 3 SVD of H by 8 sweeps of cyclic Jacobi on H^T H (pairs (0,1), (0,2),
+ *            (1,2)), V = its eigenvectors by descending eigenvalue with v3 = v1 x v2, u1 = H v1 / |H v1|, u2 = H v2 orthogonalised against u1 and normalised,
+ *            u3 = u1 x u2, third singular value SIGNED s3 = u3^T H v3 (negative = the reflection branch d = -1), R = V U^T, scale = (s1 + s2 + s3) / var,
+ *            aligned_j = scale * R a0_j + centroid(g).
+ *   Every cross-lane sum is the 64-lane xor butterfly (offsets 32, 16, .. 1) with lanes >= J holding +0.0.
+ * -> err [2][S][B][Jsel] float: plain, then aligned.  When every predicted joint of a sample is the same point, var and H are 0 and that sample's ALIGNED
+ * errors are NaN (0 / 0, as in the reference); its plain errors and every other sample are unaffected.  A rank-deficient H with var > 0 gives finite results. */
+int kpf_eval_errors_f32(const float* const* stages, int S, const float* gt, const float* cube, const int* score_index, int B, int J, int Jsel, float* err,
+                        void* stream);
+
+/* kpf_eval_accumulate: err of the call above; valid NULL or [B] bytes (0 drops a sample: the padding of a last partial batch at fixed B); thresholds [T]
+ * double (np.linspace on the host, so that they carry numpy's bits).  One workgroup per stage, every output element owned by one thread, no atomics:
+ *   n_samples [1] += valid samples; n_batches [1] += 1 unless no sample is valid (then nothing at all is added)          (64-bit integers)
+ *   sum_err, sum_pa [S][Jsel] double: the running sum continued sequentially, x = x + (double)err[b][j] for the valid b = 0 .. B-1 in order
+ *   sum_batch_mean, sum_batch_pa_mean [S] double += (sequential sum from 0.0 over valid b = 0 .. B-1, j = 0 .. Jsel-1 inner) / (valid * Jsel): the batch
+ *       means the reference averages (error_list / PA_error_list, train.py:381-397)
+ *   pck, pck_pa [S][Jsel][T] 64-bit integers += number of valid b with (double)err[b][j] <= thresholds[t] (numpy's comparison on the logged float; NaN never counts)
+ * 2 * B * Jsel * 4 + B bytes of LDS must fit 64 KiB. */
+int kpf_eval_accumulate(const float* err, const unsigned char* valid, const double* thresholds, int S, int B, int Jsel, int T, long long* n_samples,
+                        long long* n_batches, double* sum_err, double* sum_pa, double* sum_batch_mean, double* sum_batch_pa_mean, long long* pck,
+                        long long* pck_pa, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 19
+#define KPF_ABI_VERSION 20
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

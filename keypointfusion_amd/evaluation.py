@@ -112,19 +112,35 @@ def _trapz(y, x):
     return float(np.sum((y[1:] + y[:-1]) * (x[1:] - x[:-1]) / 2.0))
 
 
+def _pck_measures(curves, th):
+    """util/eval_utils.py:60-81 on the per-joint PCK curves: (mean of the per-joint AUCs, mean curve, thresholds, AUC of the mean curve from threshold
+    index 8 on with thresholds * 1000)."""
+    norm = _trapz(np.ones_like(th), th)
+    aucs = [_trapz(c, th) / norm for c in curves]
+    curve = np.mean(np.array(curves), 0)
+    x = th[8:] * 1000.0
+    sub = _trapz(curve[8:], x) / _trapz(np.ones_like(x), x)
+    return float(np.mean(aucs)), curve, th, float(sub)
+
+
 def pck_auc(per_joint_errors, val_min=0.0, val_max=50.0, steps=20):
     """util/eval_utils.py:38-81 (get_measures / _get_pck / calc_auc), as eval_auc calls it (thresholds 0..50 in 20 steps):
     per_joint_errors = list of 21 sequences of errors.  Returns (auc, pck_curve, thresholds, auc_20_50) where auc_20_50 is the
     reference's "Area under curve between 20mm - 50mm" (curve from threshold index 8 on, thresholds * 1000)."""
     th = np.linspace(val_min, val_max, steps)
-    norm = _trapz(np.ones_like(th), th)
-    aucs, curves = [], []
+    curves = []
     for j in range(len(per_joint_errors)):
         d = np.asarray(per_joint_errors[j], dtype=np.float64)
-        curve = np.array([np.mean((d <= t).astype(float)) for t in th])
-        curves.append(curve)
-        aucs.append(_trapz(curve, th) / norm)
-    curve = np.mean(np.array(curves), 0)
-    x = th[8:] * 1000.0
-    sub = _trapz(curve[8:], x) / _trapz(np.ones_like(x), x)
-    return float(np.mean(aucs)), curve, th, float(sub)
+        curves.append(np.array([np.mean((d <= t).astype(float)) for t in th]))
+    return _pck_measures(curves, th)
+
+
+def pck_auc_from_counts(counts, n, thresholds):
+    """pck_auc from threshold hit counts instead of error lists: counts [J][T] = number of the n errors of joint j that are <= thresholds[t]
+    (`evaluation_gpu.DeviceEvaluator` keeps them on the device).  The mean of a 0 / 1 vector is exactly count / n, so the result equals pck_auc on the
+    errors themselves.  thresholds: the np.linspace(val_min, val_max, steps) the counts were taken against."""
+    th = np.asarray(thresholds, dtype=np.float64)
+    counts = np.asarray(counts)
+    if counts.ndim != 2 or counts.shape[1] != th.shape[0]:
+        raise ValueError("pck_auc_from_counts: counts must be [J][%d] (got %s)" % (th.shape[0], counts.shape))
+    return _pck_measures([counts[j].astype(np.float64) / float(n) for j in range(counts.shape[0])], th)

@@ -100,8 +100,9 @@ class PipelinedEval:
     def submit_frames(self, preprocessor, rgb, depth, bbox, cam, seed, loader=None, origin=None, frame_size=None, kernel=0.8):
         """Frames and boxes in: `preprocess_gpu.DevicePreprocessor.prepare` on the slot's stream in front of the slot's graph(s), then submit().  `preprocessor`
         gives the crop size, sample count and cube; every slot works on its own copy of it (own output buffers: `depth` batches are in flight).  Returns
-        (ticket for collect(), prep): prep holds this batch's center, M, cube and cam_para (copies, ordered like the results: valid after collect(ticket)) for
-        `preprocessor.uncrop(results[5], prep)`."""
+        (ticket for collect(), prep): prep holds this batch's img, center, M, cube and cam_para (copies, ordered like the results: valid after collect(ticket))
+        for `preprocessor.uncrop(results[5], prep)` and `evaluation_gpu.DeviceEvaluator.update(results, prep["img"], xyz_gt, prep["center"], ...)` (the dense
+        stages are decoded with the depth crop)."""
         from .preprocess_gpu import DevicePreprocessor
         DevicePreprocessor.check_inputs(rgb, depth, bbox, cam, seed, origin, frame_size)
         dev = depth.device
@@ -119,7 +120,7 @@ class PipelinedEval:
             for t in (rgb, depth, bbox, cam, seed):
                 t.record_stream(st)
             prep = self._preps[1][slot].prepare(rgb, depth, bbox, cam, seed, origin, frame_size)
-            keep = {k: prep[k].clone() for k in ("center", "M", "cube", "cam_para")}
+            keep = {k: prep[k].clone() for k in ("img", "center", "M", "cube", "cam_para")}
             for t in keep.values():
                 t.record_stream(cur)  # allocated on the slot's stream, consumed on the caller's
             ticket = self.submit(prep["img_rgb"], prep["img"], prep["pcl"], loader, prep["center"], prep["M"], prep["cube"], prep["cam_para"], kernel)
