@@ -778,12 +778,39 @@ int kpf_eval_accumulate(const float* err, const unsigned char* valid, const doub
                         long long* n_batches, double* sum_err, double* sum_pa, double* sum_batch_mean, double* sum_batch_pa_mean, long long* pck,
                         long long* pck_pa, void* stream);
 
+/* Several tracks on one stored frame (ABI 21): kpf_prep_crop_u16 with a frame index.  rgb [F][Hs][Ws][3], depth [F][Hs][Ws]; frame_index [B] int (device):
+ * sample b reads stored frame frame_index[b].  The caller keeps the values in [0, F) (preprocess_gpu.make_frame_index refuses others on the host); the kernel
+ * clamps them as well, so that no index reads out of bounds.  Everything else, and every result, as kpf_prep_crop_u16 — which is this kernel without an index
+ * (sample b reads frame b). */
+int kpf_prep_crop_u16_indexed(const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const double* bbox, const double* cam,
+                              const double* cube, int B, int Hs, int Ws, int x0, int y0, int H, int W, int S, float* img, float* img_rgb, float* center, float* M,
+                              float* cube_out, float* cam_para, double* com, int* bounds, double* M64, void* stream);
+
+/* Tracking step (ABI 21): ONE launch behind the forward that takes the place of kpf_prep_uncrop_f32 in a tracked video stream and leaves the NEXT frame's box in
+ * device memory (keypointfusion_amd/tracking.py).  joints [B][J][3] float normalised to the cube; center, M, cube, cam_para: the float outputs of
+ * kpf_prep_crop_u16; pcl_count [B] int of kpf_prep_pcl_sample.  One wave64 per sample, one lane per joint, J <= 64; grid = B; no allocation, no
+ * synchronisation, no atomics; contraction off.
+ *   crop_px, frame_px [B][J][3]: the expressions and the bits of kpf_prep_uncrop_f32.   cam_mm [B][J][3] = ((j * cube) / 2) + center in float, each step rounded
+ *   (camera space, mm: demo_RGBD.py:133).   bbox_used [B][4] double: a copy of the box this frame was cropped with.
+ *   Box rule = the reference loader's get_bbox + process_bbox (dataloader/loader.py:1250-1251, :1432-1480), restated by tracking.next_bbox: min / max of the
+ *   STORED float frame_px u and v by xor butterflies (lanes >= J hold +-inf), then in FLOAT, every operation rounded: c = (lo + hi) / 2, w = (hi - lo) * expansion,
+ *   x0 = c - 0.5 w, x1 = c + 0.5 w, bx = x0, bw = x1 - x0 (the same for y); then in DOUBLE: X1 = max(0, bx), Y1 = max(0, by), X2 = min(frame_w - 1, X1 +
+ *   max(0, bw - 1)), Y2 likewise; no box unless bw * bh > 0 and X2 >= X1 and Y2 >= Y1; w = X2 - X1, h = Y2 - Y1, centre = X1 + w / 2, Y1 + h / 2, the shorter
+ *   side raised to the longer, box = (cx - w / 2, cy - h / 2, w, h).
+ *   status [B] int, bits: 1 the rule gave no box; 2 pcl_count[b] == 0 (the crop had no foreground: the prediction means nothing); 4 a frame_px u or v is not
+ *   finite (the rule is not evaluated).
+ * State, updated in place: bbox [B][4] double — in: this frame's box, out: the next frame's (status 0) or unchanged (status != 0); lost [B] int = 0 (status 0) or
+ * + 1; seed [B] 64-bit += seed_stride.  A sample's outputs do not depend on B, on its position in the batch or on a graph replay. */
+int kpf_track_step_f32(const float* joints, const float* center, const float* M, const float* cube, const float* cam_para, const int* pcl_count, int B, int J,
+                       int frame_w, int frame_h, float expansion, long long seed_stride, double* bbox, long long* seed, int* lost, float* crop_px,
+                       float* frame_px, float* cam_mm, double* bbox_used, int* status, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 20
+#define KPF_ABI_VERSION 21
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

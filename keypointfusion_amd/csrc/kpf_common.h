@@ -68,6 +68,33 @@ __host__ __device__ __forceinline__ unsigned hash32(unsigned x) {
   return x;
 }
 
+// preprocess.project_to_crop + uncrop_points for ONE joint (j: 3 floats normalised to the cube; center, M, cube, cam: the sample's float32 parameters), double
+// inside, contraction off (the host rounds every product and sum).  The one definition behind kpf_prep_uncrop_f32 and kpf_track_step_f32: their crop and
+// frame pixels are the same bits.
+__device__ __forceinline__ void kpf_uncrop_joint(const float* __restrict__ j, const float* __restrict__ center, const float* __restrict__ M,
+                                                 const float* __restrict__ cube, const float* __restrict__ cam, float* crop3, float* frame3) {
+#pragma clang fp contract(off)
+  double m[9];
+  for (int k = 0; k < 9; ++k) m[k] = (double)M[k];
+  const double x = (double)j[0] * ((double)cube[0] / 2.0) + (double)center[0];
+  const double y = (double)j[1] * ((double)cube[1] / 2.0) + (double)center[1];
+  const double z = (double)j[2] * ((double)cube[2] / 2.0) + (double)center[2];
+  const double u = x * (double)cam[0] / z + (double)cam[2], v = y * (double)cam[1] / z + (double)cam[3];
+  const double cu = u * m[0] + v * m[1] + m[2], cv = u * m[3] + v * m[4] + m[5];
+  crop3[0] = (float)cu;
+  crop3[1] = (float)cv;
+  crop3[2] = (float)z;
+  // M^-1 by cofactors (the host takes LAPACK's inverse: a few 1e-16 relative apart on these affine matrices)
+  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[2] * m[7] - m[1] * m[8], c02 = m[1] * m[5] - m[2] * m[4];
+  const double c10 = m[5] * m[6] - m[3] * m[8], c11 = m[0] * m[8] - m[2] * m[6], c12 = m[2] * m[3] - m[0] * m[5];
+  const double c20 = m[3] * m[7] - m[4] * m[6], c21 = m[1] * m[6] - m[0] * m[7], c22 = m[0] * m[4] - m[1] * m[3];
+  const double det = m[0] * c00 + m[1] * c10 + m[2] * c20;
+  const double h0 = (cu * c00 + cv * c01 + c02) / det, h1 = (cu * c10 + cv * c11 + c12) / det, h2 = (cu * c20 + cv * c21 + c22) / det;
+  frame3[0] = (float)(h0 / h2);
+  frame3[1] = (float)(h1 / h2);
+  frame3[2] = (float)z;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // "Split" operand format for the 3 x f16 MFMA path (kpf_conv.hip): a row of C fp32 values (C % 32 == 0) occupies the same
 // C*4 bytes as C/32 blocks of [32 x f16 hi | 32 x f16 lo] with x ~= hi + lo (22 significant bits; |x| is clamped to the

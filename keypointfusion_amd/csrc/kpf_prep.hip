@@ -3,6 +3,7 @@
 //
 //   kpf_prep_crop_u16    box -> centre of mass (exact 64-bit integer sums, finished by one lane in double) -> metric bounds -> nearest-neighbour crop with
 //                        zero padding -> z-clamp -> normalised depth image and RGB crop, plus center / M / cube / cam_para
+//                        (kpf_prep_crop_u16_indexed: the same kernel, sample b reading stored frame frame_index[b] — several tracks on one frame)
 //   kpf_prep_pcl_sample  foreground pixels of the normalised crop -> candidate points in np.where order -> n of them without replacement IN RANDOM ORDER:
 //                        (hash key, candidate) pairs sorted by a bitonic network in LDS (only those under a threshold that about 1.5 n pass), the first n taken
 //   kpf_prep_uncrop_f32  normalised joints -> crop pixels -> frame pixels
@@ -174,7 +175,7 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 }
 
 __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
-                                                            const double* __restrict__ bbox, const double* __restrict__ cam, const double* __restrict__ cube,
+                                                            const int* __restrict__ frame_index, int F, const double* __restrict__ bbox, const double* __restrict__ cam, const double* __restrict__ cube,
                                                             int Hs, int Ws, int ox, int oy, int H, int W, int S, float* __restrict__ img,
                                                             float* __restrict__ img_rgb, float* __restrict__ center, float* __restrict__ M,
                                                             float* __restrict__ cube_out, float* __restrict__ cam_out, double* __restrict__ com,
@@ -186,8 +187,10 @@ __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char*
   unsigned short* crop = reinterpret_cast<unsigned short*>(smem + 4 * PREP_NW * 8 + 256 + PREP_NW * 4);  // [S * S]
   static_assert(sizeof(PrepGeom) <= 256, "PrepGeom outgrew its LDS slot");
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const unsigned short* dep = depth + (size_t)b * Hs * Ws;
-  const unsigned char* col = rgb + (size_t)b * Hs * Ws * 3;
+  // stored frame of this sample: b itself, or frame_index[b] of F (several tracks on one frame), clamped so that no index reads out of bounds
+  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
+  const unsigned short* dep = depth + (size_t)f * Hs * Ws;
+  const unsigned char* col = rgb + (size_t)f * Hs * Ws * 3;
   const double* bb = bbox + 4 * b;
 
   // 1. centre of mass over the box: pixels outside the stored window read as 0, which is invalid depth, so only the intersection is visited
@@ -444,32 +447,14 @@ __global__ __launch_bounds__(PREP_NT) void prep_pcl_kernel(const float* __restri
   PREP_STAMP(7);
 }
 
-// project_to_crop + uncrop_points, one thread per joint, double inside
+// project_to_crop + uncrop_points, one thread per joint, double inside (kpf_uncrop_joint of kpf_common.h, shared with kpf_track.hip)
 __global__ __launch_bounds__(256) void prep_uncrop_kernel(const float* __restrict__ joints, const float* __restrict__ center, const float* __restrict__ M,
                                                           const float* __restrict__ cube, const float* __restrict__ cam, int B, int J, float* __restrict__ crop_px,
                                                           float* __restrict__ frame_px) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= B * J) return;
   const int b = e / J;
-  double m[9];
-  for (int k = 0; k < 9; ++k) m[k] = (double)M[9 * b + k];
-  const double x = (double)joints[3 * e] * ((double)cube[3 * b] / 2.0) + (double)center[3 * b];
-  const double y = (double)joints[3 * e + 1] * ((double)cube[3 * b + 1] / 2.0) + (double)center[3 * b + 1];
-  const double z = (double)joints[3 * e + 2] * ((double)cube[3 * b + 2] / 2.0) + (double)center[3 * b + 2];
-  const double u = x * (double)cam[4 * b] / z + (double)cam[4 * b + 2], v = y * (double)cam[4 * b + 1] / z + (double)cam[4 * b + 3];
-  const double cu = u * m[0] + v * m[1] + m[2], cv = u * m[3] + v * m[4] + m[5];
-  crop_px[3 * e] = (float)cu;
-  crop_px[3 * e + 1] = (float)cv;
-  crop_px[3 * e + 2] = (float)z;
-  // M^-1 by cofactors (the host takes LAPACK's inverse: a few 1e-16 relative apart on these affine matrices)
-  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[2] * m[7] - m[1] * m[8], c02 = m[1] * m[5] - m[2] * m[4];
-  const double c10 = m[5] * m[6] - m[3] * m[8], c11 = m[0] * m[8] - m[2] * m[6], c12 = m[2] * m[3] - m[0] * m[5];
-  const double c20 = m[3] * m[7] - m[4] * m[6], c21 = m[1] * m[6] - m[0] * m[7], c22 = m[0] * m[4] - m[1] * m[3];
-  const double det = m[0] * c00 + m[1] * c10 + m[2] * c20;
-  const double h0 = (cu * c00 + cv * c01 + c02) / det, h1 = (cu * c10 + cv * c11 + c12) / det, h2 = (cu * c20 + cv * c21 + c22) / det;
-  frame_px[3 * e] = (float)(h0 / h2);
-  frame_px[3 * e + 1] = (float)(h1 / h2);
-  frame_px[3 * e + 2] = (float)z;
+  kpf_uncrop_joint(joints + 3 * e, center + 3 * b, M + 9 * b, cube + 3 * b, cam + 4 * b, crop_px + 3 * e, frame_px + 3 * e);
 }
 #endif  // __HIPCC__
 
@@ -484,19 +469,36 @@ inline int host_pow2ceil(int v) {
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// the one launch behind kpf_prep_crop_u16 (frame_index NULL, F = B: sample b reads frame b) and kpf_prep_crop_u16_indexed
+static int prep_crop_launch(const char* name, const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const double* bbox,
+                            const double* cam, const double* cube, int B, int Hs, int Ws, int x0, int y0, int H, int W, int S, float* img, float* img_rgb,
+                            float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds, double* M64, void* stream) {
+  KPF_REQUIRE(rgb && depth && bbox && cam && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64, "%s: null pointer argument", name);
+  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
+  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
+  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
+  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
+  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
+  const size_t lds = kCropFixedLds + (size_t)S * S * 2;
+  hipLaunchKernelGGL(prep_crop_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, frame_index, F, bbox, cam, cube, Hs, Ws, x0, y0, H, W, S, img, img_rgb,
+                     center, M, cube_out, cam_para, com, bounds, M64);
+  return kpf_check_launch(name);
+}
+
 extern "C" int kpf_prep_crop_u16(const unsigned char* rgb, const unsigned short* depth, const double* bbox, const double* cam, const double* cube, int B,
                                  int Hs, int Ws, int x0, int y0, int H, int W, int S, float* img, float* img_rgb, float* center, float* M, float* cube_out,
                                  float* cam_para, double* com, int* bounds, double* M64, void* stream) {
-  KPF_REQUIRE(rgb && depth && bbox && cam && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64,
-              "kpf_prep_crop_u16: null pointer argument");
-  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "kpf_prep_crop_u16: bad shape (B %d, window %d x %d, frame %d x %d)", B, Hs, Ws, H, W);
-  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "kpf_prep_crop_u16: the %d x %d window at (%d, %d) leaves the %d x %d frame", Ws, Hs, x0, y0, W, H);
-  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "kpf_prep_crop_u16: window of %d x %d pixels is too large", Hs, Ws);
-  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "kpf_prep_crop_u16: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", S, PREP_MAX_PIX);
-  const size_t lds = kCropFixedLds + (size_t)S * S * 2;
-  hipLaunchKernelGGL(prep_crop_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, bbox, cam, cube, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M,
-                     cube_out, cam_para, com, bounds, M64);
-  return kpf_check_launch("kpf_prep_crop_u16");
+  return prep_crop_launch("kpf_prep_crop_u16", rgb, depth, nullptr, B, bbox, cam, cube, B, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para,
+                          com, bounds, M64, stream);
+}
+
+extern "C" int kpf_prep_crop_u16_indexed(const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const double* bbox,
+                                         const double* cam, const double* cube, int B, int Hs, int Ws, int x0, int y0, int H, int W, int S, float* img,
+                                         float* img_rgb, float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds, double* M64,
+                                         void* stream) {
+  KPF_REQUIRE(frame_index, "kpf_prep_crop_u16_indexed: null frame index (kpf_prep_crop_u16 is the entry without one)");
+  return prep_crop_launch("kpf_prep_crop_u16_indexed", rgb, depth, frame_index, F, bbox, cam, cube, B, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M, cube_out,
+                          cam_para, com, bounds, M64, stream);
 }
 
 extern "C" int kpf_prep_pcl_sample(const float* img, const float* center, const double* M64, const double* cube, const double* cam, const long long* seed,

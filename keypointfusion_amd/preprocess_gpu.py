@@ -26,6 +26,28 @@ def _pow2ceil(v):
     return 1 << max(int(v) - 1, 0).bit_length()
 
 
+def _named(rgb, depth, bbox, cam, seed, frame_index):
+    named = (("rgb", rgb), ("depth", depth), ("bbox", bbox), ("cam", cam), ("seed", seed))
+    return named if frame_index is None else named + (("frame_index", frame_index),)
+
+
+def make_frame_index(indices, frames, device):
+    """[B] int32 device tensor for prepare(..., frame_index=): track b reads stored frame indices[b] of `frames`.  The values are checked HERE, on the host
+    list, before anything reaches a device (the kernel clamps as well, but a wrong index is a caller's bug, not a frame to crop)."""
+    try:
+        idx = [int(v) for v in indices]
+        exact = all(v == i for v, i in zip(indices, idx))
+    except (TypeError, ValueError):
+        idx, exact = [], False
+    if isinstance(indices, torch.Tensor) or not exact or not idx:
+        raise TypeError("make_frame_index: indices must be a non-empty host sequence of integers (got %r)" % (indices,))
+    frames = int(frames)
+    bad = [v for v in idx if not 0 <= v < frames]
+    if bad:
+        raise ValueError("make_frame_index: frame index %d outside [0, %d)" % (bad[0], frames))
+    return torch.tensor(idx, dtype=torch.int32, device=device)
+
+
 class DevicePreprocessor:
     def __init__(self, img_size=128, sample_num=1024, cube=(250.0, 250.0, 250.0), debug_candidates=False):
         """debug_candidates: prepare() also returns `candidates` [B][img_size**2][3], every foreground point at its candidate index (rows >= pcl_count
@@ -45,9 +67,10 @@ class DevicePreprocessor:
 
     # -- argument checks: nothing here touches a device
     @staticmethod
-    def check_inputs(rgb, depth, bbox, cam, seed, origin=None, frame_size=None):
-        """Validates one batch and returns (B, Hs, Ws, x0, y0, H, W).  Raises TypeError / ValueError with the reason."""
-        for name, t in (("rgb", rgb), ("depth", depth), ("bbox", bbox), ("cam", cam), ("seed", seed)):
+    def check_inputs(rgb, depth, bbox, cam, seed, origin=None, frame_size=None, frame_index=None):
+        """Validates one batch and returns (B, Hs, Ws, x0, y0, H, W).  Raises TypeError / ValueError with the reason.  frame_index ([B] int32, from
+        make_frame_index): rgb and depth hold F stored frames and B, the number of samples, is the length of the index."""
+        for name, t in _named(rgb, depth, bbox, cam, seed, frame_index):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("DevicePreprocessor.prepare: %s must be a torch tensor on the GPU (got %s)" % (name, type(t).__name__))
         if depth.dtype != torch.uint16:
@@ -57,11 +80,18 @@ class DevicePreprocessor:
             raise TypeError("DevicePreprocessor.prepare: rgb must be torch.uint8 (got %s)" % rgb.dtype)
         if depth.dim() != 3:
             raise ValueError("DevicePreprocessor.prepare: depth must be [B][Hs][Ws] (got %s)" % (tuple(depth.shape),))
-        B, Hs, Ws = (int(v) for v in depth.shape)
-        if B < 1 or Hs < 1 or Ws < 1:
+        F, Hs, Ws = (int(v) for v in depth.shape)
+        if F < 1 or Hs < 1 or Ws < 1:
             raise ValueError("DevicePreprocessor.prepare: empty depth %s" % (tuple(depth.shape),))
-        if tuple(rgb.shape) != (B, Hs, Ws, 3):
+        if tuple(rgb.shape) != (F, Hs, Ws, 3):
             raise ValueError("DevicePreprocessor.prepare: rgb %s does not match depth %s (expected [B][Hs][Ws][3])" % (tuple(rgb.shape), tuple(depth.shape)))
+        B = F
+        if frame_index is not None:
+            if frame_index.dtype != torch.int32:
+                raise TypeError("DevicePreprocessor.prepare: frame_index must be torch.int32 (got %s): build it with make_frame_index" % frame_index.dtype)
+            if frame_index.dim() != 1 or frame_index.shape[0] < 1:
+                raise ValueError("DevicePreprocessor.prepare: frame_index has shape %s, expected [B]" % (tuple(frame_index.shape),))
+            B = int(frame_index.shape[0])
         for name, t, shape, dt in (("bbox", bbox, (B, 4), torch.float64), ("cam", cam, (B, 4), torch.float64), ("seed", seed, (B,), torch.int64)):
             if tuple(t.shape) != shape:
                 raise ValueError("DevicePreprocessor.prepare: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
@@ -92,15 +122,17 @@ class DevicePreprocessor:
             self._bufs[key] = b
         return b
 
-    def prepare(self, rgb, depth, bbox, cam, seed, origin=None, frame_size=None):
+    def prepare(self, rgb, depth, bbox, cam, seed, origin=None, frame_size=None, frame_index=None):
         """rgb [B][Hs][Ws][3] uint8, depth [B][Hs][Ws] uint16 (mm), bbox [B][4] float64 (x, y, w, h; x, y the top-left corner), cam [B][4] float64
         (fx, fy, u0, v0), seed [B] int64: contiguous tensors on one GPU.  Returns a dict of device tensors: the keys of preprocess.prepare_rgbd that the
         model consumes (MODEL_INPUTS, batched) plus pcl_index [B][n] (candidate index of every sample, -1 for an empty cloud), pcl_count [B], com [B][3]
         float64, bounds [B][6] int32 (xs, xe, ys, ye, resize width, resize height) and M64 (M before its rounding to float32).  The tensors are this
-        object's buffers for (B, Hs, Ws): the next prepare() of the same shape overwrites them."""
-        B, Hs, Ws, x0, y0, H, W = self.check_inputs(rgb, depth, bbox, cam, seed, origin, frame_size)
+        object's buffers for (B, Hs, Ws): the next prepare() of the same shape overwrites them.
+        frame_index ([B] int32 device tensor of make_frame_index): several samples on one stored frame — rgb and depth are [F][Hs][Ws]..., sample b reads
+        frame frame_index[b], and bbox, cam and seed stay [B].  Without it sample b reads frame b."""
+        B, Hs, Ws, x0, y0, H, W = self.check_inputs(rgb, depth, bbox, cam, seed, origin, frame_size, frame_index)
         dev = depth.device
-        for name, t in (("rgb", rgb), ("depth", depth), ("bbox", bbox), ("cam", cam), ("seed", seed)):
+        for name, t in _named(rgb, depth, bbox, cam, seed, frame_index):
             if t.device.type != "cuda" or t.device != dev:
                 raise RuntimeError("DevicePreprocessor.prepare: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
                                    "preprocess.prepare_rgbd is the host path)" % (name, t.device))
@@ -111,9 +143,14 @@ class DevicePreprocessor:
         S, n = self.img_size, self.sample_num
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            lib.check(l.kpf_prep_crop_u16(rgb.data_ptr(), depth.data_ptr(), bbox.data_ptr(), cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, S,
-                                          o["img"].data_ptr(), o["img_rgb"].data_ptr(), o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(),
-                                          o["cam_para"].data_ptr(), o["com"].data_ptr(), o["bounds"].data_ptr(), o["M64"].data_ptr(), st), "kpf_prep_crop_u16")
+            outs = (o["img"].data_ptr(), o["img_rgb"].data_ptr(), o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(), o["cam_para"].data_ptr(),
+                    o["com"].data_ptr(), o["bounds"].data_ptr(), o["M64"].data_ptr(), st)
+            if frame_index is None:
+                lib.check(l.kpf_prep_crop_u16(rgb.data_ptr(), depth.data_ptr(), bbox.data_ptr(), cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, S,
+                                              *outs), "kpf_prep_crop_u16")
+            else:
+                lib.check(l.kpf_prep_crop_u16_indexed(rgb.data_ptr(), depth.data_ptr(), frame_index.data_ptr(), int(depth.shape[0]), bbox.data_ptr(),
+                                                      cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, S, *outs), "kpf_prep_crop_u16_indexed")
             cand = o["candidates"].data_ptr() if self.debug_candidates else None
             lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["_cube64"].data_ptr(), cam.data_ptr(),
                                             seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
