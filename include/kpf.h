@@ -368,6 +368,34 @@ int kpf_conv2d_wgrad(const void* dy, const void* x, int dtype, float* dw, float*
                      int ldx, int OH, int OW, int N, int ldy, int KH, int KW, int sh, int sw, int ph, int pw, int cin_valid, int n_valid,
                      kpf_wgrad_reduce_desc* reduce /* nullable */, void* stream);
 int kpf_wgrad_reduce_multi(const kpf_wgrad_reduce_desc* descs, int n, void* stream);
+/* Which kernel kpf_conv2d_wgrad gives a call, and a switch to pin it (ABI 22; tests and tuning: the tile shapes otherwise follow from cost models over M, N, K).
+ * kpf_conv2d_wgrad_plan asks the dispatcher's own selection function — with what it decides from: dtype (any of kpf_conv2d_wgrad's), groups, M = B*OH*OW, N,
+ * K = KH*KW*Cin, is_1x1 (KH == KW == 1), trimmed (cin_valid < Cin or n_valid < N) — and makes no device call.  family: _F32 wgrad_f32_kernel<vn, vk> (output
+ * tile 32 vn x 32 vk; also the widening form of 16-bit operands, KPF_WGRAD_H16_WIDEN=1), _R16 wgrad_r16_kernel (KPF_DT_F32_MMA_* on the 64 x 64 tile; on any other
+ * tile the fp32 products: _F32), _DIRECT the 64 x 64 fp32 tile unsplit over the <= 128 rows of a 1x1, _H16S / _H16 the 64- / 128-tile kernels of 16-bit operands.
+ * S splits of sps stages each (32 pixels a stage, 128 in _H16S); writes_dw: an unsplit untrimmed 1x1 — the kernel writes dw / db itself, ws is not touched and a
+ * descriptor comes back with kind < 0; ws_floats: what ONE group needs (kpf_conv2d_wgrad accepts groups * ws_floats; kpf_conv2d_wgrad_ws_floats is the bound
+ * over every dtype and kernel size, forced tile included).
+ * kpf_conv2d_wgrad_force_form: process-wide, 0 = the cost models (the default).  KPF_WGRAD_FORM_F32_* pins the tile of every call the fp32-MFMA kernels take and
+ * switches the _DIRECT shortcut off; KPF_WGRAD_FORM_H16S / _H16 pins the kernel of every call with 16-bit operands, over the few-pixels rule and KPF_WG16_FORM
+ * (_H16 with the split of its own plan).  A value of the other family leaves a call to the rules.  Not meant to change while calls are being issued. */
+#define KPF_WGRAD_FAMILY_F32 0
+#define KPF_WGRAD_FAMILY_R16 1
+#define KPF_WGRAD_FAMILY_DIRECT 2
+#define KPF_WGRAD_FAMILY_H16S 3
+#define KPF_WGRAD_FAMILY_H16 4
+#define KPF_WGRAD_FORM_F32_2x2 1 /* (vn, vk) = (2, 2): 64 x 64 */
+#define KPF_WGRAD_FORM_F32_2x4 2 /* 64 x 128 */
+#define KPF_WGRAD_FORM_F32_4x2 3 /* 128 x 64 */
+#define KPF_WGRAD_FORM_F32_4x4 4 /* 128 x 128 */
+#define KPF_WGRAD_FORM_H16S 5
+#define KPF_WGRAD_FORM_H16 6
+typedef struct kpf_wgrad_plan {
+  int family, vn, vk, tiles_n, tiles_k, S, sps, writes_dw;
+  long ws_floats;
+} kpf_wgrad_plan;
+int kpf_conv2d_wgrad_plan(int dtype, int groups, long M, int N, int K, int is_1x1, int trimmed, kpf_wgrad_plan* out);
+int kpf_conv2d_wgrad_force_form(int form);
 
 /* Row pad / column-slice copy / type change in one launch, and the pose tokens of a fusion block at their padded width (csrc/kpf_train.hip). */
 int kpf_pad_rows(const void* src, int src_dtype, void* dst, int dst_dtype, long rows, int C, int src_ld, int Cp, void* stream);
@@ -810,7 +838,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 21
+#define KPF_ABI_VERSION 22
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

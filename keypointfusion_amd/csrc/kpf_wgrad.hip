@@ -1111,6 +1111,28 @@ struct Plan { int vn, vk, tilesN, tilesK, S, sps; };
 // — the partial layout [N][K] IS dW's for a 1x1 — without a reduce launch.  (Tried up to 24 stages for the 21-token stacks of the fusion
 // head, M = 21 B = 672: the serial walk costs 19 us against 8 + 6 for split + reduce.)
 constexpr int DIRECT_MAX_STAGES = 4;
+// one (vn, vk) tile shape of the cost model: its plan, and its modelled time in *t
+Plan plan_wgrad_tile(long M, int N, int K, int vn, int vk, double* t_out = nullptr) {
+  const int total = (int)((M + RB - 1) / RB);
+  Plan p;
+  p.vn = vn, p.vk = vk;
+  p.tilesN = (N + 32 * vn - 1) / (32 * vn);
+  p.tilesK = (K + 32 * vk - 1) / (32 * vk);
+  const int tiles = p.tilesN * p.tilesK;
+  int S = (768 + tiles - 1) / tiles;
+  const int smax = (total + 3) / 4;
+  if (S > smax) S = smax < 1 ? 1 : smax;
+  p.sps = (total + S - 1) / S;
+  p.S = (total + p.sps - 1) / p.sps;
+  const double np = 32.0 * vn * p.tilesN, kp = 32.0 * vk * p.tilesK;
+  const double t_mfma = 2.0 * M * np * kp / 110e12;
+  const double t_l2 = 4.0 * M * (np * p.tilesK + kp * p.tilesN) / 5e12;
+  const double t_ws = 8.0 * p.S * (double)N * K / 3e12;
+  const double occ = (double)tiles * p.S / 512.0;  // fewer than two workgroups per CU: the chip is not full
+  if (t_out) *t_out = (t_mfma > t_l2 ? t_mfma : t_l2) / (occ < 1.0 ? occ : 1.0) + t_ws;
+  return p;
+}
+
 Plan plan_wgrad(long M, int N, int K, bool direct_ok = false) {
   const int total = (int)((M + RB - 1) / RB);
   if (direct_ok && total <= DIRECT_MAX_STAGES) {
@@ -1124,22 +1146,8 @@ Plan plan_wgrad(long M, int N, int K, bool direct_ok = false) {
   double best_t = 1e30;
   for (int vn = 2; vn <= 4; vn += 2)
     for (int vk = 2; vk <= 4; vk += 2) {
-      Plan p;
-      p.vn = vn, p.vk = vk;
-      p.tilesN = (N + 32 * vn - 1) / (32 * vn);
-      p.tilesK = (K + 32 * vk - 1) / (32 * vk);
-      const int tiles = p.tilesN * p.tilesK;
-      int S = (768 + tiles - 1) / tiles;
-      const int smax = (total + 3) / 4;
-      if (S > smax) S = smax < 1 ? 1 : smax;
-      p.sps = (total + S - 1) / S;
-      p.S = (total + p.sps - 1) / p.sps;
-      const double np = 32.0 * vn * p.tilesN, kp = 32.0 * vk * p.tilesK;
-      const double t_mfma = 2.0 * M * np * kp / 110e12;
-      const double t_l2 = 4.0 * M * (np * p.tilesK + kp * p.tilesN) / 5e12;
-      const double t_ws = 8.0 * p.S * (double)N * K / 3e12;
-      const double occ = (double)tiles * p.S / 512.0;  // fewer than two workgroups per CU: the chip is not full
-      const double t = (t_mfma > t_l2 ? t_mfma : t_l2) / (occ < 1.0 ? occ : 1.0) + t_ws;
+      double t;
+      const Plan p = plan_wgrad_tile(M, N, K, vn, vk, &t);
       if (t < best_t) best_t = t, best = p;
     }
   return best;
@@ -1183,6 +1191,58 @@ Plan plan_wgrad_h16s(long M, int N, int K, int groups = 1) {
   p.S = (total + p.sps - 1) / p.sps;
   return p;
 }
+
+// ---- the one place that decides which kernel takes a kpf_conv2d_wgrad call (conv2d_wgrad_impl, kpf_conv2d_wgrad_ws_floats and kpf_conv2d_wgrad_plan all ask
+// here).  g_force_form (kpf_conv2d_wgrad_force_form; 0 = the rules and cost models above): KPF_WGRAD_FORM_F32_* pins the (vn, vk) tile of every call the fp32-MFMA
+// kernels take (fp32 operands, KPF_DT_F32_MMA_*, the widening form of 16-bit operands) and switches the direct shortcut off; KPF_WGRAD_FORM_H16S / _H16 pins
+// the kernel of every call the 16-bit kernels take, over the `big` rule and KPF_WG16_FORM.  A value of the other family leaves a call to the rules.
+std::atomic<int> g_force_form{0};
+
+struct WgradChoice {
+  Plan p;
+  int family;  // KPF_WGRAD_FAMILY_*
+  bool h16s, h16;
+};
+
+WgradChoice select_wgrad(int dtype, int groups, long M, int N, long K, bool one, bool trimmed, int force) {
+  (void)trimmed;  // (what a trimmed call changes is where the single partial array goes, not the kernel or its split: wgrad_writes_dw)
+  const bool r16 = dtype == KPF_DT_F32_MMA_BF16 || dtype == KPF_DT_F32_MMA_F16;
+  const bool sixteen = dtype == KPF_DT_BF16 || dtype == KPF_DT_F16;
+  static const int h16_widen = []() { const char* e = getenv("KPF_WGRAD_H16_WIDEN"); return e ? atoi(e) : 0; }();  // tuning aid: the old widening kernel
+  // 16-bit operands: the 64-tile form (wgrad_h16s_kernel, two buffers = two workgroups per CU) — GEMM + reduce of a ConvNeXt-T iteration
+  // 3.01 ms against 3.51 for the 128-tile form (a quarter of the partial-sum traffic, no split at all for the layers whose tiles fill the
+  // chip); with three buffers (one workgroup per CU) it loses (3.61).  KPF_WG16_FORM=128 selects the 128-tile form (tuning aid).
+  static const int h16_form = []() { const char* e = getenv("KPF_WG16_FORM"); return e ? atoi(e) : 64; }();
+  const bool h16 = sixteen && !h16_widen;
+  // few pixels, many output tiles (the 4 x 4 maps of the last ConvNeXt stage: M = 512, 3072 x 768 outputs per backbone): the 128-tile kernel without a split — a
+  // quarter of the workgroups of the 64-tile form, each walking all pixels, no cross-wave sum — when its tiles alone fill the chip (KPF_WG16_BIG_M: pixel limit)
+  static const int big_m = []() { const char* e = getenv("KPF_WG16_BIG_M"); return e ? atoi(e) : 512; }();
+  const bool forced16 = h16 && (force == KPF_WGRAD_FORM_H16S || force == KPF_WGRAD_FORM_H16);
+  const bool big = h16 && !forced16 && one && M <= big_m && (long)((N + HB - 1) / HB) * ((K + HB - 1) / HB) * groups >= 256;
+  WgradChoice c;
+  c.h16s = forced16 ? force == KPF_WGRAD_FORM_H16S : (h16 && h16_form != 128 && !big);
+  c.h16 = h16;
+  if (c.h16s) {
+    c.p = plan_wgrad_h16s(M, N, (int)K, groups);
+    c.family = KPF_WGRAD_FAMILY_H16S;
+  } else if (h16) {
+    c.p = plan_wgrad_h16(M, N, (int)K);
+    if (big) c.p.S = 1, c.p.sps = (int)((M + RB - 1) / RB);
+    c.family = KPF_WGRAD_FAMILY_H16;
+  } else if (force >= KPF_WGRAD_FORM_F32_2x2 && force <= KPF_WGRAD_FORM_F32_4x4) {
+    c.p = plan_wgrad_tile(M, N, (int)K, force >= KPF_WGRAD_FORM_F32_4x2 ? 4 : 2, (force == KPF_WGRAD_FORM_F32_2x4 || force == KPF_WGRAD_FORM_F32_4x4) ? 4 : 2);
+    c.family = r16 && c.p.vn == 2 && c.p.vk == 2 ? KPF_WGRAD_FAMILY_R16 : KPF_WGRAD_FAMILY_F32;
+  } else {
+    c.p = plan_wgrad(M, N, (int)K, one);
+    const bool shortcut = one && (M + RB - 1) / RB <= DIRECT_MAX_STAGES;
+    c.family = r16 && c.p.vn == 2 && c.p.vk == 2 ? KPF_WGRAD_FAMILY_R16 : (shortcut ? KPF_WGRAD_FAMILY_DIRECT : KPF_WGRAD_FAMILY_F32);
+  }
+  return c;
+}
+
+// the single partial array of an unsplit 1x1 IS dW ([N][K]): the kernel writes dw / db itself and no reduce follows
+inline bool wgrad_writes_dw(const Plan& p, bool one, bool trimmed) { return one && p.S == 1 && !trimmed; }
+inline long wgrad_group_ws(const Plan& p, int N, long K) { return (long)p.S * N * K + (long)p.S * N; }
 
 const float* zero_page() {
   static std::atomic<const float*> cache[KPF_MAX_DEVICES];
@@ -1249,9 +1309,31 @@ extern "C" {
 
 long kpf_conv2d_wgrad_ws_floats(long M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const Plan p = plan_wgrad(M, N, K), h = plan_wgrad_h16(M, N, K), hs = plan_wgrad_h16s(M, N, K);  // (any of the kernels may take the call)
+  // (any of the kernels may take the call — the query knows neither the operands' type nor the kernel size: the fp32 plan of a convolution, which no shortcut
+  //  shortens and which follows a forced tile, and both 16-bit forms)
+  const int force = g_force_form.load(std::memory_order_relaxed);
+  const Plan p = select_wgrad(KPF_DT_F32, 1, M, N, K, false, false, force).p;
+  const Plan h = select_wgrad(KPF_DT_BF16, 1, M, N, K, false, false, KPF_WGRAD_FORM_H16).p, hs = select_wgrad(KPF_DT_BF16, 1, M, N, K, false, false, KPF_WGRAD_FORM_H16S).p;
   const int S = p.S > h.S ? (p.S > hs.S ? p.S : hs.S) : (h.S > hs.S ? h.S : hs.S);
   return (long)S * N * K + (long)S * N;
+}
+
+int kpf_conv2d_wgrad_force_form(int form) {
+  KPF_REQUIRE(form >= 0 && form <= KPF_WGRAD_FORM_H16, "kpf_conv2d_wgrad_force_form: unknown form %d", form);
+  g_force_form.store(form, std::memory_order_relaxed);
+  return KPF_OK;
+}
+
+int kpf_conv2d_wgrad_plan(int dtype, int groups, long M, int N, int K, int is_1x1, int trimmed, kpf_wgrad_plan* out) {
+  KPF_REQUIRE(out, "kpf_conv2d_wgrad_plan: null pointer");
+  KPF_REQUIRE(dtype == KPF_DT_F32 || dtype == KPF_DT_BF16 || dtype == KPF_DT_F16 || dtype == KPF_DT_F32_MMA_BF16 || dtype == KPF_DT_F32_MMA_F16,
+              "kpf_conv2d_wgrad_plan: unknown dtype %d", dtype);
+  KPF_REQUIRE(groups >= 1 && groups <= 64 && M > 0 && N > 0 && K > 0, "kpf_conv2d_wgrad_plan: bad shape");
+  const WgradChoice c = select_wgrad(dtype, groups, M, N, K, is_1x1 != 0, trimmed != 0, g_force_form.load(std::memory_order_relaxed));
+  out->family = c.family, out->vn = c.p.vn, out->vk = c.p.vk, out->tiles_n = c.p.tilesN, out->tiles_k = c.p.tilesK, out->S = c.p.S, out->sps = c.p.sps;
+  out->writes_dw = wgrad_writes_dw(c.p, is_1x1 != 0, trimmed != 0) ? 1 : 0;
+  out->ws_floats = wgrad_group_ws(c.p, N, K);
+  return KPF_OK;
 }
 
 static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W,
@@ -1277,22 +1359,13 @@ static int conv2d_wgrad_impl(const void* dy, const void* x, int dtype, float* dw
   const long M = (long)B * OH * OW;
   const long K = (long)KH * KW * Cin;
   KPF_REQUIRE(M < (1L << 31) && K < (1L << 24) && (long)B * H * W < (1L << 31), "kpf_conv2d_wgrad: problem too large");
-  static const int h16_widen = []() { const char* e = getenv("KPF_WGRAD_H16_WIDEN"); return e ? atoi(e) : 0; }();  // tuning aid: the old widening kernel
-  // 16-bit operands: the 64-tile form (wgrad_h16s_kernel, two buffers = two workgroups per CU) — GEMM + reduce of a ConvNeXt-T iteration
-  // 3.01 ms against 3.51 for the 128-tile form (a quarter of the partial-sum traffic, no split at all for the layers whose tiles fill the
-  // chip); with three buffers (one workgroup per CU) it loses (3.61).  KPF_WG16_FORM=128 selects the 128-tile form (tuning aid).
-  static const int h16_form = []() { const char* e = getenv("KPF_WG16_FORM"); return e ? atoi(e) : 64; }();
-  const bool h16 = dtype != KPF_DT_F32 && !h16_widen;
   const bool one = KH == 1 && KW == 1;
-  // few pixels, many output tiles (the 4 x 4 maps of the last ConvNeXt stage: M = 512, 3072 x 768 outputs per backbone): the 128-tile kernel without a split — a
-  // quarter of the workgroups of the 64-tile form, each walking all pixels, no cross-wave sum — when its tiles alone fill the chip (KPF_WG16_BIG_M: pixel limit)
-  static const int big_m = []() { const char* e = getenv("KPF_WG16_BIG_M"); return e ? atoi(e) : 512; }();
-  const bool big = h16 && one && M <= big_m && (long)((N + HB - 1) / HB) * ((K + HB - 1) / HB) * groups >= 256;
-  const bool h16s = h16 && h16_form != 128 && !big;
-  Plan p = h16s ? plan_wgrad_h16s(M, N, (int)K, groups) : (h16 ? plan_wgrad_h16(M, N, (int)K) : plan_wgrad(M, N, (int)K, one));
-  if (big) p.S = 1, p.sps = (int)((M + RB - 1) / RB);
-  const bool direct = one && p.S == 1 && !trimmed;  // the single partial array is dW
-  const long wsg = (long)p.S * N * K + (long)p.S * N;  // one group's workspace
+  const WgradChoice ch = select_wgrad(r16 ? (r16 == 1 ? KPF_DT_F32_MMA_BF16 : KPF_DT_F32_MMA_F16) : dtype, groups, M, N, K, one, trimmed,
+                                      g_force_form.load(std::memory_order_relaxed));
+  const Plan p = ch.p;
+  const bool h16s = ch.h16s, h16 = ch.h16;
+  const bool direct = wgrad_writes_dw(p, one, trimmed);  // the single partial array is dW
+  const long wsg = wgrad_group_ws(p, N, K);  // one group's workspace
   KPF_REQUIRE(ws_floats >= groups * wsg, "kpf_conv2d_wgrad: workspace too small (%ld floats, need %ld)", ws_floats, groups * wsg);
   WgradArgs a;
   a.dy = dy, a.x = x, a.part = direct ? dw : ws, a.dbpart = db ? (direct ? db : ws + (size_t)p.S * N * K) : nullptr;

@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 21  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 22  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -55,6 +55,13 @@ class WgradReduceDesc(C.Structure):  # kpf_wgrad_reduce_desc (include/kpf.h)
     _fields_ = [("part", C.c_void_p), ("dbpart", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("g_ws", C.c_long)] + [
         (n, C.c_int) for n in "S N K Cin KHW nkb ndb groups Cin_out N_out kind first_block".split()]
 
+
+class WgradPlan(C.Structure):  # kpf_wgrad_plan (include/kpf.h)
+    _fields_ = [(n, C.c_int) for n in "family vn vk tiles_n tiles_k S sps writes_dw".split()] + [("ws_floats", C.c_long)]
+
+
+KPF_WGRAD_FAMILY = ("f32", "r16", "direct", "h16s", "h16")  # KPF_WGRAD_FAMILY_* by value
+KPF_WGRAD_FORM = {"f32_2x2": 1, "f32_2x4": 2, "f32_4x2": 3, "f32_4x4": 4, "h16s": 5, "h16": 6}  # KPF_WGRAD_FORM_* (kpf_conv2d_wgrad_force_form; 0 = cost model)
 
 _P = C.c_void_p
 _SIGS = {
@@ -118,6 +125,8 @@ _SIGS = {
     "kpf_conv2d_wgrad": [_P, _P, C.c_int] + [_P] * 3 + [C.c_long] + [C.c_int] * 18 + [C.POINTER(WgradReduceDesc), _P],
     "kpf_dwconv7_wgrad": [_P] * 5 + [C.c_long] + [C.c_int] * 4 + [C.POINTER(WgradReduceDesc), _P],
     "kpf_wgrad_reduce_multi": [C.POINTER(WgradReduceDesc), C.c_int, _P],
+    "kpf_conv2d_wgrad_plan": [C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WgradPlan)],
+    "kpf_conv2d_wgrad_force_form": [C.c_int],
     "kpf_row_gather_cols_f32": [_P, C.c_long, C.c_long, C.c_long, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_bn_ssr_forward": [_P] * 7 + [C.c_float, C.c_float, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, _P],
     "kpf_bn_ssr_backward": [_P] * 10 + [C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, _P],

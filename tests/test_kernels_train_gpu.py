@@ -19,6 +19,8 @@ def _ref(x_nhwc, dy_nhwc, wshape, stride, pad, groups=1):
     return w.grad, b.grad
 
 
+# (At these sizes kpf_conv2d_wgrad_plan names the 64 x 64 fp32 tile for every case below, four of them through the one-workgroup shortcut; the other tile shapes,
+#  the 16-bit kernels and the forms behind switches are forced and held to float64 in test_wgrad_forms_gpu.py.)
 CASES = [  # B, H, W, Cin, N, k, stride, pad
     (2, 8, 8, 384, 1536, 1, 1, 0),     # pwconv1 at stage 3
     (2, 8, 8, 1536, 384, 1, 1, 0),     # pwconv2
