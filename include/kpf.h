@@ -833,12 +833,45 @@ int kpf_track_step_f32(const float* joints, const float* center, const float* M,
                        int frame_w, int frame_h, float expansion, long long seed_stride, double* bbox, long long* seed, int* lost, float* crop_px,
                        float* frame_px, float* cam_mm, double* bbox_used, int* status, void* stream);
 
+/* Preprocessing by the dataset protocol (ABI 23): annotations in, the model's inputs AND the labels out — keypointfusion_amd/preprocess.py::prepare_annotated
+ * (reference: dataloader/loader.py:1113-1204 DexYCB and :1296-1416 HO3D, test branch, flip = 1).  The crop is cut around an ANNOTATED 3-D centre instead of a
+ * box's centre of mass, left hands are mirrored, and everything up to the integer bounds is FLOAT arithmetic (the annotations and intrinsics are float32 in
+ * the reference), every operation an IEEE +, -, *, / rounded once, no contraction.
+ *
+ * kpf_prep_annot_u16: rgb, depth, frame_index / F (NULL / F >= B: sample b reads frame b), the window and S as kpf_prep_crop_u16[_indexed]; joints_mm
+ * [B][J][3] float (camera space, mm, the model's joint order; NULL: no ground truth, the labels are zeros), cam32 [B][4] float (fx fy u0 v0), center_xyz
+ * [B][3] float (NULL: the mean of the joints; joints_mm and center_xyz are not both NULL), mirror [B] bytes (non-zero: a left hand), cube [B][3] double.
+ * One workgroup of 1024 threads per sample, J <= 64.  Wave 0, one lane per joint: uvd = (x * fx / z + u0, y * fy / z + v0, z); mirrored: u = (W - u) - 1;
+ * xyz = ((u - u0) * d / fx, (v - v0) * d / fy, d).  One lane: centre = center_xyz, or the xyz rows summed IN ORDER j = 0 .. J-1 from 0 and divided by J;
+ * center_uvd = its projection; bounds xs = (int)floor((u * d / fx - cube_x / 2) / d * fx + 0.5) (xe with +, ys / ye with v, fy, cube_y), z range d -+ cube_z
+ * / 2, all in float; from the integer bounds on as kpf_prep_crop_u16 (M in double).  A mirrored sample reads logical pixel (y, x) of the H x W frame from TRUE
+ * column W - 1 - x (the window test applies to the true column: the stored window is not flipped).
+ * -> the outputs of kpf_prep_crop_u16 with center = ((u - u0) * d / fx, (v - v0) * d / fy, d) of center_uvd in float (the round trip of the centre, which may
+ * differ from it by an ulp, as in the reference), com = center_uvd widened to double, cam_para = cam32; and
+ *   joint [B][J][3] float = (xyz - centre) / (float)(cube_z / 2)                                                        (what kpf_eval_errors_f32 takes as gt)
+ *   joint_img [B][J][3] float: p = (double)joint * (cube_x / 2) + (double)center in DOUBLE (the reference's cube is an integer array, which promotes), u =
+ *       (float)(p_x * fx / p_z + u0), v likewise, d = (float)p_z; crop pixel = (float)(scale * u + m02) (v: m12); then in float u / (S / 2) - 1, v / (S / 2) - 1,
+ *       (float)((double)(d - center_z) / (cube_x / 2))
+ *   cam64 [B][4] double = cam32 widened: kpf_prep_pcl_sample runs unchanged on img, center, M64, cube and cam64.
+ * The intrinsics are used un-mirrored on the mirrored image, as in the reference: a mirrored sample's camera space is the mirrored camera's. */
+int kpf_prep_annot_u16(const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const float* joints_mm, const float* cam32,
+                       const float* center_xyz, const unsigned char* mirror, const double* cube, int B, int J, int Hs, int Ws, int x0, int y0, int H, int W, int S,
+                       float* img, float* img_rgb, float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds, double* M64, float* joint,
+                       float* joint_img, double* cam64, void* stream);
+
+/* kpf_prep_uncrop_mirror_f32 (ABI 23): kpf_prep_uncrop_f32 for the samples of kpf_prep_annot_u16.  mirror [B] bytes, frame_w = W of the logical frame: a
+ * mirrored sample's frame_px u is W - 1 - u, taken in double before the rounding to float; crop_px, and every value of an un-mirrored sample, are the bits of
+ * kpf_prep_uncrop_f32.  The predicted xyz (joints, crop_px d, frame_px d) stays in the MIRRORED camera's space, as in the reference, which scores left hands
+ * there. */
+int kpf_prep_uncrop_mirror_f32(const float* joints, const float* center, const float* M, const float* cube, const float* cam, const unsigned char* mirror,
+                               int frame_w, int B, int J, float* crop_px, float* frame_px, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 22
+#define KPF_ABI_VERSION 23
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

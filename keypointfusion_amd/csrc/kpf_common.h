@@ -70,9 +70,10 @@ __host__ __device__ __forceinline__ unsigned hash32(unsigned x) {
 
 // preprocess.project_to_crop + uncrop_points for ONE joint (j: 3 floats normalised to the cube; center, M, cube, cam: the sample's float32 parameters), double
 // inside, contraction off (the host rounds every product and sum).  The one definition behind kpf_prep_uncrop_f32 and kpf_track_step_f32: their crop and
-// frame pixels are the same bits.
+// frame pixels are the same bits.  mirror_w >= 0 (kpf_prep_uncrop_mirror_f32: the width of a mirrored sample's frame): frame u = (mirror_w - 1) - u, in double.
 __device__ __forceinline__ void kpf_uncrop_joint(const float* __restrict__ j, const float* __restrict__ center, const float* __restrict__ M,
-                                                 const float* __restrict__ cube, const float* __restrict__ cam, float* crop3, float* frame3) {
+                                                 const float* __restrict__ cube, const float* __restrict__ cam, float* crop3, float* frame3,
+                                                 double mirror_w = -1.0) {
 #pragma clang fp contract(off)
   double m[9];
   for (int k = 0; k < 9; ++k) m[k] = (double)M[k];
@@ -90,7 +91,8 @@ __device__ __forceinline__ void kpf_uncrop_joint(const float* __restrict__ j, co
   const double c20 = m[3] * m[7] - m[4] * m[6], c21 = m[1] * m[6] - m[0] * m[7], c22 = m[0] * m[4] - m[1] * m[3];
   const double det = m[0] * c00 + m[1] * c10 + m[2] * c20;
   const double h0 = (cu * c00 + cv * c01 + c02) / det, h1 = (cu * c10 + cv * c11 + c12) / det, h2 = (cu * c20 + cv * c21 + c22) / det;
-  frame3[0] = (float)(h0 / h2);
+  const double fu = h0 / h2;
+  frame3[0] = (float)(mirror_w >= 0.0 ? (mirror_w - 1.0) - fu : fu);
   frame3[1] = (float)(h1 / h2);
   frame3[2] = (float)z;
 }

@@ -7,6 +7,9 @@
 //   kpf_prep_pcl_sample  foreground pixels of the normalised crop -> candidate points in np.where order -> n of them without replacement IN RANDOM ORDER:
 //                        (hash key, candidate) pairs sorted by a bitonic network in LDS (only those under a threshold that about 1.5 n pass), the first n taken
 //   kpf_prep_uncrop_f32  normalised joints -> crop pixels -> frame pixels
+//   kpf_prep_annot_u16   the crop by the DATASET protocol (preprocess.prepare_annotated): the centre from the annotated joints (or given), left hands mirrored,
+//                        float32 up to the integer bounds, plus the labels joint / joint_img; then the same gather and normalisation as kpf_prep_crop_u16
+//                        (kpf_prep_uncrop_mirror_f32: the un-crop that takes a mirrored sample's u back to the camera's frame)
 //
 // The host path is the yardstick (tests/test_preprocess_gpu.py): integer decisions and both images are bit-equal to it.  Everything that decides an integer
 // is computed in double in the HOST'S operation order, and the whole file is compiled with floating-point contraction OFF (the Makefile's -ffp-contract=on
@@ -46,6 +49,27 @@ struct PrepGeom {
   float center[3];                 // image_to_3d(com)
 };
 
+// From the integer bounds on: resize size, letterbox offsets, nearest-neighbour steps and M (double), shared by prep_geom and prep_geom_f32
+__host__ __device__ inline void prep_geom_layout(PrepGeom& g, int S) {
+  const int wb = g.xe - g.xs, hb = g.ye - g.ys;
+  if (wb <= 0 || hb <= 0) {  // a cube that projects to nothing (not reachable with positive focal lengths and cube sizes): an empty crop
+    g.szw = g.szh = 0;
+  } else if (wb > hb) {
+    g.szw = S;
+    g.szh = (int)((double)((long long)hb * S) / (double)wb);
+  } else {
+    g.szw = (int)((double)((long long)wb * S) / (double)hb);
+    g.szh = S;
+  }
+  g.scale = hb > wb ? (double)g.szh / (double)hb : (double)g.szw / (double)(wb > 0 ? wb : 1);
+  g.stepx = g.szw > 0 ? (double)wb / (double)g.szw : 0.0;
+  g.stepy = g.szh > 0 ? (double)hb / (double)g.szh : 0.0;
+  g.offx = (int)floor((double)S / 2.0 - (double)g.szw / 2.0);
+  g.offy = (int)floor((double)S / 2.0 - (double)g.szh / 2.0);
+  g.m02 = g.scale * (double)(-g.xs) + (double)g.offx;  // off . (scale . trans): one product, one sum, each rounded
+  g.m12 = g.scale * (double)(-g.ys) + (double)g.offy;
+}
+
 // count / sums over the valid depth of the box (indices relative to the clipped box) -> everything crop_image and normalize_depth need
 __host__ __device__ inline void prep_geom(unsigned long long cnt, unsigned long long sumx, unsigned long long sumy, unsigned long long sumd, const PrepBox& bx,
                                           const double* bbox, const double* cam, const double* cube, int S, PrepGeom& g) {
@@ -72,23 +96,7 @@ __host__ __device__ inline void prep_geom(unsigned long long cnt, unsigned long 
   g.xe = (int)floor((c0 * c2 / fx + cube[0] / 2.0) / c2 * fx + 0.5);
   g.ys = (int)floor((c1 * c2 / fy - cube[1] / 2.0) / c2 * fy + 0.5);
   g.ye = (int)floor((c1 * c2 / fy + cube[1] / 2.0) / c2 * fy + 0.5);
-  const int wb = g.xe - g.xs, hb = g.ye - g.ys;
-  if (wb <= 0 || hb <= 0) {  // a cube that projects to nothing (not reachable with positive focal lengths and cube sizes): an empty crop
-    g.szw = g.szh = 0;
-  } else if (wb > hb) {
-    g.szw = S;
-    g.szh = (int)((double)((long long)hb * S) / (double)wb);
-  } else {
-    g.szw = (int)((double)((long long)wb * S) / (double)hb);
-    g.szh = S;
-  }
-  g.scale = hb > wb ? (double)g.szh / (double)hb : (double)g.szw / (double)(wb > 0 ? wb : 1);
-  g.stepx = g.szw > 0 ? (double)wb / (double)g.szw : 0.0;
-  g.stepy = g.szh > 0 ? (double)hb / (double)g.szh : 0.0;
-  g.offx = (int)floor((double)S / 2.0 - (double)g.szw / 2.0);
-  g.offy = (int)floor((double)S / 2.0 - (double)g.szh / 2.0);
-  g.m02 = g.scale * (double)(-g.xs) + (double)g.offx;  // off . (scale . trans): one product, one sum, each rounded
-  g.m12 = g.scale * (double)(-g.ys) + (double)g.offy;
+  prep_geom_layout(g, S);
   g.far = (float)(c2 + cube[2] / 2.0);
   g.near = (float)(c2 - cube[2] / 2.0);
   g.comz = (float)c2;
@@ -96,6 +104,47 @@ __host__ __device__ inline void prep_geom(unsigned long long cnt, unsigned long 
   g.center[0] = (float)((c0 - fu) * c2 / fx);
   g.center[1] = (float)((c1 - fv) * c2 / fy);
   g.center[2] = (float)c2;
+}
+
+// IEEE float32 division on either side (the device's default `/` may be the approximate one)
+__host__ __device__ inline float prep_fdiv(float a, float b) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __fdiv_rn(a, b);
+#else
+  return a / b;
+#endif
+}
+
+// a float bound as an integer; beyond +-2^28 (or NaN -> 0: a centre at depth 0, not a hand) it saturates, so that no later integer arithmetic overflows
+__host__ __device__ inline int prep_bound_f32(float v) {
+  const float f = floorf(v);
+  return f >= 268435456.0f ? 268435456 : f <= -268435456.0f ? -268435456 : f == f ? (int)f : 0;
+}
+
+// preprocess.annotated_bounds + the scalars of normalize_depth and the round trip of the centre, for prepare_annotated: the centre cuvd (u, v, d mm) and the
+// intrinsics are float32 and every operation up to the integer bounds is a float32 one in the reference's order (dataloader/loader.py:291-301 called with
+// np.float32 operands); from the bounds on as prep_geom
+__host__ __device__ inline void prep_geom_f32(const float* cuvd, const float* cam, const double* cube, int S, PrepGeom& g) {
+  const float u = cuvd[0], v = cuvd[1], d = cuvd[2], fx = cam[0], fy = cam[1], fu = cam[2], fv = cam[3];
+  const float hx = (float)(cube[0] / 2.0), hy = (float)(cube[1] / 2.0), hz = (float)(cube[2] / 2.0);
+  g.com[0] = (double)u;
+  g.com[1] = (double)v;
+  g.com[2] = (double)d;
+  const float zs = d - hz, ze = d + hz;
+  g.zs = (double)zs;
+  g.ze = (double)ze;
+  g.xs = prep_bound_f32(prep_fdiv(prep_fdiv(u * d, fx) - hx, d) * fx + 0.5f);
+  g.xe = prep_bound_f32(prep_fdiv(prep_fdiv(u * d, fx) + hx, d) * fx + 0.5f);
+  g.ys = prep_bound_f32(prep_fdiv(prep_fdiv(v * d, fy) - hy, d) * fy + 0.5f);
+  g.ye = prep_bound_f32(prep_fdiv(prep_fdiv(v * d, fy) + hy, d) * fy + 0.5f);
+  prep_geom_layout(g, S);
+  g.far = ze;
+  g.near = zs;
+  g.comz = d;
+  g.halfz = hz;
+  g.center[0] = prep_fdiv((u - fu) * d, fx);
+  g.center[1] = prep_fdiv((v - fv) * d, fy);
+  g.center[2] = d;
 }
 
 // Frame pixel behind crop pixel (oy, ox): false = letterbox border
@@ -174,6 +223,47 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
+// Phases 3 and 4 of a crop, shared by prep_crop_kernel (mirror = 0) and prep_annot_kernel: gather (z-clamped depth into LDS, where its maximum decides the
+// far plane; RGB straight out), then normalize_depth.  A mirrored sample's logical pixel (fy, fx) of the H x W frame is TRUE column W - 1 - fx, and the
+// stored window is tested against that true column.  All PREP_NT threads of the workgroup; contains a barrier.
+__device__ __forceinline__ void prep_gather_normalize(const PrepGeom& g, const unsigned short* __restrict__ dep, const unsigned char* __restrict__ col, int mirror,
+                                                      int Hs, int Ws, int ox, int oy, int H, int W, int S, unsigned short* crop, unsigned* wmax,
+                                                      float* __restrict__ img, float* __restrict__ img_rgb) {
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int P = S * S;
+  unsigned mx = 0;
+  for (int p = t; p < P; p += PREP_NT) {
+    const int oyp = p / S, oxp = p - oyp * S;
+    int fy, fx;
+    unsigned short v = 0;
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+    if (prep_source(g, oyp, oxp, fy, fx) && fy >= 0 && fy < H && fx >= 0 && fx < W) {
+      const int wy = fy - oy, wx = (mirror ? W - 1 - fx : fx) - ox;
+      if (wy >= 0 && wy < Hs && wx >= 0 && wx < Ws) {
+        const size_t s = (size_t)wy * Ws + wx;
+        v = prep_zclamp(dep[s], g);
+        c0 = (float)col[3 * s];
+        c1 = (float)col[3 * s + 1];
+        c2 = (float)col[3 * s + 2];
+      }
+    }
+    crop[p] = v;
+    mx = max(mx, (unsigned)v);
+    float* o = img_rgb + (size_t)b * 3 * P + p;
+    o[0] = __fdiv_rn(c0, 255.0f);
+    o[P] = __fdiv_rn(c1, 255.0f);
+    o[2 * (size_t)P] = __fdiv_rn(c2, 255.0f);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+  if (lane == 0) wmax[wv] = mx;
+  __syncthreads();
+  PREP_STAMP(2);
+  unsigned premax = 0;
+  for (int w = 0; w < PREP_NW; ++w) premax = max(premax, wmax[w]);
+  for (int p = t; p < P; p += PREP_NT) img[(size_t)b * P + p] = prep_normalize(crop[p], (unsigned short)premax, g);
+}
+
 __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
                                                             const int* __restrict__ frame_index, int F, const double* __restrict__ bbox, const double* __restrict__ cam, const double* __restrict__ cube,
                                                             int Hs, int Ws, int ox, int oy, int H, int W, int S, float* __restrict__ img,
@@ -250,41 +340,116 @@ __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char*
   __syncthreads();
   const PrepGeom g = *gs;
   PREP_STAMP(1);
+  // 3. gather, 4. normalize_depth
+  prep_gather_normalize(g, dep, col, 0, Hs, Ws, ox, oy, H, W, S, crop, wmax, img, img_rgb);
+  PREP_STAMP(3);
+}
 
-  // 3. gather: z-clamped depth into LDS (its maximum decides the far plane), RGB straight out
-  const int P = S * S;
-  unsigned mx = 0;
-  for (int p = t; p < P; p += PREP_NT) {
-    const int oyp = p / S, oxp = p - oyp * S;
-    int fy, fx;
-    unsigned short v = 0;
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-    if (prep_source(g, oyp, oxp, fy, fx) && fy >= 0 && fy < H && fx >= 0 && fx < W) {
-      const int wy = fy - oy, wx = fx - ox;
-      if (wy >= 0 && wy < Hs && wx >= 0 && wx < Ws) {
-        const size_t s = (size_t)wy * Ws + wx;
-        v = prep_zclamp(dep[s], g);
-        c0 = (float)col[3 * s];
-        c1 = (float)col[3 * s + 1];
-        c2 = (float)col[3 * s + 2];
-      }
+// kpf_prep_annot_u16: the crop by the dataset protocol (preprocess.prepare_annotated).  Phase 0 replaces the box reduction: the centre comes from the annotation.
+constexpr int ANNOT_XYZ = 65 * 3;           // float xyz of up to 64 joints + the centre they are normalised by
+constexpr int ANNOT_XYZ_BYTES = 800;        // (16-byte multiple)
+__global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
+                                                             const int* __restrict__ frame_index, int F, const float* __restrict__ joints,
+                                                             const float* __restrict__ cam, const float* __restrict__ center_xyz,
+                                                             const unsigned char* __restrict__ mirror, const double* __restrict__ cube, int J, int Hs, int Ws,
+                                                             int ox, int oy, int H, int W, int S, float* __restrict__ img, float* __restrict__ img_rgb,
+                                                             float* __restrict__ center, float* __restrict__ M, float* __restrict__ cube_out,
+                                                             float* __restrict__ cam_out, double* __restrict__ com, int* __restrict__ bounds,
+                                                             double* __restrict__ Md, float* __restrict__ joint, float* __restrict__ joint_img,
+                                                             double* __restrict__ cam64) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert(ANNOT_XYZ * 4 <= ANNOT_XYZ_BYTES && ANNOT_XYZ_BYTES % 16 == 0, "the joints outgrew their LDS slot");
+  float* xyz = reinterpret_cast<float*>(smem);                                                          // [65][3]
+  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + ANNOT_XYZ_BYTES);                                   // 16-byte aligned
+  unsigned* wmax = reinterpret_cast<unsigned*>(smem + ANNOT_XYZ_BYTES + 256);                           // [PREP_NW]
+  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + ANNOT_XYZ_BYTES + 256 + PREP_NW * 4);  // [S * S]
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
+  const unsigned short* dep = depth + (size_t)f * Hs * Ws;
+  const unsigned char* col = rgb + (size_t)f * Hs * Ws * 3;
+  const int mir = mirror[b] ? 1 : 0;
+  const float fx = cam[4 * b], fy = cam[4 * b + 1], fu = cam[4 * b + 2], fv = cam[4 * b + 3];
+  PREP_STAMP(0);
+  // 0a. one lane per joint: uvd, the mirror and xyz in float.  DexYCB's item takes the joints through the image and back, mirrored or not; HO3D's item (the
+  // one with a given centre) uses them as they are
+  if (wv == 0 && joints && lane < J) {
+    const float* jp = joints + ((size_t)b * J + lane) * 3;
+    float x = jp[0], y = jp[1];
+    const float z = jp[2];
+    if (!center_xyz || mir) {
+      float u = prep_fdiv(x * fx, z) + fu;
+      const float v = prep_fdiv(y * fy, z) + fv;
+      if (mir) u = ((float)W - u) - 1.0f;
+      x = prep_fdiv((u - fu) * z, fx);
+      y = prep_fdiv((v - fv) * z, fy);
     }
-    crop[p] = v;
-    mx = max(mx, (unsigned)v);
-    float* o = img_rgb + (size_t)b * 3 * P + p;
-    o[0] = __fdiv_rn(c0, 255.0f);
-    o[P] = __fdiv_rn(c1, 255.0f);
-    o[2 * (size_t)P] = __fdiv_rn(c2, 255.0f);
+    xyz[3 * lane] = x;
+    xyz[3 * lane + 1] = y;
+    xyz[3 * lane + 2] = z;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
-  if (lane == 0) wmax[wv] = mx;
   __syncthreads();
-  PREP_STAMP(2);
-  unsigned premax = 0;
-  for (int w = 0; w < PREP_NW; ++w) premax = max(premax, wmax[w]);
-  // 4. normalize_depth
-  for (int p = t; p < P; p += PREP_NT) img[(size_t)b * P + p] = prep_normalize(crop[p], (unsigned short)premax, g);
+  // 0b. one lane: the centre (given, or the rows summed in order: np.mean(0) of a [J][3] float array), its projection, the geometry
+  if (t == 0) {
+    float c[3] = {0.f, 0.f, 0.f};
+    if (center_xyz) {
+      for (int k = 0; k < 3; ++k) c[k] = center_xyz[3 * b + k];
+    } else {
+      for (int j = 0; j < J; ++j)
+        for (int k = 0; k < 3; ++k) c[k] = c[k] + xyz[3 * j + k];
+      for (int k = 0; k < 3; ++k) c[k] = prep_fdiv(c[k], (float)J);
+    }
+    for (int k = 0; k < 3; ++k) xyz[3 * 64 + k] = c[k];
+    const float cuvd[3] = {prep_fdiv(c[0] * fx, c[2]) + fu, prep_fdiv(c[1] * fy, c[2]) + fv, c[2]};
+    PrepGeom g;
+    prep_geom_f32(cuvd, cam + 4 * b, cube + 3 * b, S, g);
+    *gs = g;
+    for (int k = 0; k < 3; ++k) {
+      center[3 * b + k] = g.center[k];
+      com[3 * b + k] = g.com[k];
+      cube_out[3 * b + k] = (float)cube[3 * b + k];
+    }
+    for (int k = 0; k < 4; ++k) {
+      cam_out[4 * b + k] = cam[4 * b + k];
+      cam64[4 * b + k] = (double)cam[4 * b + k];
+    }
+    const double m[9] = {g.scale, 0.0, g.m02, 0.0, g.scale, g.m12, 0.0, 0.0, 1.0};
+    for (int k = 0; k < 9; ++k) {
+      Md[9 * b + k] = m[k];
+      M[9 * b + k] = (float)m[k];
+    }
+    int* bo = bounds + 6 * b;
+    bo[0] = g.xs;
+    bo[1] = g.xe;
+    bo[2] = g.ys;
+    bo[3] = g.ye;
+    bo[4] = g.szw;
+    bo[5] = g.szh;
+  }
+  __syncthreads();
+  const PrepGeom g = *gs;
+  PREP_STAMP(1);
+  // 0c. the labels, one lane per joint
+  if (wv == 0 && lane < J) {
+    float lab[3] = {0.f, 0.f, 0.f}, uvd[3] = {0.f, 0.f, 0.f};
+    if (joints) {
+      for (int k = 0; k < 3; ++k) lab[k] = prep_fdiv(xyz[3 * lane + k] - xyz[3 * 64 + k], g.halfz);
+      // curLabel * (cube[0] / 2.0) + com3D: the reference's cube is an integer array, so this and the projection are double
+      const double hx = cube[3 * b] / 2.0;
+      const double px = (double)lab[0] * hx + (double)g.center[0], py = (double)lab[1] * hx + (double)g.center[1], pz = (double)lab[2] * hx + (double)g.center[2];
+      const float u = (float)(px * (double)fx / pz + (double)fu), v = (float)(py * (double)fy / pz + (double)fv), d = (float)pz;
+      const float cu = (float)(g.scale * (double)u + g.m02), cv = (float)(g.scale * (double)v + g.m12);  // transformPoints2D, stored as float
+      const float half = (float)((double)S / 2.0);
+      uvd[0] = prep_fdiv(cu, half) - 1.0f;
+      uvd[1] = prep_fdiv(cv, half) - 1.0f;
+      uvd[2] = (float)((double)(d - g.center[2]) / hx);
+    }
+    for (int k = 0; k < 3; ++k) {
+      joint[((size_t)b * J + lane) * 3 + k] = lab[k];
+      joint_img[((size_t)b * J + lane) * 3 + k] = uvd[k];
+    }
+  }
+  // 3. gather, 4. normalize_depth
+  prep_gather_normalize(g, dep, col, mir, Hs, Ws, ox, oy, H, W, S, crop, wmax, img, img_rgb);
   PREP_STAMP(3);
 }
 
@@ -456,9 +621,23 @@ __global__ __launch_bounds__(256) void prep_uncrop_kernel(const float* __restric
   const int b = e / J;
   kpf_uncrop_joint(joints + 3 * e, center + 3 * b, M + 9 * b, cube + 3 * b, cam + 4 * b, crop_px + 3 * e, frame_px + 3 * e);
 }
+
+// kpf_prep_uncrop_f32 for the samples of kpf_prep_annot_u16: a mirrored sample's frame u goes back to the camera's own frame (W - 1 - u, in double before the
+// rounding to float); crop pixels, depths and every un-mirrored sample are the bits of prep_uncrop_kernel.  The predicted xyz stays in the MIRRORED camera's
+// space, as in the reference, which scores left hands there.
+__global__ __launch_bounds__(256) void prep_uncrop_mirror_kernel(const float* __restrict__ joints, const float* __restrict__ center, const float* __restrict__ M,
+                                                                 const float* __restrict__ cube, const float* __restrict__ cam,
+                                                                 const unsigned char* __restrict__ mirror, int frame_w, int B, int J,
+                                                                 float* __restrict__ crop_px, float* __restrict__ frame_px) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * J) return;
+  const int b = e / J;
+  kpf_uncrop_joint(joints + 3 * e, center + 3 * b, M + 9 * b, cube + 3 * b, cam + 4 * b, crop_px + 3 * e, frame_px + 3 * e, mirror[b] ? (double)frame_w : -1.0);
+}
 #endif  // __HIPCC__
 
 constexpr size_t kCropFixedLds = 4 * PREP_NW * 8 + 256 + PREP_NW * 4;
+constexpr size_t kAnnotFixedLds = 800 + 256 + PREP_NW * 4;  // ANNOT_XYZ_BYTES + the geometry + the wave maxima
 inline int host_pow2ceil(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -523,6 +702,36 @@ extern "C" int kpf_prep_uncrop_f32(const float* joints, const float* center, con
   KPF_REQUIRE(B > 0 && J > 0 && (long)B * J < (1L << 30), "kpf_prep_uncrop_f32: bad shape (B %d, J %d)", B, J);
   hipLaunchKernelGGL(prep_uncrop_kernel, dim3((B * J + 255) / 256), dim3(256), 0, ST(stream), joints, center, M, cube, cam, B, J, crop_px, frame_px);
   return kpf_check_launch("kpf_prep_uncrop_f32");
+}
+
+extern "C" int kpf_prep_annot_u16(const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const float* joints_mm, const float* cam32,
+                                  const float* center_xyz, const unsigned char* mirror, const double* cube, int B, int J, int Hs, int Ws, int x0, int y0, int H,
+                                  int W, int S, float* img, float* img_rgb, float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds,
+                                  double* M64, float* joint, float* joint_img, double* cam64, void* stream) {
+  const char* name = "kpf_prep_annot_u16";
+  KPF_REQUIRE(rgb && depth && cam32 && mirror && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64 && joint && joint_img && cam64,
+              "%s: null pointer argument", name);
+  KPF_REQUIRE(joints_mm || center_xyz, "%s: neither joints nor a centre (nothing to crop around)", name);
+  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
+  KPF_REQUIRE(J > 0 && J <= 64, "%s: J = %d joints (one lane of a wave64 per joint: 1 .. 64)", name, J);
+  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
+  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
+  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
+  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
+  const size_t lds = kAnnotFixedLds + (size_t)S * S * 2;
+  hipLaunchKernelGGL(prep_annot_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, frame_index, F, joints_mm, cam32, center_xyz, mirror, cube, J, Hs, Ws, x0,
+                     y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64, joint, joint_img, cam64);
+  return kpf_check_launch(name);
+}
+
+extern "C" int kpf_prep_uncrop_mirror_f32(const float* joints, const float* center, const float* M, const float* cube, const float* cam, const unsigned char* mirror,
+                                          int frame_w, int B, int J, float* crop_px, float* frame_px, void* stream) {
+  KPF_REQUIRE(joints && center && M && cube && cam && mirror && crop_px && frame_px, "kpf_prep_uncrop_mirror_f32: null pointer argument");
+  KPF_REQUIRE(B > 0 && J > 0 && (long)B * J < (1L << 30), "kpf_prep_uncrop_mirror_f32: bad shape (B %d, J %d)", B, J);
+  KPF_REQUIRE(frame_w > 0, "kpf_prep_uncrop_mirror_f32: frame width %d", frame_w);
+  hipLaunchKernelGGL(prep_uncrop_mirror_kernel, dim3((B * J + 255) / 256), dim3(256), 0, ST(stream), joints, center, M, cube, cam, mirror, frame_w, B, J, crop_px,
+                     frame_px);
+  return kpf_check_launch("kpf_prep_uncrop_mirror_f32");
 }
 
 /* tuning aid: [B][8] 8-byte stamp slots in device memory for the next launches (NULL switches the stamps off) */

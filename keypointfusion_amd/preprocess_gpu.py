@@ -10,6 +10,13 @@ to the current stream.
     res, sws, _ = plan.forward(*[prep[k] for k in MODEL_INPUTS], 0.8, 128, 1)
     crop_px, frame_px = pre.uncrop(res[5], prep)                       # joints in crop pixels and in frame pixels
 
+By the dataset protocol (the reference's DexYCB / HO3D items at test time: the crop around an annotated 3-D centre, left hands mirrored, and the labels;
+`preprocess.prepare_annotated` is the yardstick, tests/test_prep_annot_gpu.py pins this path to it bit for bit):
+
+    prep = pre.prepare_annotated(rgb_u8, depth_u16, joints_mm, cam32, seed, mirror=left)   # [B][J][3] f32 mm, [B][4] f32, [B] int64, [B] uint8
+    evaluator.update(res, prep["img"], prep["joint"], prep["center"], prep["M"], prep["cube"], prep["cam_para"])   # xyz_gt = prep["joint"]
+    crop_px, frame_px = pre.uncrop(res[5], prep)                       # a mirrored sample's u comes back in the camera's own frame
+
 A frame may be uploaded as a window: `origin=(x0, y0), frame_size=(H, W)` says where the stored [Hs][Ws] image sits in the camera frame; pixels outside
 it read as zero.  The point sample is drawn from a counter hash of (seed[b], candidate) and is not numpy's RandomState stream: it has the same
 distribution (n candidates without replacement in random order; a cloud smaller than n tiled first), see kpf_prep_pcl_sample in include/kpf.h.
@@ -157,9 +164,119 @@ class DevicePreprocessor:
                       "kpf_prep_pcl_sample")
         return {k: v for k, v in o.items() if not k.startswith("_")}
 
+    # -- the dataset protocol
+    @staticmethod
+    def check_annotated(rgb, depth, joints_mm, cam, seed, mirror=None, center_xyz=None, origin=None, frame_size=None, frame_index=None):
+        """Validates one annotated batch and returns (B, J, Hs, Ws, x0, y0, H, W).  Raises TypeError / ValueError with the reason; touches no device."""
+        where = "DevicePreprocessor.prepare_annotated"
+        if joints_mm is None and center_xyz is None:
+            raise ValueError("%s: neither joints_mm nor center_xyz: nothing to crop around" % where)
+        named = [("rgb", rgb), ("depth", depth), ("cam", cam), ("seed", seed)] + [(k, v) for k, v in (
+            ("joints_mm", joints_mm), ("mirror", mirror), ("center_xyz", center_xyz), ("frame_index", frame_index)) if v is not None]
+        for name, t in named:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s: %s must be a torch tensor on the GPU (got %s)" % (where, name, type(t).__name__))
+        if depth.dtype != torch.uint16:
+            raise TypeError("%s: depth must be torch.uint16 millimetres (got %s): the z-clamp truncates the near plane to the sensor's type" % (where, depth.dtype))
+        if rgb.dtype != torch.uint8:
+            raise TypeError("%s: rgb must be torch.uint8 (got %s)" % (where, rgb.dtype))
+        if depth.dim() != 3 or min(depth.shape) < 1:
+            raise ValueError("%s: depth must be a non-empty [B][Hs][Ws] (got %s)" % (where, tuple(depth.shape)))
+        F, Hs, Ws = (int(v) for v in depth.shape)
+        if tuple(rgb.shape) != (F, Hs, Ws, 3):
+            raise ValueError("%s: rgb %s does not match depth %s (expected [B][Hs][Ws][3])" % (where, tuple(rgb.shape), tuple(depth.shape)))
+        B = F
+        if frame_index is not None:
+            if frame_index.dtype != torch.int32:
+                raise TypeError("%s: frame_index must be torch.int32 (got %s): build it with make_frame_index" % (where, frame_index.dtype))
+            if frame_index.dim() != 1 or frame_index.shape[0] < 1:
+                raise ValueError("%s: frame_index has shape %s, expected [B]" % (where, tuple(frame_index.shape)))
+            B = int(frame_index.shape[0])
+        J = 21
+        if joints_mm is not None:
+            if joints_mm.dim() != 3 or joints_mm.shape[0] != B or joints_mm.shape[2] != 3 or joints_mm.shape[1] < 1:
+                raise ValueError("%s: joints_mm has shape %s, expected (%d, J, 3)" % (where, tuple(joints_mm.shape), B))
+            J = int(joints_mm.shape[1])
+            if J > 64:
+                raise ValueError("%s: J = %d joints; at most 64 (one lane of a wave per joint)" % (where, J))
+        checks = [("cam", cam, (B, 4), torch.float32), ("seed", seed, (B,), torch.int64)]
+        checks += [("joints_mm", joints_mm, (B, J, 3), torch.float32)] if joints_mm is not None else []
+        checks += [("center_xyz", center_xyz, (B, 3), torch.float32)] if center_xyz is not None else []
+        checks += [("mirror", mirror, (B,), torch.uint8)] if mirror is not None else []
+        for name, t, shape, dt in checks:
+            if tuple(t.shape) != shape:
+                raise ValueError("%s: %s has shape %s, expected %s" % (where, name, tuple(t.shape), shape))
+            if t.dtype != dt:
+                raise TypeError("%s: %s must be %s (got %s)" % (where, name, dt, t.dtype))
+        if (origin is None) != (frame_size is None):
+            raise ValueError("%s: origin=(x0, y0) and frame_size=(H, W) go together" % where)
+        x0, y0 = (0, 0) if origin is None else (int(origin[0]), int(origin[1]))
+        H, W = (Hs, Ws) if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
+        if x0 < 0 or y0 < 0 or x0 + Ws > W or y0 + Hs > H:
+            raise ValueError("%s: the %d x %d window at (%d, %d) leaves the %d x %d frame" % (where, Ws, Hs, x0, y0, W, H))
+        return B, J, Hs, Ws, x0, y0, H, W
+
+    def _annot_buffers(self, dev, B, Hs, Ws, J):
+        key = (dev, B, Hs, Ws, "annot", J)
+        b = self._bufs.get(key)
+        if b is None:
+            S, n = self.img_size, self.sample_num
+            f32 = dict(device=dev, dtype=torch.float32)
+            b = dict(img_rgb=torch.zeros(B, 3, S, S, **f32), img=torch.zeros(B, 1, S, S, **f32), pcl=torch.zeros(B, n, 3, **f32), center=torch.zeros(B, 3, **f32),
+                     M=torch.zeros(B, 3, 3, **f32), cube=torch.zeros(B, 3, **f32), cam_para=torch.zeros(B, 4, **f32),
+                     pcl_index=torch.zeros(B, n, device=dev, dtype=torch.int32), pcl_count=torch.zeros(B, device=dev, dtype=torch.int32),
+                     com=torch.zeros(B, 3, device=dev, dtype=torch.float64), bounds=torch.zeros(B, 6, device=dev, dtype=torch.int32),
+                     M64=torch.zeros(B, 3, 3, device=dev, dtype=torch.float64), joint=torch.zeros(B, J, 3, **f32), joint_img=torch.zeros(B, J, 3, **f32),
+                     _cube64=torch.tensor([self.cube] * B, device=dev, dtype=torch.float64), _cam64=torch.zeros(B, 4, device=dev, dtype=torch.float64),
+                     _right=torch.zeros(B, device=dev, dtype=torch.uint8))
+            if self.debug_candidates:
+                b["candidates"] = torch.zeros(B, S * S, 3, **f32)
+            self._bufs[key] = b
+        return b
+
+    def prepare_annotated(self, rgb, depth, joints_mm, cam, seed, mirror=None, center_xyz=None, origin=None, frame_size=None, frame_index=None):
+        """The reference's dataset items at test time on the device (preprocess.prepare_annotated, bit for bit): the crop around an annotated 3-D centre, left
+        hands mirrored, and the labels.  rgb, depth, seed, origin / frame_size and frame_index as prepare(); joints_mm [B][J][3] float32 (camera space, mm,
+        the model's joint order; None with a given centre: no ground truth, the labels are zeros and J = 21), cam [B][4] float32 (fx, fy, u0, v0), mirror
+        None or [B] uint8 (non-zero: a left hand), center_xyz None (the mean of the joints) or [B][3] float32.  Two launches, no allocation.  Returns
+        prepare()'s dict plus joint [B][J][3] (normalised xyz: DeviceEvaluator.update's xyz_gt), joint_img [B][J][3] (normalised uvd), mirror ([B] uint8: the
+        tensor given, or zeros) and frame_w (int, the width the mirror acts on); uncrop() takes a mirrored sample's u back to the camera's frame."""
+        B, J, Hs, Ws, x0, y0, H, W = self.check_annotated(rgb, depth, joints_mm, cam, seed, mirror, center_xyz, origin, frame_size, frame_index)
+        dev = depth.device
+        for name, t in (("rgb", rgb), ("depth", depth), ("joints_mm", joints_mm), ("cam", cam), ("seed", seed), ("mirror", mirror), ("center_xyz", center_xyz),
+                        ("frame_index", frame_index)):
+            if t is None:
+                continue
+            if t.device.type != "cuda" or t.device != dev:
+                raise RuntimeError("DevicePreprocessor.prepare_annotated: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
+                                   "preprocess.prepare_annotated is the host path)" % (name, t.device))
+            if not t.is_contiguous():
+                raise ValueError("DevicePreprocessor.prepare_annotated: %s must be contiguous" % name)
+        l = lib.load()
+        o = self._annot_buffers(dev, B, Hs, Ws, J)
+        S, n = self.img_size, self.sample_num
+        mir = o["_right"] if mirror is None else mirror
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            lib.check(l.kpf_prep_annot_u16(rgb.data_ptr(), depth.data_ptr(), ptr(frame_index), int(depth.shape[0]), ptr(joints_mm), cam.data_ptr(), ptr(center_xyz),
+                                           mir.data_ptr(), o["_cube64"].data_ptr(), B, J, Hs, Ws, x0, y0, H, W, S, o["img"].data_ptr(), o["img_rgb"].data_ptr(),
+                                           o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(), o["cam_para"].data_ptr(), o["com"].data_ptr(),
+                                           o["bounds"].data_ptr(), o["M64"].data_ptr(), o["joint"].data_ptr(), o["joint_img"].data_ptr(), o["_cam64"].data_ptr(),
+                                           st), "kpf_prep_annot_u16")
+            cand = o["candidates"].data_ptr() if self.debug_candidates else None
+            lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["_cube64"].data_ptr(), o["_cam64"].data_ptr(),
+                                            seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
+                      "kpf_prep_pcl_sample")
+        out = {k: v for k, v in o.items() if not k.startswith("_")}
+        out.update(mirror=mir, frame_w=W)
+        return out
+
     def uncrop(self, joints_nl, prep):
         """joints_nl [B][J][3] float32 normalised to the cube (the model's xyz outputs) + a prepare() result (or any dict with center, M, cube, cam_para)
-        -> (crop_px [B][J][3]: u, v in crop pixels and d in mm; frame_px [B][J][3]: u, v in frame pixels and d in mm).  New tensors."""
+        -> (crop_px [B][J][3]: u, v in crop pixels and d in mm; frame_px [B][J][3]: u, v in frame pixels and d in mm).  New tensors.  A
+        prepare_annotated() result carries mirror and frame_w: a mirrored sample's frame u is frame_w - 1 - u, back in the camera's own frame (its depth and
+        the predicted xyz stay in the mirrored camera's space, as in the reference)."""
         if not isinstance(joints_nl, torch.Tensor) or joints_nl.dim() != 3 or joints_nl.shape[2] != 3 or joints_nl.dtype != torch.float32:
             raise ValueError("DevicePreprocessor.uncrop: joints must be a float32 tensor [B][J][3]")
         B, J = int(joints_nl.shape[0]), int(joints_nl.shape[1])
@@ -174,6 +291,15 @@ class DevicePreprocessor:
             par.append(t.contiguous())
         j = joints_nl.contiguous()
         crop_px, frame_px = torch.empty_like(j), torch.empty_like(j)
+        mirror = prep.get("mirror")
+        if mirror is not None:
+            if not isinstance(mirror, torch.Tensor) or tuple(mirror.shape) != (B,) or mirror.dtype != torch.uint8 or mirror.device != dev:
+                raise ValueError("DevicePreprocessor.uncrop: prep['mirror'] must be uint8 (%d,) on %s" % (B, dev))
+            with torch.cuda.device(dev):
+                lib.check(lib.load().kpf_prep_uncrop_mirror_f32(j.data_ptr(), *[t.data_ptr() for t in par], mirror.contiguous().data_ptr(), int(prep["frame_w"]),
+                                                                B, J, crop_px.data_ptr(), frame_px.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                          "kpf_prep_uncrop_mirror_f32")
+            return crop_px, frame_px
         with torch.cuda.device(dev):
             lib.check(lib.load().kpf_prep_uncrop_f32(j.data_ptr(), *[t.data_ptr() for t in par], B, J, crop_px.data_ptr(), frame_px.data_ptr(),
                                                      torch.cuda.current_stream(dev).cuda_stream), "kpf_prep_uncrop_f32")

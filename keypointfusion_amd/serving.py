@@ -126,6 +126,36 @@ class PipelinedEval:
             ticket = self.submit(prep["img_rgb"], prep["img"], prep["pcl"], loader, prep["center"], prep["M"], prep["cube"], prep["cam_para"], kernel)
         return ticket, keep
 
+    def submit_annotated(self, preprocessor, rgb, depth, joints_mm, cam, seed, mirror=None, center_xyz=None, loader=None, origin=None, frame_size=None,
+                         kernel=0.8):
+        """Frames and annotations in: `DevicePreprocessor.prepare_annotated` (the reference's dataset items at test time) on the slot's stream in front of the
+        slot's graph(s), then submit().  As submit_frames; prep also holds the labels joint (the evaluator's xyz_gt) and joint_img, and mirror / frame_w for
+        `preprocessor.uncrop(results[5], prep)`."""
+        from .preprocess_gpu import DevicePreprocessor
+        DevicePreprocessor.check_annotated(rgb, depth, joints_mm, cam, seed, mirror, center_xyz, origin, frame_size)
+        dev = depth.device
+        nstreams = 2 if self.stages else self.depth
+        if self._streams is None or self._streams[0].device != dev:  # (as submit() does)
+            self._streams = [torch.cuda.Stream(device=dev) for _ in range(nstreams)]
+            self._head_done = [None] * self.depth
+        if getattr(self, "_preps", None) is None or self._preps[0] is not preprocessor:
+            self._preps = (preprocessor, [DevicePreprocessor(preprocessor.img_size, preprocessor.sample_num, preprocessor.cube) for _ in range(self.depth)])
+        slot = self._next
+        st = self._streams[0] if self.stages else self._streams[slot]  # the stream the slot's (first) graph replays on
+        cur = torch.cuda.current_stream(dev)
+        st.wait_stream(cur)  # the frames and annotations were produced on the caller's stream
+        with torch.cuda.device(dev), torch.cuda.stream(st):
+            for t in (rgb, depth, joints_mm, cam, seed, mirror, center_xyz):
+                if t is not None:
+                    t.record_stream(st)
+            prep = self._preps[1][slot].prepare_annotated(rgb, depth, joints_mm, cam, seed, mirror, center_xyz, origin, frame_size)
+            keep = {k: prep[k].clone() for k in ("img", "center", "M", "cube", "cam_para", "joint", "joint_img", "mirror")}
+            for t in keep.values():
+                t.record_stream(cur)  # allocated on the slot's stream, consumed on the caller's
+            keep["frame_w"] = prep["frame_w"]
+            ticket = self.submit(prep["img_rgb"], prep["img"], prep["pcl"], loader, prep["center"], prep["M"], prep["cube"], prep["cam_para"], kernel)
+        return ticket, keep
+
     def collect(self, ticket):
         """(list of 6 results, list of 2 spatial weights, None) of a submitted batch, ordered after it on the caller's stream."""
         res, sws, ev, st = ticket

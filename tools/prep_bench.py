@@ -4,6 +4,8 @@ forward of the same build.  Prints one JSON line.
 
     python tools/prep_bench.py                      # everything
     python tools/prep_bench.py --device-only --reps 50   # only the three kpf_prep_* kernels (the form to run under rocprofv3 --kernel-trace --stats)
+    python tools/prep_bench.py --annotated          # only: prepare_annotated (the dataset protocol) beside prepare on the same B = 32 frames;
+                                                    # writes profiles/prep_annot_bench.json (--out: elsewhere)
 
 Times are host clocks around work that ends in a device synchronise (enqueue of `reps` batches, one synchronise), after a warm-up of every shape."""
 import argparse
@@ -59,12 +61,70 @@ def _timed(fn, reps, torch):
     return (time.perf_counter() - t0) / reps
 
 
+def annotated(args):
+    """prepare_annotated beside prepare: the frames of tests/annot_cases.py (mixed, a third of them left hands), each also given the box of its joints
+    (the rule of tracking.next_bbox's get_bbox, 1.5 x) for prepare, eagerly and replayed from a graph."""
+    import torch
+    import annot_cases as AC
+    from keypointfusion_amd import preprocess as P
+    from keypointfusion_amd.preprocess_gpu import DevicePreprocessor
+    dev = torch.device("cuda:0")
+    items = [AC.synth(AC.SMALL[i % len(AC.SMALL)], seed=1 + i) for i in range(B)]
+    bbox = []
+    for rgb, depth, joints_mm, cam, mirror, center in items:
+        uv = P._project_f32(joints_mm, cam)[:, :2].astype(np.float64)
+        lo, hi = uv.min(0), uv.max(0)
+        c, w = (lo + hi) / 2, (hi - lo) * 1.5
+        bbox.append([c[0] - w[0] / 2, c[1] - w[1] / 2, w[0], w[1]])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    rgb, depth = t(np.stack([i[0] for i in items])), t(np.stack([i[1] for i in items]))
+    joints, cam32 = t(np.stack([i[2] for i in items])), t(np.stack([i[3] for i in items]))
+    mirror = t(np.array([i[4] for i in items], np.uint8))
+    seed = torch.arange(B, dtype=torch.int64, device=dev)
+    box_in = (rgb, depth, t(np.array(bbox, np.float64)), cam32.double(), seed)
+    pre = DevicePreprocessor(cube=AC.CUBE)
+    rec = {"tool": "prep_bench --annotated", "B": B, "reps": args.reps, "frames": "640x480", "left_hands": int(mirror.sum())}
+    stream = torch.cuda.Stream(device=dev)
+    with torch.no_grad(), torch.cuda.stream(stream):
+        run_a = lambda: pre.prepare_annotated(rgb, depth, joints, cam32, seed, mirror=mirror)
+        run_b = lambda: pre.prepare(*box_in)
+        graphs = []
+        for fn in (run_b, run_a):
+            fn()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                fn()
+            graphs.append(graph)
+        # the two forms alternate, three rounds each, so that a drift of the box shows as spread and not as a difference
+        names = ("prepare_ms", "prepare_annotated_ms", "prepare_graph_ms", "prepare_annotated_graph_ms")
+        rounds = {k: [] for k in names}
+        for _ in range(3):
+            for k, fn in zip(names, (run_b, run_a, graphs[0].replay, graphs[1].replay)):
+                rounds[k].append(_timed(fn, args.reps, torch) * 1e3)
+        for k in names:
+            rec[k], rec[k + "_rounds"] = float(np.median(rounds[k])), rounds[k]
+        rec["pcl_count_mean_prepare"] = float(run_b()["pcl_count"].float().mean())
+        rec["pcl_count_mean_annotated"] = float(run_a()["pcl_count"].float().mean())
+    torch.cuda.synchronize()
+    rec["annotated_no_slower_than_prepare"] = bool(rec["prepare_annotated_graph_ms"] <= rec["prepare_graph_ms"])
+    line = json.dumps(rec)
+    print(line, flush=True)
+    out = args.out or os.path.join(ROOT, "profiles", "prep_annot_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--device-only", action="store_true", help="skip the host path and the model: only prepare() and uncrop() of the two input forms")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
+    ap.add_argument("--annotated", action="store_true", help="only: prepare_annotated beside prepare on the same frames; writes profiles/prep_annot_bench.json")
     args = ap.parse_args()
+    if args.annotated:
+        return annotated(args)
     rec = {"tool": "prep_bench", "B": B, "reps": args.reps}
     if not args.device_only:  # before the GPU is initialised: the pool forks
         single, pooled = host_times()
