@@ -428,6 +428,38 @@ int kpf_dwconv7_add_f32(const float* x, const float* w_dw, const float* b_dw, co
 long kpf_dwconv7_wgrad_ws_floats(int B, int H, int C);
 int kpf_dwconv7_wgrad(const float* dy, const float* x, float* dw, float* db, float* ws, long ws_floats, int B, int H, int W, int C,
                       kpf_wgrad_reduce_desc* reduce /* nullable */, void* stream);
+/* Which kernel the depthwise 7x7 entry points give a call (ABI 24; tests and tuning).  kpf_dwconv7_plan asks the launchers' own selection functions and makes no
+ * device call.  op: _LN kpf_dwconv7_ln_f32 / _split_f32 / _h16 (dtype KPF_DT_F32 | _BF16 | _F16; split != 0: the split output, fp32 storage and C % 32 == 0 only),
+ * _FWD kpf_dwconv7_f32 / _add_f32, _WGRAD kpf_dwconv7_wgrad (both fp32; split must be 0).  A shape the entry point refuses is refused here.  The tuning switches
+ * of the environment (KPF_DW_TILE, KPF_DW_UNFUSED, KPF_DW_WIDE, KPF_DW_WIDE_ROWS, KPF_DW_PX; KPF_DW7_PX, KPF_DW7_ROWS, KPF_DW7_MIN_BLOCKS; KPF_DW7_WGRAD_LDS,
+ * KPF_DW7_TARGET, KPF_DW7_MINROWS) are defaults of the selection, read once per process: the answer is the choice under them.
+ *   family   _TILE   dwconv7_ln_tile_kernel<nchk, px>: LDS halo tiles of `rows` x 4 px pixels, C = 32 nchk
+ *            _WAVE   dwconv7_ln_wave_kernel<lg>: a pixel's channel quads on an lg-lane group, strips of rows x px pixels, taps in LDS
+ *            _WIDE   dwconv7_ln_wide_kernel<nt, rows>: one workgroup of nt threads per strip of rows x px pixels, taps from global memory
+ *            _TWO_LAUNCH  dwconv7_kernel<taps_lds, px> (two rows), then the row LayerNorm in place; fp32 storage only (16-bit storage would round the
+ *                    un-normalised map between the launches: it takes _TINY on these shapes)
+ *            _TINY   dwconv7_ln_kernel: S strips of one row x px pixels per workgroup of nt threads, fp32 output tile in LDS
+ *            _CONV   dwconv7_kernel<taps_lds, px, rows> of _FWD
+ *            _WGRAD_LDS / _WGRAD_REG  dwconv7_wgrad_lds_kernel (cq channel quads per workgroup) / the register-window dwconv7_wgrad_kernel: S chunks of
+ *                    rows_per_chunk rows of the B * H; ws_floats = what this call needs (<= kpf_dwconv7_wgrad_ws_floats); raise_lds: the kernel needs the
+ *                    raised dynamic-LDS limit (> 64 KiB) — where the device refuses it, the call takes _WGRAD_REG with that kernel's own chunks
+ *   nt = threads of a workgroup, blocks = workgroups of the (first) launch, lds_bytes = its dynamic LDS; fields a family has no use for are 0. */
+#define KPF_DW7_OP_LN 0
+#define KPF_DW7_OP_FWD 1
+#define KPF_DW7_OP_WGRAD 2
+#define KPF_DW7_FAMILY_TILE 0
+#define KPF_DW7_FAMILY_WAVE 1
+#define KPF_DW7_FAMILY_WIDE 2
+#define KPF_DW7_FAMILY_TWO_LAUNCH 3
+#define KPF_DW7_FAMILY_TINY 4
+#define KPF_DW7_FAMILY_CONV 5
+#define KPF_DW7_FAMILY_WGRAD_LDS 6
+#define KPF_DW7_FAMILY_WGRAD_REG 7
+typedef struct kpf_dw7_plan {
+  int family, px, rows, taps_lds, lg, nt, nchk, cq, S, rows_per_chunk, raise_lds, reserved;
+  long blocks, lds_bytes, ws_floats;
+} kpf_dw7_plan;
+int kpf_dwconv7_plan(int op, int dtype, int split, int B, int H, int W, int C, kpf_dw7_plan* out);
 
 /*
  * BatchNorm with batch statistics (+ optional ReLU) on NHWC rows x [M][C], forward and backward: nn.BatchNorm2d / BatchNorm1d in
@@ -871,7 +903,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 23
+#define KPF_ABI_VERSION 24
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

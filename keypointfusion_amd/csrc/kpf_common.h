@@ -43,6 +43,10 @@ static inline bool kpf_raise_lds_limit(const void* kern, std::atomic<bool>* done
   return true;
 }
 
+// The selection of kpf_dwconv7_wgrad (csrc/kpf_wgrad.hip): its launcher and kpf_dwconv7_plan (csrc/kpf_elem.hip) both ask here.  No device call.  raise_refused:
+// the device refused the raised dynamic-LDS limit the first answer asked for (p->raise_lds).  grid_x (nullable): workgroups along x.
+void kpf_dw7_select_wgrad(int B, int H, int W, int C, bool raise_refused, kpf_dw7_plan* p, unsigned* grid_x);
+
 static inline bool kpf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // wave64 butterfly sum

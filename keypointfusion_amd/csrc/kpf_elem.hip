@@ -994,22 +994,90 @@ inline int grid_for(long total, int block = 256, int cap = 256 * 16) {
 template <typename TI, typename TO>
 static int layernorm_impl(const TI* x, const float* w, const float* b, TO* y, long rows, int C, float eps, void* stream, bool split);
 
+// ---- the one place that decides which kernel takes a kpf_dwconv7_ln_* call (dwconv7_ln_impl and kpf_dwconv7_plan ask here; no device call).  The tuning
+// switches of the environment are the defaults of the rules.  p: what include/kpf.h documents; xstrips / ypairs (tile: tiles_x / tiles_y; tiny: xblocks / -):
+// the grid's geometry under that choice.
+struct Dw7LnChoice {
+  kpf_dw7_plan p;
+  int xstrips, ypairs;
+};
+
+static Dw7LnChoice select_dw7_ln(int B, int H, int W, int C, bool f32, bool split) {
+  Dw7LnChoice c;
+  c.p = kpf_dw7_plan{};
+  c.xstrips = c.ypairs = 0;
+  const int C4 = C / 4;
+  static const int tile_env = []() { const char* e = getenv("KPF_DW_TILE"); return e ? atoi(e) : 1; }();  // tuning aid
+  if (tile_env && (C == 96 || C == 128 || C == 192) && H >= 16 && W >= 16) {
+    // LDS-tiled, fused: every input pixel crosses L2 -> L1 about twice instead of seven times
+    const int TX = C == 192 ? 16 : 32;
+    c.xstrips = (W + TX - 1) / TX, c.ypairs = (H + DT_TY - 1) / DT_TY;
+    c.p.family = KPF_DW7_FAMILY_TILE, c.p.nchk = C / 32, c.p.px = TX / 4, c.p.rows = DT_TY, c.p.taps_lds = 1, c.p.nt = 256;
+    c.p.blocks = (long)B * c.ypairs * c.xstrips;
+    return c;
+  }
+  if (H * W >= 64 && C4 <= 64 && (size_t)49 * C * sizeof(float) <= 64 * 1024 && !getenv("KPF_DW_UNFUSED")) {
+    // fused, one pass over the activation: channel quads of a pixel on one 32- or 64-lane group, LayerNorm by shuffles
+    c.xstrips = (W + 7) / 8, c.ypairs = (H + 1) / 2;
+    c.p.family = KPF_DW7_FAMILY_WAVE, c.p.lg = C4 <= 32 ? 32 : 64, c.p.px = 8, c.p.rows = 2, c.p.taps_lds = 1, c.p.nt = 256;
+    c.p.blocks = ((long)B * c.ypairs * c.xstrips * c.p.lg + 255) / 256;
+    c.p.lds_bytes = (long)49 * C * sizeof(float);
+    return c;
+  }
+  static const int wide_env = []() { const char* e = getenv("KPF_DW_WIDE"); return e ? atoi(e) : 1; }();  // tuning aid
+  if (wide_env && C4 > 64 && C4 <= 256 && H * W >= 16) {
+    c.xstrips = (W + 7) / 8;
+    // one-row strips while two-row strips would leave half the CUs without a workgroup (KPF_DW_WIDE_ROWS=1|2 forces a form: tuning aid)
+    static const int rows_env = []() { const char* e = getenv("KPF_DW_WIDE_ROWS"); return e ? atoi(e) : 0; }();
+    const bool one_row = rows_env ? rows_env == 1 : (long)B * ((H + 1) / 2) * c.xstrips < 256;
+    c.ypairs = one_row ? H : (H + 1) / 2;  // row groups
+    c.p.family = KPF_DW7_FAMILY_WIDE, c.p.nt = C4 <= 128 ? 128 : (C4 <= 192 ? 192 : 256), c.p.px = 8, c.p.rows = one_row ? 1 : 2;
+    c.p.blocks = (long)B * c.ypairs * c.xstrips;
+    return c;
+  }
+  if (f32 && (H * W >= 64 || split)) {
+    // two launches: register-tiled depthwise conv, then the row LayerNorm in place (each streams the tensor once; measured faster
+    // than the single fused kernel, whose LDS output tile caps occupancy).  Tiny maps keep the fused kernel (one launch).  fp32 storage only: between the
+    // launches the un-normalised map would be rounded to 16 bits, and the LayerNorm of a rounded map is off by |conv| * eps / sigma, far above the
+    // rounding of its own output wherever |mean| is not small against sigma; 16-bit storage takes the fused kernel below, which keeps fp32 up to the store.
+    static const int px_env = []() { const char* e = getenv("KPF_DW_PX"); return e ? atoi(e) : 8; }();  // tuning aid
+    const int PXr = px_env == 4 ? 4 : 8;
+    c.xstrips = (W + PXr - 1) / PXr, c.ypairs = (H + 1) / 2;
+    const size_t wbytes = (size_t)49 * C * sizeof(float);
+    c.p.family = KPF_DW7_FAMILY_TWO_LAUNCH, c.p.px = PXr, c.p.rows = 2, c.p.taps_lds = wbytes <= 48 * 1024, c.p.nt = 256;
+    c.p.blocks = ((long)B * c.ypairs * c.xstrips * C4 + 255) / 256;
+    c.p.lds_bytes = c.p.taps_lds ? (long)wbytes : 0;
+    return c;
+  }
+  int S = 1;
+  while (S * 2 * C4 <= 256 && S * DW_T < W) S *= 2;  // strips per block: <= 256 threads, no wider than the row
+  c.xstrips = (W + S * DW_T - 1) / (S * DW_T);  // (blocks along a row)
+  c.p.family = KPF_DW7_FAMILY_TINY, c.p.S = S, c.p.px = DW_T, c.p.rows = 1, c.p.nt = ((S * C4 + 63) / 64) * 64;
+  c.p.blocks = (long)B * H * c.xstrips;
+  c.p.lds_bytes = (long)S * DW_T * C * sizeof(float);
+  return c;
+}
+
+static int dwconv7_ln_shape_ok(int B, int H, int W, int C, bool f32, bool split) {
+  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && C <= 2048, "kpf_dwconv7_ln: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
+  KPF_REQUIRE(!split || (f32 && C % 32 == 0), "kpf_dwconv7_ln_split_f32: C=%d must be a multiple of 32 (fp32 storage)", C);
+  return KPF_OK;
+}
+
 template <typename TA>
 static int dwconv7_ln_impl(const TA* x, const float* w_dw, const float* b_dw, const float* ln_w, const float* ln_b, TA* y, int B, int H,
                            int W, int C, float eps, void* stream, bool split) {
   constexpr bool F32 = sizeof(TA) == 4;  // (the split operand format exists for fp32 storage only)
   KPF_REQUIRE(x && w_dw && b_dw && ln_w && ln_b && y, "kpf_dwconv7_ln: null pointer");
-  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && C <= 2048, "kpf_dwconv7_ln: bad shape B=%d H=%d W=%d C=%d", B, H, W, C);
+  if (int rc = dwconv7_ln_shape_ok(B, H, W, C, F32, split)) return rc;
   KPF_REQUIRE(kpf_aligned16(x) && kpf_aligned16(y) && kpf_aligned16(w_dw), "kpf_dwconv7_ln: unaligned pointer");
-  KPF_REQUIRE(!split || (F32 && C % 32 == 0), "kpf_dwconv7_ln_split_f32: C=%d must be a multiple of 32 (fp32 storage)", C);
-  const int C4 = C / 4;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  static const int tile_env = []() { const char* e = getenv("KPF_DW_TILE"); return e ? atoi(e) : 1; }();  // tuning aid
-  if (tile_env && (C == 96 || C == 128 || C == 192) && H >= 16 && W >= 16) {
-    // LDS-tiled, fused: every input pixel crosses L2 -> L1 about twice instead of seven times
-    const int TX = C == 192 ? 16 : 32;
-    const int tiles_x = (W + TX - 1) / TX, tiles_y = (H + DT_TY - 1) / DT_TY;
-    const dim3 grid((unsigned)((long)B * tiles_y * tiles_x));
+  const Dw7LnChoice ch = select_dw7_ln(B, H, W, C, F32, split);
+  const kpf_dw7_plan& p = ch.p;
+  const int xstrips = ch.xstrips, ypairs = ch.ypairs;
+  const dim3 grid((unsigned)p.blocks);
+  if (p.family == KPF_DW7_FAMILY_TILE) {
+    const int tiles_x = xstrips, tiles_y = ypairs;
 #define KPF_DWT(NCHK, PXS)                                                                                                                     \
   do {                                                                                                                                         \
     if constexpr (F32) {                                                                                                                       \
@@ -1022,21 +1090,16 @@ static int dwconv7_ln_impl(const TA* x, const float* w_dw, const float* b_dw, co
     hipLaunchKernelGGL((dwconv7_ln_tile_kernel<TA, NCHK, PXS, false>), grid, dim3(256), 0, st, x, w_dw, b_dw, ln_w, ln_b, y, B, H, W, tiles_x, \
                        tiles_y, eps);                                                                                                          \
   } while (0)
-    if (C == 96) KPF_DWT(3, 8);
-    else if (C == 128) KPF_DWT(4, 8);
+    if (p.nchk == 3) KPF_DWT(3, 8);
+    else if (p.nchk == 4) KPF_DWT(4, 8);
     else KPF_DWT(6, 4);
 #undef KPF_DWT
     return kpf_check_launch("kpf_dwconv7_ln");
   }
-  if (H * W >= 64 && C4 <= 64 && (size_t)49 * C * sizeof(float) <= 64 * 1024 && !getenv("KPF_DW_UNFUSED")) {
-    // fused, one pass over the activation: channel quads of a pixel on one 32- or 64-lane group, LayerNorm by shuffles
-    const int xstrips = (W + 7) / 8, ypairs = (H + 1) / 2;
-    const long groups = (long)B * ypairs * xstrips;
-    const size_t wbytes = (size_t)49 * C * sizeof(float);
+  if (p.family == KPF_DW7_FAMILY_WAVE) {
+    const size_t wbytes = (size_t)p.lds_bytes;
 #define KPF_DWW(LG)                                                                                                                            \
   do {                                                                                                                                         \
-    const long threads = groups * LG;                                                                                                          \
-    const dim3 grid((unsigned)((threads + 255) / 256));                                                                                        \
     if constexpr (F32) {                                                                                                                       \
       if (split) {                                                                                                                             \
         hipLaunchKernelGGL((dwconv7_ln_wave_kernel<TA, LG, true>), grid, dim3(256), wbytes, st, x, w_dw, b_dw, ln_w, ln_b, y, B, H, W, C,      \
@@ -1047,19 +1110,13 @@ static int dwconv7_ln_impl(const TA* x, const float* w_dw, const float* b_dw, co
     hipLaunchKernelGGL((dwconv7_ln_wave_kernel<TA, LG, false>), grid, dim3(256), wbytes, st, x, w_dw, b_dw, ln_w, ln_b, y, B, H, W, C,         \
                        xstrips, ypairs, eps);                                                                                                  \
   } while (0)
-    if (C4 <= 32) KPF_DWW(32);
+    if (p.lg == 32) KPF_DWW(32);
     else KPF_DWW(64);
 #undef KPF_DWW
     return kpf_check_launch("kpf_dwconv7_ln");
   }
-  static const int wide_env = []() { const char* e = getenv("KPF_DW_WIDE"); return e ? atoi(e) : 1; }();  // tuning aid
-  if (wide_env && C4 > 64 && C4 <= 256 && H * W >= 16) {
-    const int xstrips = (W + 7) / 8;
-    // one-row strips while two-row strips would leave half the CUs without a workgroup (KPF_DW_WIDE_ROWS=1|2 forces a form: tuning aid)
-    static const int rows_env = []() { const char* e = getenv("KPF_DW_WIDE_ROWS"); return e ? atoi(e) : 0; }();
-    const bool one_row = rows_env ? rows_env == 1 : (long)B * ((H + 1) / 2) * xstrips < 256;
-    const int ypairs = one_row ? H : (H + 1) / 2;  // row groups
-    const dim3 grid((unsigned)((long)B * ypairs * xstrips));
+  if (p.family == KPF_DW7_FAMILY_WIDE) {
+    const bool one_row = p.rows == 1;
 #define KPF_DWX2(NT, ROWS)                                                                                                                     \
   do {                                                                                                                                         \
     if constexpr (F32) {                                                                                                                       \
@@ -1077,52 +1134,33 @@ static int dwconv7_ln_impl(const TA* x, const float* w_dw, const float* b_dw, co
     if (one_row) KPF_DWX2(NT, 1);                                                                                                              \
     else KPF_DWX2(NT, 2);                                                                                                                      \
   } while (0)
-    if (C4 <= 128) KPF_DWX(128);
-    else if (C4 <= 192) KPF_DWX(192);
+    if (p.nt == 128) KPF_DWX(128);
+    else if (p.nt == 192) KPF_DWX(192);
     else KPF_DWX(256);
 #undef KPF_DWX2
 #undef KPF_DWX
     return kpf_check_launch("kpf_dwconv7_ln");
   }
-  if (H * W >= 64 || split) {
-    // two launches: register-tiled depthwise conv, then the row LayerNorm in place (each streams the tensor once; measured faster
-    // than the single fused kernel, whose LDS output tile caps occupancy).  Tiny maps keep the fused kernel (one launch).
-    static const int px_env = []() { const char* e = getenv("KPF_DW_PX"); return e ? atoi(e) : 8; }();  // tuning aid
-    const int PXr = px_env == 4 ? 4 : 8;
-    const int xstrips = (W + PXr - 1) / PXr, ypairs = (H + 1) / 2;
-    const long total = (long)B * ypairs * xstrips * C4;
-    const size_t wbytes = (size_t)49 * C * sizeof(float);
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (wbytes <= 48 * 1024) {
-      if (PXr == 4) hipLaunchKernelGGL((dwconv7_kernel<TA, true, 4>), grid, dim3(256), wbytes, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs);
+  if (p.family == KPF_DW7_FAMILY_TWO_LAUNCH) {
+    const size_t wbytes = (size_t)p.lds_bytes;
+    if (p.taps_lds) {
+      if (p.px == 4) hipLaunchKernelGGL((dwconv7_kernel<TA, true, 4>), grid, dim3(256), wbytes, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs);
       else hipLaunchKernelGGL((dwconv7_kernel<TA, true, 8>), grid, dim3(256), wbytes, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs);
     } else {
-      if (PXr == 4) hipLaunchKernelGGL((dwconv7_kernel<TA, false, 4>), grid, dim3(256), 0, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs);
+      if (p.px == 4) hipLaunchKernelGGL((dwconv7_kernel<TA, false, 4>), grid, dim3(256), 0, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs);
       else hipLaunchKernelGGL((dwconv7_kernel<TA, false, 8>), grid, dim3(256), 0, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs);
     }
     int rc = kpf_check_launch("kpf_dwconv7_ln");
     if (rc) return rc;
     return layernorm_impl<TA, TA>(y, ln_w, ln_b, y, (long)B * H * W, C, eps, stream, split);
   }
-  int S = 1;
-  while (S * 2 * C4 <= 256 && S * DW_T < W) S *= 2;  // strips per block: <= 256 threads, no wider than the row
-  const int threads = ((S * C4 + 63) / 64) * 64;
-  KPF_REQUIRE(threads <= 512, "kpf_dwconv7_ln: C too large");
-  const int xblocks = (W + S * DW_T - 1) / (S * DW_T);
-  const size_t lds = (size_t)S * DW_T * C * sizeof(float);
-  hipLaunchKernelGGL(dwconv7_ln_kernel<TA>, dim3((unsigned)((long)B * H * xblocks)), dim3(threads), lds, st, x, w_dw, b_dw, ln_w, ln_b, y, H, W, C,
-                     S, xblocks, eps);
+  KPF_REQUIRE(p.nt <= 512, "kpf_dwconv7_ln: C too large");
+  hipLaunchKernelGGL(dwconv7_ln_kernel<TA>, grid, dim3(p.nt), (size_t)p.lds_bytes, st, x, w_dw, b_dw, ln_w, ln_b, y, H, W, C, p.S, xstrips, eps);
   return kpf_check_launch("kpf_dwconv7_ln");
 }
 
-// depthwise 7x7 + bias alone (training: forward of the ConvNeXt block's dwconv with the pre-norm activation kept for backward, and
-// its data gradient = the same convolution of dY with the taps mirrored)
-static int dwconv7_impl(const float* x, const float* w_dw, const float* b_dw, const float* addend, float* y, int B, int H, int W, int C, void* stream) {
-  KPF_REQUIRE(x && w_dw && b_dw && y && x != y, "kpf_dwconv7_f32: null pointer or in-place call");
-  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "kpf_dwconv7_f32: bad shape (C %% 4 == 0)");
-  KPF_REQUIRE(kpf_aligned16(x) && kpf_aligned16(y) && kpf_aligned16(w_dw) && kpf_aligned16(b_dw) && kpf_aligned16(addend),
-              "kpf_dwconv7_f32: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
+// ---- the one place that decides which form of dwconv7_kernel takes a kpf_dwconv7_f32 / _add_f32 call (dwconv7_impl and kpf_dwconv7_plan ask here; no device call)
+static kpf_dw7_plan select_dw7_conv(int B, int H, int W, int C) {
   // work per thread: 2 rows x 8 pixels while that fills the chip (>= KPF_DW7_MIN_BLOCKS workgroups), else 4 pixels, else 1 row x 4 pixels — the 16 x 16 ... 4 x 4
   // maps of a training iteration are 96 - 192 workgroups in the widest form (tuning aids: KPF_DW7_PX = 8 | 4, KPF_DW7_ROWS = 2 | 1 force a form)
   static const int px_env = []() { const char* e = getenv("KPF_DW7_PX"); return e ? atoi(e) : 0; }();
@@ -1134,11 +1172,28 @@ static int dwconv7_impl(const float* x, const float* w_dw, const float* b_dw, co
   if (blocks(px, 2) < min_blocks) rows = 1;
   if (px_env == 4 || px_env == 8) px = px_env;
   if (rows_env == 1 || rows_env == 2) rows = rows_env;
-  const int xstrips = (W + px - 1) / px, ypairs = (H + rows - 1) / rows;
-  const long total = (long)B * ypairs * xstrips * (C / 4);
   const size_t wbytes = (size_t)49 * C * sizeof(float);
-  const dim3 grid((unsigned)((total + 255) / 256));
-  const bool wl = wbytes <= 48 * 1024;
+  kpf_dw7_plan p = kpf_dw7_plan{};
+  p.family = KPF_DW7_FAMILY_CONV, p.px = px, p.rows = rows, p.taps_lds = wbytes <= 48 * 1024, p.nt = 256;
+  p.blocks = blocks(px, rows);
+  p.lds_bytes = p.taps_lds ? (long)wbytes : 0;
+  return p;
+}
+
+// depthwise 7x7 + bias alone (training: forward of the ConvNeXt block's dwconv with the pre-norm activation kept for backward, and
+// its data gradient = the same convolution of dY with the taps mirrored)
+static int dwconv7_impl(const float* x, const float* w_dw, const float* b_dw, const float* addend, float* y, int B, int H, int W, int C, void* stream) {
+  KPF_REQUIRE(x && w_dw && b_dw && y && x != y, "kpf_dwconv7_f32: null pointer or in-place call");
+  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "kpf_dwconv7_f32: bad shape (C %% 4 == 0)");
+  KPF_REQUIRE(kpf_aligned16(x) && kpf_aligned16(y) && kpf_aligned16(w_dw) && kpf_aligned16(b_dw) && kpf_aligned16(addend),
+              "kpf_dwconv7_f32: pointers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const kpf_dw7_plan p = select_dw7_conv(B, H, W, C);
+  const int px = p.px, rows = p.rows;
+  const int xstrips = (W + px - 1) / px, ypairs = (H + rows - 1) / rows;
+  const size_t wbytes = (size_t)p.lds_bytes;
+  const dim3 grid((unsigned)p.blocks);
+  const bool wl = p.taps_lds;
 #define KPF_DW7(WL, PXV, R2V) hipLaunchKernelGGL((dwconv7_kernel<float, WL, PXV, R2V>), grid, dim3(256), WL ? wbytes : 0, st, x, w_dw, b_dw, y, B, H, W, C, xstrips, ypairs, addend)
   if (wl) {
     if (px == 8) { if (rows == 2) KPF_DW7(true, 8, true); else KPF_DW7(true, 8, false); }
@@ -1158,6 +1213,25 @@ extern "C" int kpf_dwconv7_f32(const float* x, const float* w_dw, const float* b
 extern "C" int kpf_dwconv7_add_f32(const float* x, const float* w_dw, const float* b_dw, const float* addend, float* y, int B, int H, int W, int C, void* stream) {
   KPF_REQUIRE(addend && addend != y, "kpf_dwconv7_add_f32: addend missing or aliasing the output");
   return dwconv7_impl(x, w_dw, b_dw, addend, y, B, H, W, C, stream);
+}
+
+extern "C" int kpf_dwconv7_plan(int op, int dtype, int split, int B, int H, int W, int C, kpf_dw7_plan* out) {
+  KPF_REQUIRE(out, "kpf_dwconv7_plan: null pointer");
+  KPF_REQUIRE(op == KPF_DW7_OP_LN || op == KPF_DW7_OP_FWD || op == KPF_DW7_OP_WGRAD, "kpf_dwconv7_plan: unknown op %d", op);
+  if (op == KPF_DW7_OP_LN) {
+    KPF_REQUIRE(dtype == KPF_DT_F32 || dtype == KPF_DT_BF16 || dtype == KPF_DT_F16, "kpf_dwconv7_plan: unknown dtype %d", dtype);
+    if (int rc = dwconv7_ln_shape_ok(B, H, W, C, dtype == KPF_DT_F32, split != 0)) return rc;
+    *out = select_dw7_ln(B, H, W, C, dtype == KPF_DT_F32, split != 0).p;
+    KPF_REQUIRE(out->nt <= 512, "kpf_dwconv7_ln: C too large");
+    return KPF_OK;
+  }
+  KPF_REQUIRE(dtype == KPF_DT_F32 && !split, "kpf_dwconv7_plan: the training kernels take fp32 operands and have no split output");
+  KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "kpf_dwconv7_plan: bad shape (C %% 4 == 0)");
+  if (op == KPF_DW7_OP_FWD)
+    *out = select_dw7_conv(B, H, W, C);
+  else
+    kpf_dw7_select_wgrad(B, H, W, C, false, out, nullptr);
+  return KPF_OK;
 }
 
 extern "C" int kpf_dwconv7_ln_f32(const float* x, const float* w_dw, const float* b_dw, const float* ln_w, const float* ln_b,

@@ -1305,6 +1305,24 @@ int dw_chunk_rows(int B, int H, int C) {
 
 }  // namespace
 
+// ---- the one place that decides which kernel takes a kpf_dwconv7_wgrad call and how the rows are chunked (dwconv7_wgrad_impl and kpf_dwconv7_plan ask here)
+void kpf_dw7_select_wgrad(int B, int H, int W, int C, bool raise_refused, kpf_dw7_plan* p, unsigned* grid_x) {
+  static const int lds_form = []() { const char* e = getenv("KPF_DW7_WGRAD_LDS"); return e ? atoi(e) : 1; }();  // tuning aid: 0 = the register-window kernel
+  const DwlGeom gm = dwl_geom(W, C);
+  const bool use_lds = lds_form && gm.CQ >= 1 && (size_t)gm.lds_f4 * 16 <= 80 * 1024 && W * gm.CQ <= 512 && !raise_refused;  // (80 KB: two workgroups per CU)
+  const int rpc = use_lds ? dwl_chunk_rows(B, H, C) : dw_chunk_rows(B, H, C);
+  *p = kpf_dw7_plan{};
+  p->family = use_lds ? KPF_DW7_FAMILY_WGRAD_LDS : KPF_DW7_FAMILY_WGRAD_REG;
+  p->cq = use_lds ? gm.CQ : 0, p->nt = 256;
+  p->rows_per_chunk = rpc, p->S = (int)(((long)B * H + rpc - 1) / rpc);
+  p->lds_bytes = use_lds ? (long)gm.lds_f4 * 16 : 0;
+  p->raise_lds = use_lds && p->lds_bytes > 64 * 1024;
+  p->ws_floats = (long)p->S * 50 * C;
+  const unsigned gx = use_lds ? ((C >> 2) + gm.CQ - 1) / gm.CQ : (7 * (C / 4) + 255) / 256;
+  p->blocks = (long)gx * p->S;
+  if (grid_x) *grid_x = gx;
+}
+
 extern "C" {
 
 long kpf_conv2d_wgrad_ws_floats(long M, int N, int K) {
@@ -1500,22 +1518,21 @@ static int dwconv7_wgrad_impl(const float* dy, const float* x, float* dw, float*
   KPF_REQUIRE(dy && x && dw && ws, "kpf_dwconv7_wgrad: null pointer");
   KPF_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "kpf_dwconv7_wgrad: bad shape (C %% 4 == 0)");
   KPF_REQUIRE(kpf_aligned16(dy) && kpf_aligned16(x) && kpf_aligned16(ws), "kpf_dwconv7_wgrad: dy, x, ws must be 16-byte aligned");
-  static const int lds_form = []() { const char* e = getenv("KPF_DW7_WGRAD_LDS"); return e ? atoi(e) : 1; }();  // tuning aid: 0 = the register-window kernel
-  const DwlGeom gm = dwl_geom(W, C);
-  bool use_lds = lds_form && gm.CQ >= 1 && (size_t)gm.lds_f4 * 16 <= 80 * 1024 && W * gm.CQ <= 512;  // (80 KB: two workgroups per CU)
-  if (use_lds && (size_t)gm.lds_f4 * 16 > 64 * 1024) {  // the 32-quad channel blocks of the 8 x 8 and 4 x 4 maps: 66.5 KB
+  kpf_dw7_plan p;
+  unsigned gx;
+  kpf_dw7_select_wgrad(B, H, W, C, false, &p, &gx);
+  if (p.raise_lds) {  // the 32-quad channel blocks of the 8 x 8 and 4 x 4 maps: 66.5 KB
     static std::atomic<bool> lds_ok[KPF_MAX_DEVICES];
-    use_lds = kpf_raise_lds_limit(reinterpret_cast<const void*>(&dwconv7_wgrad_lds_kernel), lds_ok);
+    if (!kpf_raise_lds_limit(reinterpret_cast<const void*>(&dwconv7_wgrad_lds_kernel), lds_ok)) kpf_dw7_select_wgrad(B, H, W, C, true, &p, &gx);
   }
-  const int rpc = use_lds ? dwl_chunk_rows(B, H, C) : dw_chunk_rows(B, H, C);
-  const int S = (int)(((long)B * H + rpc - 1) / rpc);
-  KPF_REQUIRE(ws_floats >= (long)S * 50 * C, "kpf_dwconv7_wgrad: workspace too small");
+  const int rpc = p.rows_per_chunk, S = p.S;
+  KPF_REQUIRE(ws_floats >= p.ws_floats, "kpf_dwconv7_wgrad: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   float* dbpart = ws + (size_t)S * 49 * C;
-  if (use_lds)
-    hipLaunchKernelGGL(dwconv7_wgrad_lds_kernel, dim3(((C >> 2) + gm.CQ - 1) / gm.CQ, S), dim3(256), (size_t)gm.lds_f4 * 16, st, dy, x, ws, dbpart, B, H, W, C, rpc);
+  if (p.family == KPF_DW7_FAMILY_WGRAD_LDS)
+    hipLaunchKernelGGL(dwconv7_wgrad_lds_kernel, dim3(gx, S), dim3(256), (size_t)p.lds_bytes, st, dy, x, ws, dbpart, B, H, W, C, rpc);
   else
-    hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3((7 * (C / 4) + 255) / 256, S), dim3(256), 0, st, dy, x, ws, dbpart, B, H, W, C, rpc);
+    hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3(gx, S), dim3(256), 0, st, dy, x, ws, dbpart, B, H, W, C, rpc);
   int rc = kpf_check_launch("kpf_dwconv7_wgrad");
   if (rc != KPF_OK) return rc;
   const int nkb = reduce_blocks(49L * C, S), ndb = db ? reduce_blocks(C, S) : 0;

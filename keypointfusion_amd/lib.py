@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 23  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 24  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -62,6 +62,15 @@ class WgradPlan(C.Structure):  # kpf_wgrad_plan (include/kpf.h)
 
 KPF_WGRAD_FAMILY = ("f32", "r16", "direct", "h16s", "h16")  # KPF_WGRAD_FAMILY_* by value
 KPF_WGRAD_FORM = {"f32_2x2": 1, "f32_2x4": 2, "f32_4x2": 3, "f32_4x4": 4, "h16s": 5, "h16": 6}  # KPF_WGRAD_FORM_* (kpf_conv2d_wgrad_force_form; 0 = cost model)
+
+
+class Dw7Plan(C.Structure):  # kpf_dw7_plan (include/kpf.h)
+    _fields_ = [(n, C.c_int) for n in "family px rows taps_lds lg nt nchk cq S rows_per_chunk raise_lds reserved".split()] + [
+        (n, C.c_long) for n in "blocks lds_bytes ws_floats".split()]
+
+
+KPF_DW7_OP = {"ln": 0, "fwd": 1, "wgrad": 2}  # KPF_DW7_OP_*
+KPF_DW7_FAMILY = ("tile", "wave", "wide", "two_launch", "tiny", "conv", "wgrad_lds", "wgrad_reg")  # KPF_DW7_FAMILY_* by value
 
 _P = C.c_void_p
 _SIGS = {
@@ -126,6 +135,7 @@ _SIGS = {
     "kpf_dwconv7_wgrad": [_P] * 5 + [C.c_long] + [C.c_int] * 4 + [C.POINTER(WgradReduceDesc), _P],
     "kpf_wgrad_reduce_multi": [C.POINTER(WgradReduceDesc), C.c_int, _P],
     "kpf_conv2d_wgrad_plan": [C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WgradPlan)],
+    "kpf_dwconv7_plan": [C.c_int] * 7 + [C.POINTER(Dw7Plan)],
     "kpf_conv2d_wgrad_force_form": [C.c_int],
     "kpf_row_gather_cols_f32": [_P, C.c_long, C.c_long, C.c_long, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_bn_ssr_forward": [_P] * 7 + [C.c_float, C.c_float, _P, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, _P],

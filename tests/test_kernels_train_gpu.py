@@ -71,8 +71,9 @@ def test_conv_wgrad_large_pixel_count():
 @pytest.mark.parametrize("shape", [(2, 32, 32, 96), (3, 16, 16, 192), (2, 8, 8, 384), (2, 4, 4, 768), (1, 5, 11, 8), (8, 32, 32, 192), (2, 64, 64, 96), (3, 7, 20, 36),
                                    (1, 3, 70, 12), (5, 9, 24, 100), (1, 2, 150, 8)])
 def test_dwconv7_forward_backward_match_torch(shape):
-    # (the weight gradient: the LDS-staged kernel for maps up to ~144 columns — every width class of its 8-column segments and channel-block sizes, chunks that
-    #  start inside an image — and the register-window kernel beyond)
+    # (the weight gradient: the LDS-staged kernel — every width class of its 8-column segments and channel-block sizes, chunks that start inside an image.  All
+    #  eleven shapes take it, 150 columns included: the register-window kernel starts at 289 columns.  Forward and data gradient: every shape is below the 768
+    #  workgroups of the wider forms and runs dwconv7_kernel<PX = 4, one row>.  The other forms of both: test_dw7_forms_gpu.py)
     from keypointfusion_amd.training import dwconv7_nhwc
     B, H, W, Cc = shape
     g = torch.Generator().manual_seed(B * H + Cc)
