@@ -898,12 +898,46 @@ int kpf_prep_annot_u16(const unsigned char* rgb, const unsigned short* depth, co
 int kpf_prep_uncrop_mirror_f32(const float* joints, const float* center, const float* M, const float* cube, const float* cam, const unsigned char* mirror,
                                int frame_w, int B, int J, float* crop_px, float* frame_px, void* stream);
 
+/* Training augmentation by the dataset protocol (ABI 25): keypointfusion_amd/preprocess.py::prepare_augmented, the reference's TRAINING item
+ * (dataloader/loader.py:1140-1156 DexYCB, :1325-1347 HO3D; augmentCrop / augmentCrop_RGB, moveCoM, rotateHand, scaleHand, recropHand, normalize_img).
+ *
+ * kpf_prep_augment_u16: every argument of kpf_prep_annot_u16 with its meaning, plus per-sample device arrays: mode [B] int (0 rot, 1 com, 2 sc, 3 none:
+ * the reference's aug_modes order; any other value is prepared as none), off [B][3] double mm, sc [B] double, rot [B] double degrees, rot_cs [B][2] double =
+ * (cos, sin) of fmod(rot, 360) * pi / 180 as the CALLER computed them (no trigonometric function is called here), color [B][3] double or NULL (HO3D's colour
+ * scale: clip(value * color, 0, 255) in double before the rounding to float and the / 255).  One workgroup of 1024 threads per sample, grid = B, no
+ * allocation, no atomics.  The base crop is kpf_prep_annot_u16's (z-clamped uint16 values in LDS, premax = their maximum); one lane then computes the augmented
+ * geometry in double in the host's operation order, one lane per joint the labels, and every thread its destination pixels through the inverse map:
+ *   perspective (com, sc): A = Mnew . inv(M), Ai = adj(A) / det(A); W = Ai20 x + Ai21 y + Ai22, W = W != 0 ? 1 / W : 0; X = rint((Ai00 x + (Ai01 y + Ai02)) W),
+ *     Y likewise (half to even); affine (rot): the closed-form inverse of getRotationMatrix2D((S/2, S/2), -rot) in OpenCV's 10-bit fixed point: X = (rint((Ai01
+ *     y + Ai02) 1024) + 512 + rint(Ai00 x 1024)) >> 10, Y likewise; a source outside [0, S) is the border 0.  (The project's own rule, restated from OpenCV's
+ *     nearest-neighbour warps and unpinned against a real OpenCV.)
+ * Depth reads the LDS crop, then recropHand's z-threshold in float, normalize_img with the PRE-augmentation maximum and the new centre / cube; RGB reads the
+ * frame at the crop pixel's source.  An all-zero depth crop (premax = 0) leaves depth, labels and geometry unaugmented; RGB is warped all the same.
+ * -> kpf_prep_annot_u16's outputs (bounds: those of the BASE crop) with center, M, M64, cube_out, com and the labels of the training item, plus cube64 [B][3]
+ * double (the cube the sample was normalised with: kpf_prep_pcl_sample takes it in place of cube) and aug_status [B] int: bit 0 = the depth side was
+ * augmented, bit 1 = REFUSED parameters (a non-finite off / rot / rot_cs / sc / color, sc <= 0, an offset that takes the centre to where it does not project, a
+ * singular map, or new bounds that are degenerate or saturated): the sample is
+ * prepared as mode none.  No index is formed from a NaN: every float-to-int conversion saturates and every index is range-tested. */
+int kpf_prep_augment_u16(const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const float* joints_mm, const float* cam32,
+                         const float* center_xyz, const unsigned char* mirror, const double* cube, const int* mode, const double* off, const double* sc,
+                         const double* rot, const double* rot_cs, const double* color, int B, int J, int Hs, int Ws, int x0, int y0, int H, int W, int S,
+                         float* img, float* img_rgb, float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds, double* M64,
+                         float* joint, float* joint_img, double* cam64, double* cube64, int* aug_status, void* stream);
+
+/* kpf_prep_aug_draw (ABI 25): the reference's rand_augment (dataloader/loader.py:495-498) and HO3D's colour scale from a counter hash of seed [B] (device,
+ * read then advanced: seed[b] += seed_stride, so that a replayed graph draws anew) — preprocess.draw_augment is the host twin, bit-equal except rot_cs.
+ * Uniform k of sample b: u = (53 bits of two hash words) * 2^-53, a + (b - a) * u like random.uniform.  mode = floor(4 u0); off = (-1 + 2 u) * sigma_com for
+ * u1..u3; rot = -range + (2 range) u4; sc = |1 + (-1 + 2 u5) * sigma_sc|; color = (1 - f) + ((1 + f) - (1 - f)) u for u6..u8; rot_cs = (cos, sin) of fmod(rot,
+ * 360) * pi / 180 by the device's double library (within 4 ulp).  Python's Mersenne-Twister stream is not reproduced.  One thread per sample. */
+int kpf_prep_aug_draw(long long* seed, int B, double sigma_com, double sigma_sc, double rot_range, double color_factor, long long seed_stride, int* mode,
+                      double* off, double* sc, double* rot, double* rot_cs, double* color, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 24
+#define KPF_ABI_VERSION 25
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

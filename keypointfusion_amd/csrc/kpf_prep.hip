@@ -10,6 +10,9 @@
 //   kpf_prep_annot_u16   the crop by the DATASET protocol (preprocess.prepare_annotated): the centre from the annotated joints (or given), left hands mirrored,
 //                        float32 up to the integer bounds, plus the labels joint / joint_img; then the same gather and normalisation as kpf_prep_crop_u16
 //                        (kpf_prep_uncrop_mirror_f32: the un-crop that takes a mirrored sample's u back to the camera's frame)
+//   kpf_prep_augment_u16 the TRAINING item of the dataset protocol (preprocess.prepare_augmented): kpf_prep_annot_u16's crop, then the reference's augmentation
+//                        (rotation, centre jitter, cube scale, none; colour scale) of both crops through one inverse map per sample, and of the labels
+//   kpf_prep_aug_draw    the augmentation parameters from a device-resident seed (preprocess.draw_augment), which it advances
 //
 // The host path is the yardstick (tests/test_preprocess_gpu.py): integer decisions and both images are bit-equal to it.  Everything that decides an integer
 // is computed in double in the HOST'S operation order, and the whole file is compiled with floating-point contraction OFF (the Makefile's -ffp-contract=on
@@ -223,25 +226,33 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
-// Phases 3 and 4 of a crop, shared by prep_crop_kernel (mirror = 0) and prep_annot_kernel: gather (z-clamped depth into LDS, where its maximum decides the
-// far plane; RGB straight out), then normalize_depth.  A mirrored sample's logical pixel (fy, fx) of the H x W frame is TRUE column W - 1 - fx, and the
-// stored window is tested against that true column.  All PREP_NT threads of the workgroup; contains a barrier.
-__device__ __forceinline__ void prep_gather_normalize(const PrepGeom& g, const unsigned short* __restrict__ dep, const unsigned char* __restrict__ col, int mirror,
-                                                      int Hs, int Ws, int ox, int oy, int H, int W, int S, unsigned short* crop, unsigned* wmax,
-                                                      float* __restrict__ img, float* __restrict__ img_rgb) {
+// Offset, in the stored window, of the frame pixel behind crop pixel (oyp, oxp): false = letterbox border, outside the frame or outside the window (all read
+// as 0).  A mirrored sample's logical pixel (fy, fx) of the H x W frame is TRUE column W - 1 - fx, and the stored window is tested against that true column.
+__device__ __forceinline__ bool prep_window_offset(const PrepGeom& g, int oyp, int oxp, int mirror, int Hs, int Ws, int ox, int oy, int H, int W, size_t& s) {
+  int fy, fx;
+  if (!(prep_source(g, oyp, oxp, fy, fx) && fy >= 0 && fy < H && fx >= 0 && fx < W)) return false;
+  const int wy = fy - oy, wx = (mirror ? W - 1 - fx : fx) - ox;
+  if (!(wy >= 0 && wy < Hs && wx >= 0 && wx < Ws)) return false;
+  s = (size_t)wy * Ws + wx;
+  return true;
+}
+
+// Phase 3 of a crop, shared by prep_crop_kernel (mirror = 0), prep_annot_kernel and prep_augment_kernel (img_rgb NULL: its RGB goes through the warp): the
+// z-clamped depth crop into LDS and RGB straight out; returns the maximum of the crop, which decides the far plane.  All PREP_NT threads of the workgroup;
+// contains a barrier, after which crop[] is complete.
+__device__ __forceinline__ unsigned prep_gather(const PrepGeom& g, const unsigned short* __restrict__ dep, const unsigned char* __restrict__ col, int mirror, int Hs,
+                                                int Ws, int ox, int oy, int H, int W, int S, unsigned short* crop, unsigned* wmax, float* __restrict__ img_rgb) {
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int P = S * S;
   unsigned mx = 0;
   for (int p = t; p < P; p += PREP_NT) {
     const int oyp = p / S, oxp = p - oyp * S;
-    int fy, fx;
+    size_t s;
     unsigned short v = 0;
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-    if (prep_source(g, oyp, oxp, fy, fx) && fy >= 0 && fy < H && fx >= 0 && fx < W) {
-      const int wy = fy - oy, wx = (mirror ? W - 1 - fx : fx) - ox;
-      if (wy >= 0 && wy < Hs && wx >= 0 && wx < Ws) {
-        const size_t s = (size_t)wy * Ws + wx;
-        v = prep_zclamp(dep[s], g);
+    if (prep_window_offset(g, oyp, oxp, mirror, Hs, Ws, ox, oy, H, W, s)) {
+      v = prep_zclamp(dep[s], g);
+      if (img_rgb) {
         c0 = (float)col[3 * s];
         c1 = (float)col[3 * s + 1];
         c2 = (float)col[3 * s + 2];
@@ -249,10 +260,12 @@ __device__ __forceinline__ void prep_gather_normalize(const PrepGeom& g, const u
     }
     crop[p] = v;
     mx = max(mx, (unsigned)v);
-    float* o = img_rgb + (size_t)b * 3 * P + p;
-    o[0] = __fdiv_rn(c0, 255.0f);
-    o[P] = __fdiv_rn(c1, 255.0f);
-    o[2 * (size_t)P] = __fdiv_rn(c2, 255.0f);
+    if (img_rgb) {
+      float* o = img_rgb + (size_t)b * 3 * P + p;
+      o[0] = __fdiv_rn(c0, 255.0f);
+      o[P] = __fdiv_rn(c1, 255.0f);
+      o[2 * (size_t)P] = __fdiv_rn(c2, 255.0f);
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
@@ -261,6 +274,15 @@ __device__ __forceinline__ void prep_gather_normalize(const PrepGeom& g, const u
   PREP_STAMP(2);
   unsigned premax = 0;
   for (int w = 0; w < PREP_NW; ++w) premax = max(premax, wmax[w]);
+  return premax;
+}
+
+// Phases 3 and 4 of a crop: prep_gather, then normalize_depth.
+__device__ __forceinline__ void prep_gather_normalize(const PrepGeom& g, const unsigned short* __restrict__ dep, const unsigned char* __restrict__ col, int mirror,
+                                                      int Hs, int Ws, int ox, int oy, int H, int W, int S, unsigned short* crop, unsigned* wmax,
+                                                      float* __restrict__ img, float* __restrict__ img_rgb) {
+  const int b = blockIdx.x, t = threadIdx.x, P = S * S;
+  const unsigned premax = prep_gather(g, dep, col, mirror, Hs, Ws, ox, oy, H, W, S, crop, wmax, img_rgb);
   for (int p = t; p < P; p += PREP_NT) img[(size_t)b * P + p] = prep_normalize(crop[p], (unsigned short)premax, g);
 }
 
@@ -348,6 +370,40 @@ __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char*
 // kpf_prep_annot_u16: the crop by the dataset protocol (preprocess.prepare_annotated).  Phase 0 replaces the box reduction: the centre comes from the annotation.
 constexpr int ANNOT_XYZ = 65 * 3;           // float xyz of up to 64 joints + the centre they are normalised by
 constexpr int ANNOT_XYZ_BYTES = 800;        // (16-byte multiple)
+
+// Phase 0a of the dataset protocol, one lane per joint: the joint's xyz in float.  through_image: DexYCB's item takes the joints through the image and back,
+// mirrored or not; HO3D's item (the one with a given centre) uses them as they are
+__device__ __forceinline__ void annot_joint_xyz(const float* jp, const float* cam, bool through_image, int mir, int W, float* out) {
+  const float fx = cam[0], fy = cam[1], fu = cam[2], fv = cam[3];
+  float x = jp[0], y = jp[1];
+  const float z = jp[2];
+  if (through_image) {
+    float u = prep_fdiv(x * fx, z) + fu;
+    const float v = prep_fdiv(y * fy, z) + fv;
+    if (mir) u = ((float)W - u) - 1.0f;
+    x = prep_fdiv((u - fu) * z, fx);
+    y = prep_fdiv((v - fv) * z, fy);
+  }
+  out[0] = x;
+  out[1] = y;
+  out[2] = z;
+}
+
+// Phase 0b, one lane: the centre (given, or the rows of xyz summed in order: np.mean(0) of a [J][3] float array) into xyz[64], its projection, the geometry
+__device__ __forceinline__ void annot_centre_geom(float* xyz, const float* given, int J, const float* cam, const double* cube, int S, PrepGeom& g) {
+  const float fx = cam[0], fy = cam[1], fu = cam[2], fv = cam[3];
+  float c[3] = {0.f, 0.f, 0.f};
+  if (given) {
+    for (int k = 0; k < 3; ++k) c[k] = given[k];
+  } else {
+    for (int j = 0; j < J; ++j)
+      for (int k = 0; k < 3; ++k) c[k] = c[k] + xyz[3 * j + k];
+    for (int k = 0; k < 3; ++k) c[k] = prep_fdiv(c[k], (float)J);
+  }
+  for (int k = 0; k < 3; ++k) xyz[3 * 64 + k] = c[k];
+  const float cuvd[3] = {prep_fdiv(c[0] * fx, c[2]) + fu, prep_fdiv(c[1] * fy, c[2]) + fv, c[2]};
+  prep_geom_f32(cuvd, cam, cube, S, g);
+}
 __global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
                                                              const int* __restrict__ frame_index, int F, const float* __restrict__ joints,
                                                              const float* __restrict__ cam, const float* __restrict__ center_xyz,
@@ -372,36 +428,12 @@ __global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char
   PREP_STAMP(0);
   // 0a. one lane per joint: uvd, the mirror and xyz in float.  DexYCB's item takes the joints through the image and back, mirrored or not; HO3D's item (the
   // one with a given centre) uses them as they are
-  if (wv == 0 && joints && lane < J) {
-    const float* jp = joints + ((size_t)b * J + lane) * 3;
-    float x = jp[0], y = jp[1];
-    const float z = jp[2];
-    if (!center_xyz || mir) {
-      float u = prep_fdiv(x * fx, z) + fu;
-      const float v = prep_fdiv(y * fy, z) + fv;
-      if (mir) u = ((float)W - u) - 1.0f;
-      x = prep_fdiv((u - fu) * z, fx);
-      y = prep_fdiv((v - fv) * z, fy);
-    }
-    xyz[3 * lane] = x;
-    xyz[3 * lane + 1] = y;
-    xyz[3 * lane + 2] = z;
-  }
+  if (wv == 0 && joints && lane < J) annot_joint_xyz(joints + ((size_t)b * J + lane) * 3, cam + 4 * b, !center_xyz || mir, mir, W, xyz + 3 * lane);
   __syncthreads();
   // 0b. one lane: the centre (given, or the rows summed in order: np.mean(0) of a [J][3] float array), its projection, the geometry
   if (t == 0) {
-    float c[3] = {0.f, 0.f, 0.f};
-    if (center_xyz) {
-      for (int k = 0; k < 3; ++k) c[k] = center_xyz[3 * b + k];
-    } else {
-      for (int j = 0; j < J; ++j)
-        for (int k = 0; k < 3; ++k) c[k] = c[k] + xyz[3 * j + k];
-      for (int k = 0; k < 3; ++k) c[k] = prep_fdiv(c[k], (float)J);
-    }
-    for (int k = 0; k < 3; ++k) xyz[3 * 64 + k] = c[k];
-    const float cuvd[3] = {prep_fdiv(c[0] * fx, c[2]) + fu, prep_fdiv(c[1] * fy, c[2]) + fv, c[2]};
     PrepGeom g;
-    prep_geom_f32(cuvd, cam + 4 * b, cube + 3 * b, S, g);
+    annot_centre_geom(xyz, center_xyz ? center_xyz + 3 * b : nullptr, J, cam + 4 * b, cube + 3 * b, S, g);
     *gs = g;
     for (int k = 0; k < 3; ++k) {
       center[3 * b + k] = g.center[k];
@@ -453,6 +485,381 @@ __global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char
   PREP_STAMP(3);
 }
 
+// ---- kpf_prep_augment_u16: the training item (preprocess.prepare_augmented).  Everything one lane decides about a sample's augmentation:
+struct AugGeom {
+  int warp;            // the RGB crop's warp: 0 none, 1 perspective (Ai), 2 affine (Ai[0..5] = i00 i01 i02 i10 i11 i12)
+  int warp_depth;      // the depth crop's: the same, or 0 for an all-zero crop
+  int zthresh;         // recropHand's z-threshold follows the depth warp
+  int lab;             // labels: 0 unchanged, 1 shifted by the centre's move, 2 rotated in the image plane
+  int has_color, status;
+  float zs, ze;                          // the z-threshold's planes
+  float far, near, comz, halfz, premax;  // normalize_img's float scalars (of the NEW centre and cube) and the pre-augmentation maximum
+  float c3old[3], center[3], comu, comv; // back-projected old / final centre; the old centre in the image
+  double Ai[9], c, s;
+  double hx, hz;                         // new_cube[0] / 2, new_cube[2] / 2
+  double scale, m02, m12;                // Mnew
+  double color[3];
+};
+
+__host__ __device__ inline bool aug_finite(double v) { return v - v == 0.0; }
+
+// loader.comToTransform for centre cuvd and cube `size`: the bounds in float (prep_geom_f32), the letterbox offset from the UNTRUNCATED resize size
+__host__ __device__ inline bool aug_transform(const float* cuvd, const float* cam, const double* size, int S, double& scale, double& m02, double& m12) {
+  PrepGeom q;
+  prep_geom_f32(cuvd, cam, size, S, q);
+  const int wb = q.xe - q.xs, hb = q.ye - q.ys;
+  const int sat = 268435456;  // prep_bound_f32's saturation: a bound that reached it is not a bound (the host refuses it too)
+  if (wb <= 0 || hb <= 0 || abs(q.xs) >= sat || abs(q.xe) >= sat || abs(q.ys) >= sat || abs(q.ye) >= sat) return false;
+  double sz0, sz1;
+  if (wb > hb) {
+    scale = (double)S / (double)wb;
+    sz0 = (double)S;
+    sz1 = (double)hb * (double)S / (double)wb;
+  } else {
+    scale = (double)S / (double)hb;
+    sz0 = (double)wb * (double)S / (double)hb;
+    sz1 = (double)S;
+  }
+  const double x0 = floor((double)S / 2.0 - sz0 / 2.0), y0 = floor((double)S / 2.0 - sz1 / 2.0);
+  m02 = scale * (double)(-q.xs) + x0;
+  m12 = scale * (double)(-q.ys) + y0;
+  return true;
+}
+
+// One lane: the augmented geometry in the host's precisions and operation order (prepare_augmented).  g: the base crop's geometry; premax: its maximum.
+__host__ __device__ inline void aug_geometry(const PrepGeom& g, const float* cam, const double* cube, int mode, const double* off, double sc, double rot,
+                                             const double* rot_cs, const double* color, unsigned premax, int S, AugGeom& a, double* cube_new, float* com_new) {
+  const float cuvd[3] = {(float)g.com[0], (float)g.com[1], (float)g.com[2]};  // (exact: g.com holds floats)
+  const double c = rot_cs[0], s = rot_cs[1];
+  bool finite = aug_finite(off[0]) && aug_finite(off[1]) && aug_finite(off[2]) && aug_finite(rot) && aug_finite(sc) && aug_finite(c) && aug_finite(s) && sc > 0.0;
+  if (color) finite = finite && aug_finite(color[0]) && aug_finite(color[1]) && aug_finite(color[2]);
+  double ncube[3] = {cube[0], cube[1], cube[2]};
+  float ncom[3] = {cuvd[0], cuvd[1], cuvd[2]};
+  double scale = g.scale, m02 = g.m02, m12 = g.m12;
+  int warp = 0, lab = 0;
+  bool moved = false, ok = finite, scaled = false;
+  if (finite && mode == 1 && !(fabs(off[0]) <= 1e-8 && fabs(off[1]) <= 1e-8 && fabs(off[2]) <= 1e-8)) {
+    const double p0 = (double)g.center[0] + off[0], p1 = (double)g.center[1] + off[1], p2 = (double)g.center[2] + off[2];
+    ncom[0] = (float)(p0 * (double)cam[0] / p2 + (double)cam[2]);
+    ncom[1] = (float)(p1 * (double)cam[1] / p2 + (double)cam[3]);
+    ncom[2] = (float)p2;
+    lab = 1;
+    if (!(aug_finite((double)ncom[0]) && aug_finite((double)ncom[1]) && aug_finite((double)ncom[2]))) {
+      ok = false;  // the offset moved the centre into the camera plane: refused
+    } else if (!(fabs((double)cuvd[2]) <= 1e-8 || fabs((double)ncom[2]) <= 1e-8)) {
+      moved = true;
+      ok = aug_transform(ncom, cam, cube, S, scale, m02, m12);
+    }
+  } else if (finite && mode == 2 && !(fabs(sc - 1.0) <= 1e-8 + 1e-5 * fabs(1.0))) {
+    for (int k = 0; k < 3; ++k) ncube[k] = cube[k] * sc;
+    scaled = true;
+    if (!(fabs((double)cuvd[2]) <= 1e-8)) {
+      moved = true;
+      ok = aug_transform(cuvd, cam, ncube, S, scale, m02, m12);
+    }
+  } else if (finite && mode == 0 && !(fabs(rot) <= 1e-8)) {
+    warp = 2;
+    lab = 2;
+  }
+  if (ok && moved) {
+    // A = np.dot(Mnew, np.linalg.inv(M)) on crop matrices: inv = [[1/s, 0, (-t)(1/s)], ...], every product and the one sum rounded separately
+    const double r = 1.0 / g.scale, i02 = -g.m02 * r, i12 = -g.m12 * r;
+    const double A[9] = {scale * r, 0.0, scale * i02 + m02, 0.0, scale * r, scale * i12 + m12, 0.0, 0.0, 1.0};
+    bool fin = A[0] != 0.0 && A[4] != 0.0;
+    for (int k = 0; k < 9; ++k) fin = fin && aug_finite(A[k]);
+    if (!fin) {
+      ok = false;
+    } else {
+      const double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+      const double d = 1.0 / det;
+      a.Ai[0] = (A[4] * A[8] - A[5] * A[7]) * d;
+      a.Ai[1] = (A[2] * A[7] - A[1] * A[8]) * d;
+      a.Ai[2] = (A[1] * A[5] - A[2] * A[4]) * d;
+      a.Ai[3] = (A[5] * A[6] - A[3] * A[8]) * d;
+      a.Ai[4] = (A[0] * A[8] - A[2] * A[6]) * d;
+      a.Ai[5] = (A[2] * A[3] - A[0] * A[5]) * d;
+      a.Ai[6] = (A[3] * A[7] - A[4] * A[6]) * d;
+      a.Ai[7] = (A[1] * A[6] - A[0] * A[7]) * d;
+      a.Ai[8] = (A[0] * A[4] - A[1] * A[3]) * d;
+      warp = 1;
+    }
+  }
+  a.status = 0;
+  a.has_color = color ? 1 : 0;
+  if (!ok) {  // refused: mode none, no colour
+    a.status = 2;
+    a.has_color = 0;
+    warp = lab = 0;
+    scaled = false;
+    for (int k = 0; k < 3; ++k) {
+      ncube[k] = cube[k];
+      ncom[k] = cuvd[k];
+    }
+    scale = g.scale, m02 = g.m02, m12 = g.m12;
+  }
+  if (warp == 2) {
+    // cv2.getRotationMatrix2D((S / 2, S / 2), -rot, 1) and warpAffine's closed-form inverse
+    const double cx = (double)(S / 2), cy = cx, al = c, be = -s;
+    const double m00 = al, m01 = be, m2 = (1.0 - al) * cx - be * cy, m10 = -be, m11 = al, m5 = be * cx + (1.0 - al) * cy;
+    double D = m00 * m11 - m01 * m10;
+    D = D != 0.0 ? 1.0 / D : 0.0;
+    const double i00 = m11 * D, i11 = m00 * D, i01 = m01 * -D, i10 = m10 * -D;
+    a.Ai[0] = i00;
+    a.Ai[1] = i01;
+    a.Ai[2] = -i00 * m2 - i01 * m5;
+    a.Ai[3] = i10;
+    a.Ai[4] = i11;
+    a.Ai[5] = -i10 * m2 - i11 * m5;
+  }
+  a.warp = warp;
+  a.c = c;
+  a.s = s;
+  if (a.has_color)
+    for (int k = 0; k < 3; ++k) a.color[k] = color[k];
+  for (int k = 0; k < 3; ++k) a.c3old[k] = g.center[k];
+  a.comu = cuvd[0];
+  a.comv = cuvd[1];
+  a.premax = (float)premax;
+  if (premax == 0) {  // an all-zero depth crop: depth, labels, centre, M and cube stay (the RGB crop is warped all the same)
+    a.warp_depth = a.zthresh = a.lab = 0;
+    for (int k = 0; k < 3; ++k) {
+      ncube[k] = cube[k];
+      ncom[k] = cuvd[k];
+    }
+    scale = g.scale, m02 = g.m02, m12 = g.m12;
+  } else {
+    a.warp_depth = warp;
+    a.zthresh = warp == 1;
+    a.lab = lab;
+    if (warp != 0 || lab != 0 || scaled) a.status |= 1;
+  }
+  // recropHand's z-threshold: the centre after the move with the OLD cube (also in mode sc); normalize_img: the new centre and the new cube, in float
+  const float hzold = (float)(cube[2] / 2.0), hz = (float)(ncube[2] / 2.0);
+  a.zs = ncom[2] - hzold;
+  a.ze = ncom[2] + hzold;
+  a.far = ncom[2] + hz;
+  a.near = ncom[2] - hz;
+  a.comz = ncom[2];
+  a.halfz = hz;
+  a.hx = ncube[0] / 2.0;
+  a.hz = ncube[2] / 2.0;
+  a.scale = scale;
+  a.m02 = m02;
+  a.m12 = m12;
+  a.center[0] = prep_fdiv((ncom[0] - cam[2]) * ncom[2], cam[0]);
+  a.center[1] = prep_fdiv((ncom[1] - cam[3]) * ncom[2], cam[1]);
+  a.center[2] = ncom[2];
+  for (int k = 0; k < 3; ++k) {
+    cube_new[k] = ncube[k];
+    com_new[k] = ncom[k];
+  }
+}
+
+// Crop pixel behind destination pixel (y, x) of a warp (the rule of preprocess.warp_perspective_nearest / warp_affine_nearest): false = border.  No integer
+// is formed from a value that is not finite or out of range.
+__host__ __device__ inline bool aug_source(int warp, const double* Ai, int y, int x, int S, int& Y, int& X) {
+  if (warp == 0) {
+    Y = y;
+    X = x;
+    return true;
+  }
+  const double xd = (double)x, yd = (double)y;
+  if (warp == 1) {
+    double W = (Ai[6] * xd + Ai[7] * yd) + Ai[8];
+    W = W != 0.0 ? 1.0 / W : 0.0;
+    const double Xd = rint((Ai[0] * xd + (Ai[1] * yd + Ai[2])) * W), Yd = rint((Ai[3] * xd + (Ai[4] * yd + Ai[5])) * W);
+    if (!(Xd >= 0.0 && Xd < (double)S && Yd >= 0.0 && Yd < (double)S)) return false;  // (NaN compares false)
+    X = (int)Xd;
+    Y = (int)Yd;
+    return true;
+  }
+  const double tx0 = rint((Ai[1] * yd + Ai[2]) * 1024.0), tx1 = rint((Ai[0] * xd) * 1024.0);
+  const double ty0 = rint((Ai[4] * yd + Ai[5]) * 1024.0), ty1 = rint((Ai[3] * xd) * 1024.0);
+  const double lim = 1099511627776.0;  // 2^40
+  if (!(fabs(tx0) < lim && fabs(tx1) < lim && fabs(ty0) < lim && fabs(ty1) < lim)) return false;
+  const long long Xl = ((long long)tx0 + 512 + (long long)tx1) >> 10, Yl = ((long long)ty0 + 512 + (long long)ty1) >> 10;
+  if (!(Xl >= 0 && Xl < S && Yl >= 0 && Yl < S)) return false;
+  X = (int)Xl;
+  Y = (int)Yl;
+  return true;
+}
+
+// sampling-style counter hash for the augmentation draw: uniform i of a sample = 53 bits of words 2 i and 2 i + 1, times 2^-53
+constexpr unsigned AUG_SALT = 0xa4093822U;
+__host__ __device__ inline double aug_uniform(unsigned base, unsigned i) {
+  const unsigned w0 = hash32(base ^ hash32((2u * i) * 0x85ebca6bU + AUG_SALT)), w1 = hash32(base ^ hash32((2u * i + 1u) * 0x85ebca6bU + AUG_SALT));
+  return (double)(((unsigned long long)w0 << 21) | (unsigned long long)(w1 >> 11)) * 1.1102230246251565e-16;  // 2^-53
+}
+
+constexpr int AUG_GEOM_BYTES = 320;
+__global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
+                                                               const int* __restrict__ frame_index, int F, const float* __restrict__ joints,
+                                                               const float* __restrict__ cam, const float* __restrict__ center_xyz,
+                                                               const unsigned char* __restrict__ mirror, const double* __restrict__ cube,
+                                                               const int* __restrict__ mode, const double* __restrict__ off, const double* __restrict__ sc,
+                                                               const double* __restrict__ rot, const double* __restrict__ rot_cs, const double* __restrict__ color,
+                                                               int J, int Hs, int Ws, int ox, int oy, int H, int W, int S, float* __restrict__ img,
+                                                               float* __restrict__ img_rgb, float* __restrict__ center, float* __restrict__ M,
+                                                               float* __restrict__ cube_out, float* __restrict__ cam_out, double* __restrict__ com,
+                                                               int* __restrict__ bounds, double* __restrict__ Md, float* __restrict__ joint,
+                                                               float* __restrict__ joint_img, double* __restrict__ cam64, double* __restrict__ cube64,
+                                                               int* __restrict__ aug_status) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert(sizeof(AugGeom) <= AUG_GEOM_BYTES && AUG_GEOM_BYTES % 16 == 0, "AugGeom outgrew its LDS slot");
+  float* xyz = reinterpret_cast<float*>(smem);                                             // [65][3]
+  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + ANNOT_XYZ_BYTES);                      // 16-byte aligned
+  AugGeom* as = reinterpret_cast<AugGeom*>(smem + ANNOT_XYZ_BYTES + 256);
+  unsigned* wmax = reinterpret_cast<unsigned*>(smem + ANNOT_XYZ_BYTES + 256 + AUG_GEOM_BYTES);  // [PREP_NW]
+  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + ANNOT_XYZ_BYTES + 256 + AUG_GEOM_BYTES + PREP_NW * 4);  // [S * S]
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6, P = S * S;
+  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
+  const unsigned short* dep = depth + (size_t)f * Hs * Ws;
+  const unsigned char* col = rgb + (size_t)f * Hs * Ws * 3;
+  const int mir = mirror[b] ? 1 : 0;
+  const float fx = cam[4 * b], fy = cam[4 * b + 1], fu = cam[4 * b + 2], fv = cam[4 * b + 3];
+  PREP_STAMP(0);
+  // 1. joints, centre and base geometry exactly as prep_annot_kernel
+  if (wv == 0 && lane < J) annot_joint_xyz(joints + ((size_t)b * J + lane) * 3, cam + 4 * b, !center_xyz || mir, mir, W, xyz + 3 * lane);
+  __syncthreads();
+  if (t == 0) {
+    PrepGeom g;
+    annot_centre_geom(xyz, center_xyz ? center_xyz + 3 * b : nullptr, J, cam + 4 * b, cube + 3 * b, S, g);
+    *gs = g;
+  }
+  __syncthreads();
+  const PrepGeom g = *gs;
+  PREP_STAMP(1);
+  // 2. the z-clamped base depth crop into LDS and its maximum (RGB is read through the warp in phase 5)
+  const unsigned premax = prep_gather(g, dep, col, mir, Hs, Ws, ox, oy, H, W, S, crop, wmax, nullptr);
+  // 3. one lane: the augmented geometry, and the sample's small outputs
+  if (t == 0) {
+    AugGeom a;
+    double ncube[3];
+    float ncom[3];
+    aug_geometry(g, cam + 4 * b, cube + 3 * b, mode[b], off + 3 * b, sc[b], rot[b], rot_cs + 2 * b, color ? color + 3 * b : nullptr, premax, S, a, ncube, ncom);
+    *as = a;
+    for (int k = 0; k < 3; ++k) {
+      center[3 * b + k] = a.center[k];
+      com[3 * b + k] = (double)ncom[k];
+      cube_out[3 * b + k] = (float)ncube[k];
+      cube64[3 * b + k] = ncube[k];
+    }
+    for (int k = 0; k < 4; ++k) {
+      cam_out[4 * b + k] = cam[4 * b + k];
+      cam64[4 * b + k] = (double)cam[4 * b + k];
+    }
+    const double m[9] = {a.scale, 0.0, a.m02, 0.0, a.scale, a.m12, 0.0, 0.0, 1.0};
+    for (int k = 0; k < 9; ++k) {
+      Md[9 * b + k] = m[k];
+      M[9 * b + k] = (float)m[k];
+    }
+    int* bo = bounds + 6 * b;
+    bo[0] = g.xs;
+    bo[1] = g.xe;
+    bo[2] = g.ys;
+    bo[3] = g.ye;
+    bo[4] = g.szw;
+    bo[5] = g.szh;
+    aug_status[b] = a.status;
+  }
+  __syncthreads();
+  // 4. the labels, one lane per joint: float up to the division by the half cube, double from there (the reference's cube is an integer or float64 array)
+  if (wv == 0 && lane < J) {
+    const int lab = as->lab;
+    float l[3];
+    for (int k = 0; k < 3; ++k) l[k] = xyz[3 * lane + k] - xyz[3 * 64 + k];
+    if (lab == 1) {
+      const float cn[3] = {as->center[0], as->center[1], as->center[2]};
+      for (int k = 0; k < 3; ++k) l[k] = (l[k] + as->c3old[k]) - cn[k];
+    } else if (lab == 2) {
+      const float q0 = l[0] + as->c3old[0], q1 = l[1] + as->c3old[1], q2 = l[2] + as->c3old[2];
+      const float u = prep_fdiv(q0 * fx, q2) + fu, v = prep_fdiv(q1 * fy, q2) + fv;
+      const float pp0 = u - as->comu, pp1 = v - as->comv;
+      const double c = as->c, s = as->s;
+      float r0 = (float)((double)pp0 * c - (double)pp1 * s), r1 = (float)((double)pp0 * s + (double)pp1 * c);
+      r0 = r0 + as->comu;
+      r1 = r1 + as->comv;
+      l[0] = prep_fdiv((r0 - fu) * q2, fx) - as->c3old[0];
+      l[1] = prep_fdiv((r1 - fv) * q2, fy) - as->c3old[1];
+      l[2] = q2 - as->c3old[2];
+    }
+    const double hx = as->hx, hz = as->hz;
+    const double l0 = (double)l[0] / hz, l1 = (double)l[1] / hz, l2 = (double)l[2] / hz;
+    const double px = l0 * hx + (double)as->center[0], py = l1 * hx + (double)as->center[1], pz = l2 * hx + (double)as->center[2];
+    const float u = (float)(px * (double)fx / pz + (double)fu), v = (float)(py * (double)fy / pz + (double)fv), d = (float)pz;
+    const float cu = (float)(as->scale * (double)u + as->m02), cv = (float)(as->scale * (double)v + as->m12);
+    const float half = (float)((double)S / 2.0);
+    float* jo = joint + ((size_t)b * J + lane) * 3;
+    float* ji = joint_img + ((size_t)b * J + lane) * 3;
+    jo[0] = (float)l0;
+    jo[1] = (float)l1;
+    jo[2] = (float)l2;
+    ji[0] = prep_fdiv(cu, half) - 1.0f;
+    ji[1] = prep_fdiv(cv, half) - 1.0f;
+    ji[2] = (float)((double)(d - as->center[2]) / hx);
+  }
+  // 5. every destination pixel through the inverse map: depth from LDS (z-threshold, premax rule, normalisation in float), RGB from the frame
+  const int warp = as->warp, warp_depth = as->warp_depth, zthresh = as->zthresh, has_color = as->has_color;
+  const float zs = as->zs, ze = as->ze, far = as->far, near = as->near, comz = as->comz, halfz = as->halfz, pmx = as->premax;
+  double Ai[9];
+  for (int k = 0; k < 9; ++k) Ai[k] = as->Ai[k];
+  double cs[3] = {1.0, 1.0, 1.0};
+  if (has_color)
+    for (int k = 0; k < 3; ++k) cs[k] = as->color[k];
+  for (int p = t; p < P; p += PREP_NT) {
+    const int y = p / S, x = p - y * S;
+    int Y = 0, X = 0;
+    const bool in = aug_source(warp, Ai, y, x, S, Y, X);
+    float v = 0.f;
+    if (warp_depth == 0)
+      v = (float)crop[p];
+    else if (in)
+      v = (float)crop[Y * S + X];  // (0 <= Y, X < S: tested by aug_source)
+    if (zthresh) {
+      const bool m1 = v < zs && v != 0.f, m2 = v > ze && v != 0.f;
+      if (m1) v = zs;
+      if (m2) v = 0.f;
+    }
+    if (v == pmx) v = far;
+    if (v == 0.f) v = far;
+    if (v >= far) v = far;
+    if (v <= near) v = near;
+    img[(size_t)b * P + p] = __fdiv_rn(v - comz, halfz);
+    float c3[3] = {0.f, 0.f, 0.f};
+    size_t so;
+    if (in && prep_window_offset(g, Y, X, mir, Hs, Ws, ox, oy, H, W, so))
+      for (int k = 0; k < 3; ++k) c3[k] = (float)col[3 * so + k];
+    if (has_color)
+      for (int k = 0; k < 3; ++k) c3[k] = (float)fmin(fmax((double)c3[k] * cs[k], 0.0), 255.0);
+    float* o = img_rgb + (size_t)b * 3 * P + p;
+    o[0] = __fdiv_rn(c3[0], 255.0f);
+    o[P] = __fdiv_rn(c3[1], 255.0f);
+    o[2 * (size_t)P] = __fdiv_rn(c3[2], 255.0f);
+  }
+  PREP_STAMP(3);
+}
+
+// kpf_prep_aug_draw: one thread per sample (preprocess.draw_augment is the host twin)
+__global__ __launch_bounds__(256) void prep_aug_draw_kernel(long long* __restrict__ seed, int B, double sigma_com, double sigma_sc, double rot_range, double cf,
+                                                            long long stride, int* __restrict__ mode, double* __restrict__ off, double* __restrict__ sc,
+                                                            double* __restrict__ rot, double* __restrict__ rot_cs, double* __restrict__ color) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const long long sd = seed[b];
+  const unsigned base = prep_seed_base(sd);
+  mode[b] = (int)floor(4.0 * aug_uniform(base, 0));
+  for (int k = 0; k < 3; ++k) off[3 * b + k] = (-1.0 + 2.0 * aug_uniform(base, 1 + k)) * sigma_com;
+  const double r = -rot_range + (rot_range - -rot_range) * aug_uniform(base, 4);
+  rot[b] = r;
+  sc[b] = fabs(1.0 + (-1.0 + 2.0 * aug_uniform(base, 5)) * sigma_sc);
+  for (int k = 0; k < 3; ++k) color[3 * b + k] = (1.0 - cf) + ((1.0 + cf) - (1.0 - cf)) * aug_uniform(base, 6 + k);
+  double m = fmod(r, 360.0);  // np.mod: the sign of the divisor
+  if (m != 0.0 && m < 0.0) m += 360.0;
+  const double al = m * 3.141592653589793 / 180.0;
+  rot_cs[2 * b] = cos(al);
+  rot_cs[2 * b + 1] = sin(al);
+  seed[b] = sd + stride;
+}
 // Sorts a[0, P2) ascending (P2 a power of two), all PREP_NT threads of the workgroup; ends with a barrier.
 __device__ __forceinline__ void prep_bitonic_sort(unsigned long long* a, int P2) {
   const int t = threadIdx.x;
@@ -638,6 +1045,7 @@ __global__ __launch_bounds__(256) void prep_uncrop_mirror_kernel(const float* __
 
 constexpr size_t kCropFixedLds = 4 * PREP_NW * 8 + 256 + PREP_NW * 4;
 constexpr size_t kAnnotFixedLds = 800 + 256 + PREP_NW * 4;  // ANNOT_XYZ_BYTES + the geometry + the wave maxima
+constexpr size_t kAugFixedLds = 800 + 256 + 320 + PREP_NW * 4;  // kAnnotFixedLds + AUG_GEOM_BYTES
 inline int host_pow2ceil(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -732,6 +1140,43 @@ extern "C" int kpf_prep_uncrop_mirror_f32(const float* joints, const float* cent
   hipLaunchKernelGGL(prep_uncrop_mirror_kernel, dim3((B * J + 255) / 256), dim3(256), 0, ST(stream), joints, center, M, cube, cam, mirror, frame_w, B, J, crop_px,
                      frame_px);
   return kpf_check_launch("kpf_prep_uncrop_mirror_f32");
+}
+
+extern "C" int kpf_prep_augment_u16(const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const float* joints_mm, const float* cam32,
+                                    const float* center_xyz, const unsigned char* mirror, const double* cube, const int* mode, const double* off, const double* sc,
+                                    const double* rot, const double* rot_cs, const double* color, int B, int J, int Hs, int Ws, int x0, int y0, int H, int W, int S,
+                                    float* img, float* img_rgb, float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds, double* M64,
+                                    float* joint, float* joint_img, double* cam64, double* cube64, int* aug_status, void* stream) {
+  const char* name = "kpf_prep_augment_u16";
+  KPF_REQUIRE(rgb && depth && cam32 && mirror && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64 && joint && joint_img && cam64 &&
+                  cube64 && aug_status,
+              "%s: null pointer argument", name);
+  KPF_REQUIRE(joints_mm, "%s: null joints (a training item has labels)", name);
+  KPF_REQUIRE(mode && off && sc && rot && rot_cs, "%s: null augmentation parameter (mode, off, sc, rot and rot_cs are required; color may be NULL)", name);
+  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
+  KPF_REQUIRE(J > 0 && J <= 64, "%s: J = %d joints (one lane of a wave64 per joint: 1 .. 64)", name, J);
+  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
+  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
+  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
+  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
+  const size_t lds = kAugFixedLds + (size_t)S * S * 2;
+  hipLaunchKernelGGL(prep_augment_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, frame_index, F, joints_mm, cam32, center_xyz, mirror, cube, mode, off, sc,
+                     rot, rot_cs, color, J, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64, joint, joint_img, cam64, cube64,
+                     aug_status);
+  return kpf_check_launch(name);
+}
+
+extern "C" int kpf_prep_aug_draw(long long* seed, int B, double sigma_com, double sigma_sc, double rot_range, double color_factor, long long seed_stride, int* mode,
+                                 double* off, double* sc, double* rot, double* rot_cs, double* color, void* stream) {
+  const char* name = "kpf_prep_aug_draw";
+  KPF_REQUIRE(seed && mode && off && sc && rot && rot_cs && color, "%s: null pointer argument", name);
+  KPF_REQUIRE(B > 0, "%s: B = %d", name, B);
+  KPF_REQUIRE(sigma_com >= 0 && sigma_sc >= 0 && rot_range >= 0 && color_factor >= 0 && sigma_com - sigma_com == 0 && sigma_sc - sigma_sc == 0 &&
+                  rot_range - rot_range == 0 && color_factor - color_factor == 0,
+              "%s: sigma_com %g, sigma_sc %g, rot_range %g and color_factor %g must be finite and not negative", name, sigma_com, sigma_sc, rot_range, color_factor);
+  hipLaunchKernelGGL(prep_aug_draw_kernel, dim3((B + 255) / 256), dim3(256), 0, ST(stream), seed, B, sigma_com, sigma_sc, rot_range, color_factor, seed_stride, mode, off,
+                     sc, rot, rot_cs, color);
+  return kpf_check_launch(name);
 }
 
 /* tuning aid: [B][8] 8-byte stamp slots in device memory for the next launches (NULL switches the stamps off) */

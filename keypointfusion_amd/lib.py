@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 24  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 25  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -202,6 +202,8 @@ _SIGS = {
     "kpf_prep_set_stamps": [_P],
     "kpf_prep_annot_u16": [_P] * 3 + [C.c_int] + [_P] * 5 + [C.c_int] * 9 + [_P] * 13,
     "kpf_prep_uncrop_mirror_f32": [_P] * 6 + [C.c_int] * 3 + [_P] * 3,
+    "kpf_prep_augment_u16": [_P] * 3 + [C.c_int] + [_P] * 11 + [C.c_int] * 9 + [_P] * 15,
+    "kpf_prep_aug_draw": [_P, C.c_int] + [C.c_double] * 4 + [C.c_longlong] + [_P] * 7,
     "kpf_track_step_f32": [_P] * 6 + [C.c_int] * 4 + [C.c_float, C.c_longlong] + [_P] * 9,
     "kpf_eval_errors_f32": [C.POINTER(C.c_void_p), C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
     "kpf_eval_accumulate": [_P, _P, _P] + [C.c_int] * 4 + [_P] * 9,

@@ -10,6 +10,11 @@ Pinned by the reference's own committed crops (tests/test_preprocess.py).
 prepare_annotated / uncrop_points_mirrored restate the DATASET items' test-time path instead (dataloader/loader.py:1113-1204 DexYCB, :1296-1416 HO3D): the
 crop around an annotated 3-D centre, left hands mirrored, the labels, float32 up to the integer bounds.  Pinned to the reference's own items bit for bit
 (tests/test_prep_annot_host.py, tests/golden/dataset_item.npz); DESIGN.md §4.9.
+
+prepare_augmented / draw_augment restate the items' TRAINING path (dataloader/loader.py:1140-1156, :1325-1347, :363-593): the same crop, then one of the
+reference's four augmentation modes and HO3D's colour scale.  Pinned to the reference's items bit for bit around the project's own nearest-neighbour warp rule
+(warp_perspective_nearest / warp_affine_nearest: restated from OpenCV's algorithm, unpinned against a real OpenCV); tests/test_prep_augment_host.py,
+tests/golden/augment_item.npz; DESIGN.md §4.10.
 """
 import math
 
@@ -311,6 +316,308 @@ def prepare_annotated(rgb, depth, joints_mm, cam, mirror=False, center_xyz=None,
     return dict(img_rgb=(crop_rgb.astype(np.float32) / 255.0).transpose(2, 0, 1), img=img_n[None].astype(np.float32), pcl=pcl, center=com3d,
                 M=M.astype(np.float32), cube=np.asarray(cube, np.float32), cam_para=np.asarray(cam, np.float32), crop_rgb=crop_rgb,
                 com=center_uvd.astype(np.float64), joint=joint.astype(np.float32), joint_img=joint_img, mirror=bool(mirror), frame_w=int(W))
+
+
+AUG_MODES = ("rot", "com", "sc", "none")  # the reference's aug_modes order: aug["mode"] indexes it
+
+
+def _invert_crop_matrix(M):
+    """np.linalg.inv of a crop matrix [[s, 0, t], [0, s', u], [0, 0, 1]] as the LAPACK behind NumPy computes it (no pivoting happens, the triangular solve
+    multiplies by the RECIPROCAL of the diagonal): entries 1 / s, 1 / s', (-t) * (1 / s), (-u) * (1 / s').  Checked against np.linalg.inv by
+    tests/golden/gen_golden_augment.py on every case."""
+    r0, r1 = 1.0 / M[0, 0], 1.0 / M[1, 1]
+    return np.array([[r0, 0.0, -M[0, 2] * r0], [0.0, r1, -M[1, 2] * r1], [0.0, 0.0, 1.0]])
+
+
+def _dot_crop_matrices(Mn, Mi):
+    """np.dot(Mn, Mi) of two matrices of that form: every product and the one sum rounded separately."""
+    return np.array([[Mn[0, 0] * Mi[0, 0], 0.0, Mn[0, 0] * Mi[0, 2] + Mn[0, 2]], [0.0, Mn[1, 1] * Mi[1, 1], Mn[1, 1] * Mi[1, 2] + Mn[1, 2]], [0.0, 0.0, 1.0]])
+
+
+def _warp_take(src, X, Y, ok):
+    S0, S1 = src.shape[:2]
+    ok = ok & (X >= 0) & (X < S1) & (Y >= 0) & (Y < S0)
+    xi, yi = np.where(ok, X, 0).astype(np.int64), np.where(ok, Y, 0).astype(np.int64)
+    out = src[yi, xi]
+    out[~ok] = 0
+    return out
+
+
+def warp_perspective_nearest(src, A):
+    """cv2.warpPerspective(src, A, src.shape, flags=INTER_NEAREST, borderMode=BORDER_CONSTANT, borderValue=0), restated from OpenCV's algorithm (UNPINNED:
+    no OpenCV on the build machines; a pixel on a rounding boundary may differ from a real OpenCV).  The rule, float64, every operation rounded once, in
+    this order:
+      det = a00 (a11 a22 - a12 a21) - a01 (a10 a22 - a12 a20) + a02 (a10 a21 - a11 a20);  d = 1 / det
+      Ai = [[(a11 a22 - a12 a21) d, (a02 a21 - a01 a22) d, (a01 a12 - a02 a11) d],
+            [(a12 a20 - a10 a22) d, (a00 a22 - a02 a20) d, (a02 a10 - a00 a12) d],
+            [(a10 a21 - a11 a20) d, (a01 a20 - a00 a21) d, (a00 a11 - a01 a10) d]]
+      per destination pixel (x, y):  W = (Ai20 x + Ai21 y) + Ai22;  W = 1 / W if W != 0 else 0
+      X = rint((Ai00 x + (Ai01 y + Ai02)) W),  Y = rint((Ai10 x + (Ai11 y + Ai12)) W)       (half to even)
+      dst[y, x] = src[Y, X] if 0 <= X < width and 0 <= Y < height (and both are finite) else 0"""
+    a = np.asarray(A, np.float64)
+    det = a[0, 0] * (a[1, 1] * a[2, 2] - a[1, 2] * a[2, 1]) - a[0, 1] * (a[1, 0] * a[2, 2] - a[1, 2] * a[2, 0]) + a[0, 2] * (a[1, 0] * a[2, 1] - a[1, 1] * a[2, 0])
+    with np.errstate(all="ignore"):
+        d = 1.0 / np.float64(det)
+        Ai = np.array([[(a[1, 1] * a[2, 2] - a[1, 2] * a[2, 1]) * d, (a[0, 2] * a[2, 1] - a[0, 1] * a[2, 2]) * d, (a[0, 1] * a[1, 2] - a[0, 2] * a[1, 1]) * d],
+                       [(a[1, 2] * a[2, 0] - a[1, 0] * a[2, 2]) * d, (a[0, 0] * a[2, 2] - a[0, 2] * a[2, 0]) * d, (a[0, 2] * a[1, 0] - a[0, 0] * a[1, 2]) * d],
+                       [(a[1, 0] * a[2, 1] - a[1, 1] * a[2, 0]) * d, (a[0, 1] * a[2, 0] - a[0, 0] * a[2, 1]) * d, (a[0, 0] * a[1, 1] - a[0, 1] * a[1, 0]) * d]])
+        x = np.arange(src.shape[1], dtype=np.float64)[None, :]
+        y = np.arange(src.shape[0], dtype=np.float64)[:, None]
+        W = (Ai[2, 0] * x + Ai[2, 1] * y) + Ai[2, 2]
+        W = np.where(W != 0, 1.0 / np.where(W != 0, W, 1.0), 0.0)
+        X = np.rint((Ai[0, 0] * x + (Ai[0, 1] * y + Ai[0, 2])) * W)
+        Y = np.rint((Ai[1, 0] * x + (Ai[1, 1] * y + Ai[1, 2])) * W)
+    return _warp_take(src, X, Y, np.isfinite(X) & np.isfinite(Y))
+
+
+def rotation_matrix_2d(cx, cy, c, s):
+    """cv2.getRotationMatrix2D((cx, cy), -rot, 1) with (c, s) = (cos, sin) of rot: alpha = c, beta = -s,
+    [[alpha, beta, (1 - alpha) cx - beta cy], [-beta, alpha, beta cx + (1 - alpha) cy]]."""
+    cx, cy = float(cx), float(cy)
+    al, be = float(c), -float(s)
+    return np.array([[al, be, (1.0 - al) * cx - be * cy], [-be, al, be * cx + (1.0 - al) * cy]])
+
+
+def warp_affine_nearest(src, M2):
+    """cv2.warpAffine(src, M2, src.shape, flags=INTER_NEAREST, borderMode=BORDER_CONSTANT, borderValue=0), restated from OpenCV's algorithm (UNPINNED, as
+    warp_perspective_nearest).  The rule, float64, every operation rounded once:
+      D = m00 m11 - m01 m10;  D = 1 / D if D != 0 else 0
+      i00 = m11 D, i11 = m00 D, i01 = m01 (-D), i10 = m10 (-D);  i02 = (-i00) m02 - i01 m12,  i12 = (-i10) m02 - i11 m12
+      X = (rint((i01 y + i02) 1024) + 512 + rint((i00 x) 1024)) >> 10,  Y = (rint((i11 y + i12) 1024) + 512 + rint((i10 x) 1024)) >> 10   (half to even;
+      OpenCV's 10-bit fixed point; a term that is not finite or reaches 2^40 makes the pixel a border pixel)
+      dst[y, x] = src[Y, X] if 0 <= X < width and 0 <= Y < height else 0"""
+    m = np.asarray(M2, np.float64)
+    with np.errstate(all="ignore"):
+        D = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+        D = 1.0 / D if D != 0 else 0.0
+        i00, i11, i01, i10 = m[1, 1] * D, m[0, 0] * D, m[0, 1] * -D, m[1, 0] * -D
+        i02 = -i00 * m[0, 2] - i01 * m[1, 2]
+        i12 = -i10 * m[0, 2] - i11 * m[1, 2]
+        x = np.arange(src.shape[1], dtype=np.float64)[None, :]
+        y = np.arange(src.shape[0], dtype=np.float64)[:, None]
+        tx0, tx1 = np.rint((i01 * y + i02) * 1024.0), np.rint((i00 * x) * 1024.0)
+        ty0, ty1 = np.rint((i11 * y + i12) * 1024.0), np.rint((i10 * x) * 1024.0)
+        lim = 2.0 ** 40
+        ok = (np.abs(tx0) < lim) & (np.abs(tx1) < lim) & (np.abs(ty0) < lim) & (np.abs(ty1) < lim)  # (NaN compares false)
+        X = np.floor(((np.where(ok, tx0, 0.0) + 512.0) + np.where(ok, tx1, 0.0)) / 1024.0)  # exact integers below 2^42: floor(/1024) is >> 10
+        Y = np.floor(((np.where(ok, ty0, 0.0) + 512.0) + np.where(ok, ty1, 0.0)) / 1024.0)
+    return _warp_take(src, X, Y, ok)
+
+
+def _aug_transform(com, size, S, cam):
+    """loader.comToTransform (dataloader/loader.py:303-338): bounds in float32 (annotated_bounds), then float64; the letterbox offset comes from the UNTRUNCATED
+    resize size (sz = hb * S / wb as a float), unlike the crop's own M.  None when the bounds are degenerate."""
+    try:
+        xs, xe, ys, ye, _, _ = annotated_bounds(com, size, cam)
+    except (OverflowError, ValueError):  # a bound that is not finite (a centre moved to depth 0)
+        return None
+    wb, hb = xe - xs, ye - ys
+    if wb <= 0 or hb <= 0 or max(abs(v) for v in (xs, xe, ys, ye)) >= 2 ** 28:  # (the device saturates its bounds there: refused on both sides)
+        return None
+    if wb > hb:
+        scale, sz = float(S) / float(wb), (float(S), hb * float(S) / wb)
+    else:
+        scale, sz = float(S) / float(hb), (wb * float(S) / hb, float(S))
+    x0, y0 = float(np.floor(S / 2.0 - sz[0] / 2.0)), float(np.floor(S / 2.0 - sz[1] / 2.0))
+    return np.array([[scale, 0.0, scale * float(-xs) + x0], [0.0, scale, scale * float(-ys) + y0], [0.0, 0.0, 1.0]])
+
+
+def _rot_cs(rot):
+    a = np.mod(np.float64(rot), 360) * np.pi / 180.0
+    return np.float64(np.cos(a)), np.float64(np.sin(a))
+
+
+def prepare_augmented(rgb, depth, joints_mm, cam, aug, mirror=False, center_xyz=None, cube=(250, 250, 250), img_size=128, sample_num=1024, rng=None):
+    """The reference's dataset items at TRAINING time (dataloader/loader.py:1140-1156 DexYCB, :1325-1347 HO3D): prepare_annotated up to the two crops, then
+    augmentCrop / augmentCrop_RGB (moveCoM, rotateHand, scaleHand, recropHand, comToTransform), normalize_img with the pre-augmentation maximum, and the
+    labels.  aug: dict with mode 0..3 (AUG_MODES: rot, com, sc, none), off [3] float64 mm, rot float64 degrees, sc float64, optional rot_cs = (cos, sin) of
+    np.mod(rot, 360) * pi / 180 as float64 (absent: computed with NumPy; given: no trigonometric function is called) and optional color [3] float64 (HO3D's
+    colour scale: clip(crop * color, 0, 255) in float64 before the float32 cast and the / 255).  joints_mm is required (a training item has labels).
+
+    Returns prepare_annotated's keys (center, M, cube, com, joint, joint_img, img, img_rgb, pcl of the training item) plus M64, cube64 and aug_status (bit 0:
+    the depth side was augmented; bit 1: the parameters were REFUSED — a non-finite value, sc <= 0, a centre moved to where it does not project, or degenerate new bounds — and the sample was prepared as
+    mode none without colour).
+
+    Precisions, the reference's under NumPy 2: the crop, the centre and every bound are prepare_annotated's (float32); the augmented centre is projected in
+    float64 and stored as float32; Mnew, the inverse maps and the warps are float64; the z-threshold and normalize_img are float32; the labels are divided by
+    the float64 half cube and stay FLOAT64 into joint_img (so mode none differs from the test item in joint_img), joint is their float32 rounding.  The
+    early exits are the reference's: allclose(off, 0), allclose(rot, 0), allclose(sc, 1), an all-zero depth crop (depth and labels stay, RGB is warped all the
+    same), and the com[2] guards.  The reference's `warped[warped < min - 1] = background` lines are left out: a nearest-neighbour warp with a zero border
+    returns only values of the source crop or 0; the non-zero ones are >= min > min - 1, and a 0 is only rewritten to the background, which is 0.
+    The two warps are warp_perspective_nearest and warp_affine_nearest: the project's own rule, unpinned against a real OpenCV."""
+    rng = np.random.RandomState(0) if rng is None else rng
+    if joints_mm is None:
+        raise ValueError("prepare_augmented: joints_mm is required: a training item has labels")
+    rgb, depth = np.asarray(rgb), np.asarray(depth)
+    cam = tuple(np.float32(c) for c in cam)
+    if len(cam) != 4 or len(cube) != 3:
+        raise ValueError("prepare_augmented: cam is (fx, fy, u0, v0) and cube three sizes in mm")
+    mode = int(aug["mode"])
+    off = np.asarray(aug["off"], np.float64)
+    rot, sc = np.float64(aug["rot"]), np.float64(aug["sc"])
+    if not 0 <= mode <= 3 or off.shape != (3,):
+        raise ValueError("prepare_augmented: aug['mode'] is 0..3 (%s) and aug['off'] three mm" % (AUG_MODES,))
+    c, s = (np.float64(v) for v in aug["rot_cs"]) if aug.get("rot_cs") is not None else _rot_cs(rot) if np.isfinite(rot) else (np.float64("nan"),) * 2
+    color = None if aug.get("color") is None else np.asarray(aug["color"], np.float64)
+    if color is not None and color.shape != (3,):
+        raise ValueError("prepare_augmented: aug['color'] is three factors")
+    S, W = int(img_size), depth.shape[1]
+    if mirror:
+        rgb, depth = rgb[:, ::-1].copy(), depth[:, ::-1].copy()
+    joints_mm = _f32(joints_mm)
+    if joints_mm.ndim != 2 or joints_mm.shape[1] != 3:
+        raise ValueError("prepare_augmented: joints_mm must be [J][3] (got %s)" % (joints_mm.shape,))
+    joint_xyz = joints_mm
+    if center_xyz is None or mirror:
+        joint_uvd = _project_f32(joints_mm, cam)
+        if mirror:
+            joint_uvd[:, 0] = np.float32(W) - joint_uvd[:, 0] - np.float32(1)
+        joint_xyz = _backproject_f32(joint_uvd, cam)
+    if center_xyz is None:
+        center_xyz = _mean_rows_f32(joint_xyz)
+    else:
+        center_xyz = _f32(center_xyz)
+        if center_xyz.shape != (3,):
+            raise ValueError("prepare_augmented: center_xyz must be [3] (got %s)" % (center_xyz.shape,))
+    com = _project_f32(center_xyz, cam)  # center_uvd, float32
+    bounds = annotated_bounds(com, cube, cam)
+    crop_rgb, _ = _crop_to_bounds(rgb, bounds, (S, S), thresh_z=False)
+    crop_d, M = _crop_to_bounds(depth, bounds, (S, S), thresh_z=True)
+    gt = joint_xyz - center_xyz  # gt3Dcrop, float32
+    premax = crop_d.max()
+    cube64 = np.asarray(cube, np.float64)  # cube[k] / 2.0 is a float64 in every mode (an int64 array, or the list of Python floats of scaleHand)
+
+    # -- the geometry of the mode: Mnew / A for the perspective warp, or the 2 x 3 matrix of the rotation; None = an early exit
+    status = 0
+    finite = bool(np.isfinite(off).all() and np.isfinite(rot) and np.isfinite(sc) and np.isfinite(c) and np.isfinite(s) and sc > 0
+                  and (color is None or np.isfinite(color).all()))
+    new_com, new_cube, Mnew, A, R = com, cube64, M, None, None
+    shift = False
+    com3d_old = _backproject_f32(com, cam)
+    with np.errstate(all="ignore"):
+        if finite and mode == 1 and not np.allclose(off, 0.0):
+            p = com3d_old.astype(np.float64) + off  # joint3DToImg of a float64 point: float64, stored as float32
+            fx, fy, fu, fv = (np.float64(v) for v in cam)
+            new_com = np.array([p[0] * fx / p[2] + fu, p[1] * fy / p[2] + fv, p[2]]).astype(np.float32)
+            shift = True
+            if not np.isfinite(new_com).all():  # the offset moved the centre into the camera plane: refused
+                Mnew = None
+            elif not (np.allclose(com[2], 0.0) or np.allclose(new_com[2], 0.0)):
+                Mnew = _aug_transform(new_com, cube, S, cam)
+        elif finite and mode == 2 and not np.allclose(sc, 1.0):
+            new_cube = np.array([float(v) * float(sc) for v in cube])
+            if not np.allclose(com[2], 0.0):
+                Mnew = _aug_transform(com, new_cube, S, cam)
+        elif finite and mode == 0 and not np.allclose(rot, 0.0):
+            R = rotation_matrix_2d(S // 2, S // 2, c, s)
+        if Mnew is not None and Mnew is not M:
+            A = _dot_crop_matrices(Mnew, _invert_crop_matrix(M))
+            if not (np.isfinite(A).all() and A[0, 0] != 0 and A[1, 1] != 0):
+                Mnew = None
+    if not finite or Mnew is None:  # refused: mode none, no colour
+        status, mode, color = 2, 3, None
+        new_com, new_cube, Mnew, A, R, shift = com, cube64, M, None, None, False
+
+    # -- RGB: warped whatever the depth crop holds (augmentCrop_RGB has no all-zero test)
+    crop_rgb_aug = crop_rgb
+    if A is not None:
+        crop_rgb_aug = warp_perspective_nearest(crop_rgb, A)
+    elif R is not None:
+        crop_rgb_aug = warp_affine_nearest(crop_rgb, R)
+    if color is not None:
+        crop_rgb_aug = np.clip(crop_rgb_aug * color[None, None, :], 0, 255)
+    crop_rgb_aug = crop_rgb_aug.astype(np.float32)
+
+    # -- depth and labels
+    d = crop_d.astype(np.float32, copy=True)
+    lab = gt
+    if premax == 0:  # an all-zero crop: depth, labels, com, M and cube stay
+        new_com, new_cube, Mnew = com, cube64, M
+    else:
+        if A is not None or R is not None or shift or new_cube is not cube64:
+            status |= 1
+        if A is not None:
+            d = warp_perspective_nearest(d, A)
+            zc = new_com if mode == 1 else com  # recropHand's z-threshold: the new centre with the OLD cube (also in mode sc)
+            zs, ze = zc[2] - np.float32(cube[2] / 2.0), zc[2] + np.float32(cube[2] / 2.0)
+            m1, m2 = np.logical_and(d < zs, d != 0), np.logical_and(d > ze, d != 0)
+            d[m1] = zs
+            d[m2] = 0.0
+        elif R is not None:
+            d = warp_affine_nearest(d, R)
+        if shift:
+            lab = gt + com3d_old - _backproject_f32(new_com, cam)
+        elif R is not None:
+            j2 = _project_f32(gt + com3d_old, cam)
+            pp = j2[:, 0:2] - com[0:2]
+            pr = np.zeros_like(j2)
+            pr[:, 0] = pp[:, 0].astype(np.float64) * c - pp[:, 1].astype(np.float64) * s
+            pr[:, 1] = pp[:, 0].astype(np.float64) * s + pp[:, 1].astype(np.float64) * c
+            pr[:, 2] = j2[:, 2]
+            pr[:, 0:2] += com[0:2]
+            lab = _backproject_f32(pr, cam) - com3d_old
+    # normalize_img(premax, imgD, com, cube): float32 scalars (a float32 centre and Python-float halves)
+    hz = np.float32(new_cube[2] / 2.0)
+    far, near = new_com[2] + hz, new_com[2] - hz
+    d[d == premax] = far
+    d[d == 0] = far
+    d[d >= far] = far
+    d[d <= near] = near
+    d -= new_com[2]
+    d /= hz
+    com3d = _backproject_f32(new_com, cam)
+    lab64 = lab.astype(np.float64) / (new_cube[2] / 2.0)
+    p = lab64 * (new_cube[0] / 2.0) + com3d.astype(np.float64)
+    fx, fy, fu, fv = (float(v) for v in cam)
+    with np.errstate(all="ignore"):
+        uvd = np.stack([p[:, 0] * fx / p[:, 2] + fu, p[:, 1] * fy / p[:, 2] + fv, p[:, 2]], 1).astype(np.float32)
+        joint_img = uvd.copy()
+        joint_img[:, 0] = Mnew[0, 0] * uvd[:, 0].astype(np.float64) + Mnew[0, 2]
+        joint_img[:, 1] = Mnew[1, 1] * uvd[:, 1].astype(np.float64) + Mnew[1, 2]
+        joint_img[:, 0:2] = joint_img[:, 0:2] / np.float32(S / 2) - np.float32(1)
+        joint_img[:, 2] = (joint_img[:, 2] - com3d[2]).astype(np.float64) / (new_cube[0] / 2.0)
+    cam64 = tuple(float(v) for v in cam)
+    pcl = sample_points(depth_to_pcl(d, com3d, new_cube, Mnew, cam64), sample_num, rng)
+    return dict(img_rgb=(crop_rgb_aug / np.float32(255.0)).transpose(2, 0, 1), img=d[None].astype(np.float32), pcl=pcl, center=com3d,
+                M=Mnew.astype(np.float32), cube=new_cube.astype(np.float32), cam_para=np.asarray(cam, np.float32), crop_rgb=crop_rgb_aug,
+                com=new_com.astype(np.float64), joint=lab64.astype(np.float32), joint_img=joint_img, mirror=bool(mirror), frame_w=int(W),
+                M64=Mnew, cube64=new_cube, aug_status=int(status))
+
+
+# ---- drawing the augmentation parameters: the counter hash of kpf_prep.hip (hash32 / prep_seed_base), vectorised over the seeds
+AUG_SALT = 0xa4093822
+
+
+def _hash32(x):
+    x = np.asarray(x, np.uint64) & np.uint64(0xffffffff)
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7feb352d)) & np.uint64(0xffffffff)
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846ca68b)) & np.uint64(0xffffffff)
+    return x ^ (x >> np.uint64(16))
+
+
+def draw_augment(seed, sigma_com=10.0, sigma_sc=0.2, rot_range=180.0, color_factor=0.0):
+    """The host twin of kpf_prep_aug_draw: the reference's rand_augment (dataloader/loader.py:495-498) and HO3D's colour scale, drawn from seed [B] int64 by
+    the sampler's counter hash.  Word k of sample b = hash32(base ^ hash32(k * 0x85ebca6b + AUG_SALT)), base = prep_seed_base(seed[b]); uniform i = ((word 2i
+    << 21) | (word 2i+1 >> 11)) * 2^-53, mapped a + (b - a) * u like random.uniform.  mode = floor(4 u0); off = (-1 + 2 u1..3) * sigma_com; rot = -range + (2
+    range) u4; sc = |1 + (-1 + 2 u5) * sigma_sc|; color = (1 - f) + ((1 + f) - (1 - f)) u6..8; rot_cs = (cos, sin)(mod(rot, 360) pi / 180) with NumPy.  Python's
+    Mersenne-Twister stream (the reference's `random`) is NOT reproduced: the distribution is.  Returns dict(mode [B] int32, off [B][3], rot [B], sc [B],
+    rot_cs [B][2], color [B][3]) of float64."""
+    seed = np.atleast_1d(np.asarray(seed, np.int64)).view(np.uint64)
+    lo, hi = seed & np.uint64(0xffffffff), seed >> np.uint64(32)
+    base = _hash32(lo ^ _hash32((hi + np.uint64(0x9e3779b9)) & np.uint64(0xffffffff)))
+    k = np.arange(18, dtype=np.uint64)[None, :]
+    w = _hash32(base[:, None] ^ _hash32((k * np.uint64(0x85ebca6b) + np.uint64(AUG_SALT)) & np.uint64(0xffffffff)))
+    u = ((w[:, 0::2] << np.uint64(21)) | (w[:, 1::2] >> np.uint64(11))).astype(np.float64) * 2.0 ** -53
+    sigma_com, sigma_sc, rot_range, f = float(sigma_com), float(sigma_sc), float(rot_range), float(color_factor)
+    mode = np.floor(4.0 * u[:, 0]).astype(np.int32)
+    off = (-1.0 + 2.0 * u[:, 1:4]) * sigma_com
+    rot = -rot_range + (rot_range - -rot_range) * u[:, 4]
+    sc = np.abs(1.0 + (-1.0 + 2.0 * u[:, 5]) * sigma_sc)
+    color = (1.0 - f) + ((1.0 + f) - (1.0 - f)) * u[:, 6:9]
+    a = np.mod(rot, 360) * np.pi / 180.0
+    return dict(mode=mode, off=off, rot=rot, sc=sc, rot_cs=np.stack([np.cos(a), np.sin(a)], 1), color=color)
 
 
 def uncrop_points_mirrored(uv, M, mirror, frame_w):

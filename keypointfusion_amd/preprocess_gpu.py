@@ -17,6 +17,12 @@ By the dataset protocol (the reference's DexYCB / HO3D items at test time: the c
     evaluator.update(res, prep["img"], prep["joint"], prep["center"], prep["M"], prep["cube"], prep["cam_para"])   # xyz_gt = prep["joint"]
     crop_px, frame_px = pre.uncrop(res[5], prep)                       # a mirrored sample's u comes back in the camera's own frame
 
+Training from frames (the reference's items at TRAINING time: the same crop, then one of its augmentations per sample; `preprocess.prepare_augmented` is the
+yardstick, tests/test_prep_augment_gpu.py pins this path to it bit for bit):
+
+    prep = pre.prepare_augmented(rgb_u8, depth_u16, joints_mm, cam32, seed, mirror=left)   # parameters drawn on the device from seed, which advances by B
+    loss = step(train_batch(prep))                                     # training.GraphedTrainStep: uvd_gt = prep["joint_img"], xyz_gt = prep["joint"]
+
 A frame may be uploaded as a window: `origin=(x0, y0), frame_size=(H, W)` says where the stored [Hs][Ws] image sits in the camera frame; pixels outside
 it read as zero.  The point sample is drawn from a counter hash of (seed[b], candidate) and is not numpy's RandomState stream: it has the same
 distribution (n candidates without replacement in random order; a cloud smaller than n tiled first), see kpf_prep_pcl_sample in include/kpf.h.
@@ -216,8 +222,8 @@ class DevicePreprocessor:
             raise ValueError("%s: the %d x %d window at (%d, %d) leaves the %d x %d frame" % (where, Ws, Hs, x0, y0, W, H))
         return B, J, Hs, Ws, x0, y0, H, W
 
-    def _annot_buffers(self, dev, B, Hs, Ws, J):
-        key = (dev, B, Hs, Ws, "annot", J)
+    def _annot_buffers(self, dev, B, Hs, Ws, J, kind="annot"):
+        key = (dev, B, Hs, Ws, kind, J)
         b = self._bufs.get(key)
         if b is None:
             S, n = self.img_size, self.sample_num
@@ -272,11 +278,115 @@ class DevicePreprocessor:
         out.update(mirror=mir, frame_w=W)
         return out
 
+    # -- training augmentation by the dataset protocol
+    AUG_KEYS = (("mode", (), torch.int32), ("off", (3,), torch.float64), ("sc", (), torch.float64), ("rot", (), torch.float64), ("rot_cs", (2,), torch.float64))
+
+    @staticmethod
+    def check_augmented(rgb, depth, joints_mm, cam, seed, aug=None, mirror=None, center_xyz=None, origin=None, frame_size=None, frame_index=None,
+                        sigma_com=10, sigma_sc=0.2, rot_range=180, color_factor=0):
+        """Validates one batch for prepare_augmented and returns check_annotated's tuple.  Raises TypeError / ValueError with the reason; touches no device."""
+        where = "DevicePreprocessor.prepare_augmented"
+        if joints_mm is None:
+            raise ValueError("%s: joints_mm is required: a training item has labels" % where)
+        shape = DevicePreprocessor.check_annotated(rgb, depth, joints_mm, cam, seed, mirror, center_xyz, origin, frame_size, frame_index)
+        B = shape[0]
+        for name, v in (("sigma_com", sigma_com), ("sigma_sc", sigma_sc), ("rot_range", rot_range), ("color_factor", color_factor)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not 0 <= float(v) < float("inf"):
+                raise ValueError("%s: %s must be a finite number >= 0 (got %r)" % (where, name, v))
+        if aug is not None:
+            if not isinstance(aug, dict):
+                raise TypeError("%s: aug must be a dict of device tensors (mode, off, sc, rot, rot_cs and optionally color), got %s" % (where, type(aug).__name__))
+            keys = DevicePreprocessor.AUG_KEYS + ((("color", (3,), torch.float64),) if aug.get("color") is not None else ())
+            for k, tail, dt in keys:
+                t = aug.get(k)
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError("%s: aug[%r] must be a torch tensor on the GPU (got %s)" % (where, k, type(t).__name__))
+                if tuple(t.shape) != (B,) + tail:
+                    raise ValueError("%s: aug[%r] has shape %s, expected %s" % (where, k, tuple(t.shape), (B,) + tail))
+                if t.dtype != dt:
+                    raise TypeError("%s: aug[%r] must be %s (got %s)" % (where, k, dt, t.dtype))
+        return shape
+
+    def _aug_buffers(self, dev, B, Hs, Ws, J):
+        key = (dev, B, Hs, Ws, "augment", J)
+        b = self._bufs.get(key)
+        if b is None:
+            b = dict(self._annot_buffers(dev, B, Hs, Ws, J, kind="augment-outputs"))  # (its own set: prepare_annotated's results stay)
+            f64 = dict(device=dev, dtype=torch.float64)
+            b.update(cube64=torch.zeros(B, 3, **f64), aug_status=torch.zeros(B, device=dev, dtype=torch.int32),
+                     _pcl_seed=torch.zeros(B, device=dev, dtype=torch.int64),
+                     _aug=dict(mode=torch.zeros(B, device=dev, dtype=torch.int32), off=torch.zeros(B, 3, **f64), sc=torch.zeros(B, **f64), rot=torch.zeros(B, **f64),
+                               rot_cs=torch.zeros(B, 2, **f64), color=torch.zeros(B, 3, **f64)))
+            self._bufs[key] = b
+        return b
+
+    def prepare_augmented(self, rgb, depth, joints_mm, cam, seed, aug=None, mirror=None, center_xyz=None, origin=None, frame_size=None, frame_index=None,
+                          sigma_com=10, sigma_sc=0.2, rot_range=180, color_factor=0):
+        """The reference's dataset items at TRAINING time on the device (preprocess.prepare_augmented, bit for bit): prepare_annotated's crop, then the
+        reference's augmentation — one of rot / com / sc / none per sample — of both crops and the labels.  Inputs as prepare_annotated (joints_mm is
+        required).  aug: dict of device tensors mode [B] int32 (0 rot, 1 com, 2 sc, 3 none), off [B][3], sc [B], rot [B] (degrees), rot_cs [B][2] = (cos,
+        sin) of mod(rot, 360) pi / 180, optionally color [B][3], all float64.  aug=None: the parameters are DRAWN on the device from seed (the reference's
+        rand_augment with sigma_com, sigma_sc, rot_range; color_factor > 0 also draws HO3D's colour scale; preprocess.draw_augment is the host twin), and seed
+        is ADVANCED in place by B, so that the next call — or the next replay of a captured graph — draws anew; the point sample uses the seed before the
+        advance.  Draw, crop and sample are three launches; no allocation.  Returns prepare_annotated's dict plus cube64, aug (the parameters used) and
+        aug_status [B] int32 (bit 0: the depth side was augmented; bit 1: refused parameters — not finite, sc <= 0, degenerate bounds — prepared as mode
+        none).  bounds are those of the base crop.  The result is marked `augmented`: uncrop() refuses it."""
+        B, J, Hs, Ws, x0, y0, H, W = self.check_augmented(rgb, depth, joints_mm, cam, seed, aug, mirror, center_xyz, origin, frame_size, frame_index, sigma_com,
+                                                          sigma_sc, rot_range, color_factor)
+        dev = depth.device
+        named = [("rgb", rgb), ("depth", depth), ("joints_mm", joints_mm), ("cam", cam), ("seed", seed), ("mirror", mirror), ("center_xyz", center_xyz),
+                 ("frame_index", frame_index)] + [("aug[%r]" % k, v) for k, v in (aug or {}).items()]
+        for name, t in named:
+            if t is None:
+                continue
+            if t.device.type != "cuda" or t.device != dev:
+                raise RuntimeError("DevicePreprocessor.prepare_augmented: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
+                                   "preprocess.prepare_augmented is the host path)" % (name, t.device))
+            if not t.is_contiguous():
+                raise ValueError("DevicePreprocessor.prepare_augmented: %s must be contiguous" % name)
+        l = lib.load()
+        o = self._aug_buffers(dev, B, Hs, Ws, J)
+        S, n = self.img_size, self.sample_num
+        mir = o["_right"] if mirror is None else mirror
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            pcl_seed = seed
+            if aug is None:
+                a = o["_aug"]
+                pcl_seed = o["_pcl_seed"]
+                pcl_seed.copy_(seed)  # (a device copy on the current stream: capturable)
+                lib.check(l.kpf_prep_aug_draw(seed.data_ptr(), B, float(sigma_com), float(sigma_sc), float(rot_range), float(color_factor), B, a["mode"].data_ptr(),
+                                              a["off"].data_ptr(), a["sc"].data_ptr(), a["rot"].data_ptr(), a["rot_cs"].data_ptr(), a["color"].data_ptr(), st),
+                          "kpf_prep_aug_draw")
+                used = dict(a) if float(color_factor) != 0 else {k: v for k, v in a.items() if k != "color"}
+            else:
+                used = {k: aug[k] for k in ("mode", "off", "sc", "rot", "rot_cs")}
+                if aug.get("color") is not None:
+                    used["color"] = aug["color"]
+            lib.check(l.kpf_prep_augment_u16(rgb.data_ptr(), depth.data_ptr(), ptr(frame_index), int(depth.shape[0]), joints_mm.data_ptr(), cam.data_ptr(),
+                                             ptr(center_xyz), mir.data_ptr(), o["_cube64"].data_ptr(), used["mode"].data_ptr(), used["off"].data_ptr(),
+                                             used["sc"].data_ptr(), used["rot"].data_ptr(), used["rot_cs"].data_ptr(), ptr(used.get("color")), B, J, Hs, Ws, x0, y0,
+                                             H, W, S, o["img"].data_ptr(), o["img_rgb"].data_ptr(), o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(),
+                                             o["cam_para"].data_ptr(), o["com"].data_ptr(), o["bounds"].data_ptr(), o["M64"].data_ptr(), o["joint"].data_ptr(),
+                                             o["joint_img"].data_ptr(), o["_cam64"].data_ptr(), o["cube64"].data_ptr(), o["aug_status"].data_ptr(), st),
+                      "kpf_prep_augment_u16")
+            cand = o["candidates"].data_ptr() if self.debug_candidates else None
+            lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["cube64"].data_ptr(), o["_cam64"].data_ptr(),
+                                            pcl_seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
+                      "kpf_prep_pcl_sample")
+        out = {k: v for k, v in o.items() if not k.startswith("_")}
+        out.update(mirror=mir, frame_w=W, aug=used, augmented=True)
+        return out
+
     def uncrop(self, joints_nl, prep):
         """joints_nl [B][J][3] float32 normalised to the cube (the model's xyz outputs) + a prepare() result (or any dict with center, M, cube, cam_para)
         -> (crop_px [B][J][3]: u, v in crop pixels and d in mm; frame_px [B][J][3]: u, v in frame pixels and d in mm).  New tensors.  A
         prepare_annotated() result carries mirror and frame_w: a mirrored sample's frame u is frame_w - 1 - u, back in the camera's own frame (its depth and
         the predicted xyz stay in the mirrored camera's space, as in the reference)."""
+        if prep.get("augmented"):
+            raise ValueError("DevicePreprocessor.uncrop: an augmented crop is refused: after a rotation the crop is no longer an axis-aligned window of the "
+                             "frame, and M alone does not take its pixels back (un-crop a prepare() or prepare_annotated() result)")
         if not isinstance(joints_nl, torch.Tensor) or joints_nl.dim() != 3 or joints_nl.shape[2] != 3 or joints_nl.dtype != torch.float32:
             raise ValueError("DevicePreprocessor.uncrop: joints must be a float32 tensor [B][J][3]")
         B, J = int(joints_nl.shape[0]), int(joints_nl.shape[1])
@@ -304,3 +414,16 @@ class DevicePreprocessor:
             lib.check(lib.load().kpf_prep_uncrop_f32(j.data_ptr(), *[t.data_ptr() for t in par], B, J, crop_px.data_ptr(), frame_px.data_ptr(),
                                                      torch.cuda.current_stream(dev).cuda_stream), "kpf_prep_uncrop_f32")
         return crop_px, frame_px
+
+
+def train_batch(prep, epoch=None):
+    """The dict GraphedTrainStep and training.kpfusion_loss take, from a prepare_augmented() (or prepare_annotated()) result: MODEL_INPUTS plus uvd_gt =
+    joint_img and xyz_gt = joint, and `epoch` when given.  The tensors are the preprocessor's buffers, not copies."""
+    missing = [k for k in MODEL_INPUTS + ("joint_img", "joint") if k not in prep]
+    if missing:
+        raise ValueError("train_batch: the preprocessing result has no %s: it takes a prepare_augmented() or prepare_annotated() result" % ", ".join(missing))
+    batch = {k: prep[k] for k in MODEL_INPUTS}
+    batch.update(uvd_gt=prep["joint_img"], xyz_gt=prep["joint"])
+    if epoch is not None:
+        batch["epoch"] = epoch
+    return batch

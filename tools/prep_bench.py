@@ -6,6 +6,8 @@ forward of the same build.  Prints one JSON line.
     python tools/prep_bench.py --device-only --reps 50   # only the three kpf_prep_* kernels (the form to run under rocprofv3 --kernel-trace --stats)
     python tools/prep_bench.py --annotated          # only: prepare_annotated (the dataset protocol) beside prepare on the same B = 32 frames;
                                                     # writes profiles/prep_annot_bench.json (--out: elsewhere)
+    python tools/prep_bench.py --augmented          # only: prepare_augmented with parameters drawn on the device (training augmentation) beside
+                                                    # prepare_annotated on the same B = 32 frames; writes profiles/prep_augment_bench.json (--out: elsewhere)
 
 Times are host clocks around work that ends in a device synchronise (enqueue of `reps` batches, one synchronise), after a warm-up of every shape."""
 import argparse
@@ -116,15 +118,66 @@ def annotated(args):
         f.write(line + "\n")
 
 
+def augmented(args):
+    """prepare_augmented (draw + crop + sample, the parameters drawn on the device, so every replay sees a fresh mix of the four modes) beside
+    prepare_annotated on the frames of tests/annot_cases.py, eagerly and replayed from a graph, alternating as annotated() does."""
+    import torch
+    import annot_cases as AC
+    from keypointfusion_amd.preprocess_gpu import DevicePreprocessor
+    dev = torch.device("cuda:0")
+    items = [AC.synth(AC.SMALL[i % len(AC.SMALL)], seed=1 + i) for i in range(B)]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    rgb, depth = t(np.stack([i[0] for i in items])), t(np.stack([i[1] for i in items]))
+    joints, cam32 = t(np.stack([i[2] for i in items])), t(np.stack([i[3] for i in items]))
+    mirror = t(np.array([i[4] for i in items], np.uint8))
+    seed, seed_aug = torch.arange(B, dtype=torch.int64, device=dev), torch.arange(B, dtype=torch.int64, device=dev)
+    pre = DevicePreprocessor(cube=AC.CUBE)
+    rec = {"tool": "prep_bench --augmented", "B": B, "reps": args.reps, "frames": "640x480", "left_hands": int(mirror.sum()), "color_factor": 0.2}
+    stream = torch.cuda.Stream(device=dev)
+    with torch.no_grad(), torch.cuda.stream(stream):
+        run_a = lambda: pre.prepare_annotated(rgb, depth, joints, cam32, seed, mirror=mirror)
+        run_g = lambda: pre.prepare_augmented(rgb, depth, joints, cam32, seed_aug, mirror=mirror, color_factor=0.2)
+        graphs = []
+        for fn in (run_a, run_g):
+            fn()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                fn()
+            graphs.append(graph)
+        names = ("prepare_annotated_ms", "prepare_augmented_ms", "prepare_annotated_graph_ms", "prepare_augmented_graph_ms")
+        rounds = {k: [] for k in names}
+        for _ in range(3):
+            for k, fn in zip(names, (run_a, run_g, graphs[0].replay, graphs[1].replay)):
+                rounds[k].append(_timed(fn, args.reps, torch) * 1e3)
+        for k in names:
+            rec[k], rec[k + "_rounds"] = float(np.median(rounds[k])), rounds[k]
+        out = run_g()
+        rec["pcl_count_mean_augmented"] = float(out["pcl_count"].float().mean())
+        rec["modes_of_the_last_batch"] = torch.bincount(out["aug"]["mode"].long(), minlength=4).tolist()
+        rec["refused"] = int((out["aug_status"] & 2).ne(0).sum())
+    torch.cuda.synchronize()
+    rec["augmented_over_annotated_graph"] = rec["prepare_augmented_graph_ms"] / rec["prepare_annotated_graph_ms"]
+    line = json.dumps(rec)
+    print(line, flush=True)
+    out = args.out or os.path.join(ROOT, "profiles", "prep_augment_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--device-only", action="store_true", help="skip the host path and the model: only prepare() and uncrop() of the two input forms")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     ap.add_argument("--annotated", action="store_true", help="only: prepare_annotated beside prepare on the same frames; writes profiles/prep_annot_bench.json")
+    ap.add_argument("--augmented", action="store_true", help="only: prepare_augmented (drawn parameters) beside prepare_annotated; writes profiles/prep_augment_bench.json")
     args = ap.parse_args()
     if args.annotated:
         return annotated(args)
+    if args.augmented:
+        return augmented(args)
     rec = {"tool": "prep_bench", "B": B, "reps": args.reps}
     if not args.device_only:  # before the GPU is initialised: the pool forks
         single, pooled = host_times()
