@@ -17,6 +17,11 @@
 // The host path is the yardstick (tests/test_preprocess_gpu.py): integer decisions and both images are bit-equal to it.  Everything that decides an integer
 // is computed in double in the HOST'S operation order, and the whole file is compiled with floating-point contraction OFF (the Makefile's -ffp-contract=on
 // would fuse `a * b + c`, which numpy rounds twice); float32 divisions are IEEE divisions.
+//
+// The three crop kernels (prep_crop_kernel, prep_annot_kernel, prep_augment_kernel) are three launches and share their steps as functions: prep_frame (the
+// stored frame of a sample), prep_publish (the per-sample small outputs, from one lane), prep_gather (the z-clamped crop into LDS), prep_normalize_f32 (the
+// normalize_depth rule), the LDS plans PREP_LDS_* (read by a kernel and by its launcher) and prep_crop_args (the launchers' common argument checks); the two
+// dataset kernels also annot_joint_xyz, annot_centre_geom and prep_label_to_image (normalised label -> joint_img).
 #include "kpf_common.h"
 
 #pragma clang fp contract(off)
@@ -167,19 +172,31 @@ __host__ __device__ inline unsigned short prep_zclamp(unsigned short v, const Pr
   return v;
 }
 
-// normalize_depth on one pixel (premax: the maximum of the z-clamped S x S crop), float32 like the host
+// normalize_depth / normalize_img on one pixel (premax: the maximum of the z-clamped S x S crop), float32 like the host
+__host__ __device__ inline float prep_normalize_f32(float v, float premax, float far, float near, float comz, float halfz) {
+  if (v == premax) v = far;
+  if (v == 0.0f) v = far;
+  if (v >= far) v = far;
+  if (v <= near) v = near;
+  return prep_fdiv(v - comz, halfz);
+}
+// ... on the sensor's uint16 values, which float holds exactly
 __host__ __device__ inline float prep_normalize(unsigned short raw, unsigned short premax, const PrepGeom& g) {
-  float v = (float)raw;
-  if (raw == premax) v = g.far;
-  if (v == 0.0f) v = g.far;
-  if (v >= g.far) v = g.far;
-  if (v <= g.near) v = g.near;
-  v = v - g.comz;
-#ifdef __HIP_DEVICE_COMPILE__
-  return __fdiv_rn(v, g.halfz);
-#else
-  return v / g.halfz;
-#endif
+  return prep_normalize_f32((float)raw, (float)premax, g.far, g.near, g.comz, g.halfz);
+}
+
+// The tail of the dataset protocol's labels: the label normalised by the half cube (l0, l1, l2; double from here on: the reference's cube is an integer or
+// float64 array) -> the point -> its projection, stored as float -> transformPoints2D with M = (scale, m02, m12) -> joint_img.  hx: cube[0] / 2; ctr: the
+// float centre
+__host__ __device__ inline void prep_label_to_image(double l0, double l1, double l2, double hx, const float* ctr, float fx, float fy, float fu, float fv,
+                                                    double scale, double m02, double m12, int S, float* joint_img) {
+  const double px = l0 * hx + (double)ctr[0], py = l1 * hx + (double)ctr[1], pz = l2 * hx + (double)ctr[2];  // curLabel * (cube[0] / 2.0) + com3D
+  const float u = (float)(px * (double)fx / pz + (double)fu), v = (float)(py * (double)fy / pz + (double)fv), d = (float)pz;
+  const float cu = (float)(scale * (double)u + m02), cv = (float)(scale * (double)v + m12);  // transformPoints2D, stored as float
+  const float half = (float)((double)S / 2.0);
+  joint_img[0] = prep_fdiv(cu, half) - 1.0f;
+  joint_img[1] = prep_fdiv(cv, half) - 1.0f;
+  joint_img[2] = (float)((double)(d - ctr[2]) / hx);
 }
 
 // ---- preprocess.depth_to_pcl for one pixel of the normalised crop: false = background; else the cube-normalised point clipped to [-1, 1]
@@ -211,6 +228,37 @@ __host__ __device__ inline unsigned long long prep_key(unsigned base, unsigned i
   return ((unsigned long long)h1 << 32) | ((unsigned long long)(h2 & 15u) << 28) | (unsigned long long)(cand << 14) | (unsigned long long)pix;
 }
 
+// ---- kpf_prep_augment_u16: everything one lane decides about a sample's augmentation (aug_geometry)
+struct AugGeom {
+  int warp;            // the RGB crop's warp: 0 none, 1 perspective (Ai), 2 affine (Ai[0..5] = i00 i01 i02 i10 i11 i12)
+  int warp_depth;      // the depth crop's: the same, or 0 for an all-zero crop
+  int zthresh;         // recropHand's z-threshold follows the depth warp
+  int lab;             // labels: 0 unchanged, 1 shifted by the centre's move, 2 rotated in the image plane
+  int has_color, status;
+  float zs, ze;                          // the z-threshold's planes
+  float far, near, comz, halfz, premax;  // normalize_img's float scalars (of the NEW centre and cube) and the pre-augmentation maximum
+  float c3old[3], center[3], comu, comv; // back-projected old / final centre; the old centre in the image
+  double Ai[9], c, s;
+  double hx, hz;                         // new_cube[0] / 2, new_cube[2] / 2
+  double scale, m02, m12;                // Mnew
+  double color[3];
+};
+
+// ---- the LDS plan of a crop kernel, read by the kernel and by its launcher: a front slot at 0 (prep_crop_kernel: the box reduction's [4][PREP_NW] 64-bit
+// sums; the dataset kernels: float xyz of up to 64 joints + the centre they are normalised by), the PrepGeom, the AugGeom (prep_augment_kernel), the
+// [PREP_NW] wave maxima and the z-clamped crop [S * S] uint16.  Every slot but the last two is a 16-byte multiple.
+constexpr int ANNOT_XYZ = 65 * 3;
+constexpr int ANNOT_XYZ_BYTES = 800, PREP_GEOM_BYTES = 256, AUG_GEOM_BYTES = 320;
+struct PrepLds {
+  int geom, aug, wmax, crop;  // byte offsets
+  constexpr size_t bytes(int S) const { return (size_t)crop + (size_t)S * S * 2; }
+};
+constexpr PrepLds prep_lds(int front, int aug) { return {front, front + PREP_GEOM_BYTES, front + PREP_GEOM_BYTES + aug, front + PREP_GEOM_BYTES + aug + PREP_NW * 4}; }
+constexpr PrepLds PREP_LDS_CROP = prep_lds(4 * PREP_NW * 8, 0), PREP_LDS_ANNOT = prep_lds(ANNOT_XYZ_BYTES, 0), PREP_LDS_AUGMENT = prep_lds(ANNOT_XYZ_BYTES, AUG_GEOM_BYTES);
+static_assert(sizeof(PrepGeom) <= PREP_GEOM_BYTES && PREP_GEOM_BYTES % 16 == 0, "PrepGeom outgrew its LDS slot");
+static_assert(ANNOT_XYZ * 4 <= ANNOT_XYZ_BYTES && ANNOT_XYZ_BYTES % 16 == 0, "the joints outgrew their LDS slot");
+static_assert(sizeof(AugGeom) <= AUG_GEOM_BYTES && AUG_GEOM_BYTES % 16 == 0, "AugGeom outgrew its LDS slot");
+
 #ifdef __HIPCC__
 // tuning aid: wall-clock stamps (100 MHz) of every workgroup's thread 0 at phase boundaries, [B][8] slots set by kpf_prep_set_stamps (NULL = off, the default):
 // crop 0 start, 1 geometry published, 2 gather done, 3 end; sample 4 start, 5 candidates compacted and keyed, 6 sorted, 7 end
@@ -224,6 +272,42 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// Stored frame of sample b: b itself, or frame_index[b] of F (several tracks on one frame), clamped so that no index reads out of bounds
+struct PrepFrame {
+  const unsigned short* dep;
+  const unsigned char* col;
+};
+__device__ __forceinline__ PrepFrame prep_frame(int b, const int* frame_index, int F, int Hs, int Ws, const unsigned short* depth, const unsigned char* rgb) {
+  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
+  return {depth + (size_t)f * Hs * Ws, rgb + (size_t)f * Hs * Ws * 3};
+}
+
+// One lane: the per-sample small outputs of a crop kernel.  ctr / com3 / cube3 and M = (scale, m02, m12) are the sample's FINAL ones (the augmented ones
+// in prep_augment_kernel), the bounds g's (the base crop's); the intrinsics come as double values, which hold a float exactly (cam_out is their rounding to
+// float: the value itself where they were floats).  cam64 / cube64 may be NULL.
+__device__ __forceinline__ void prep_publish(int b, const PrepGeom& g, const float* ctr, const double* com3, const double* cube3, double fx, double fy, double fu,
+                                             double fv, double scale, double m02, double m12, float* center, double* com, float* cube_out, float* cam_out,
+                                             double* cam64, double* cube64, float* M, double* Md, int* bounds) {
+  for (int k = 0; k < 3; ++k) {
+    center[3 * b + k] = ctr[k];
+    com[3 * b + k] = com3[k];
+    cube_out[3 * b + k] = (float)cube3[k];
+    if (cube64) cube64[3 * b + k] = cube3[k];
+  }
+  const double c[4] = {fx, fy, fu, fv};
+  for (int k = 0; k < 4; ++k) {
+    cam_out[4 * b + k] = (float)c[k];
+    if (cam64) cam64[4 * b + k] = c[k];
+  }
+  const double m[9] = {scale, 0.0, m02, 0.0, scale, m12, 0.0, 0.0, 1.0};
+  for (int k = 0; k < 9; ++k) {
+    Md[9 * b + k] = m[k];
+    M[9 * b + k] = (float)m[k];
+  }
+  const int bo[6] = {g.xs, g.xe, g.ys, g.ye, g.szw, g.szh};
+  for (int k = 0; k < 6; ++k) bounds[6 * b + k] = bo[k];
 }
 
 // Offset, in the stored window, of the frame pixel behind crop pixel (oyp, oxp): false = letterbox border, outside the frame or outside the window (all read
@@ -293,16 +377,13 @@ __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char*
                                                             float* __restrict__ cube_out, float* __restrict__ cam_out, double* __restrict__ com,
                                                             int* __restrict__ bounds, double* __restrict__ Md) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* red = reinterpret_cast<unsigned long long*>(smem);            // [4][PREP_NW]
-  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + 4 * PREP_NW * 8);               // 512: 16-byte aligned
-  unsigned* wmax = reinterpret_cast<unsigned*>(smem + 4 * PREP_NW * 8 + 256);       // [PREP_NW]
-  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + 4 * PREP_NW * 8 + 256 + PREP_NW * 4);  // [S * S]
-  static_assert(sizeof(PrepGeom) <= 256, "PrepGeom outgrew its LDS slot");
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(smem);  // [4][PREP_NW]
+  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + PREP_LDS_CROP.geom);
+  unsigned* wmax = reinterpret_cast<unsigned*>(smem + PREP_LDS_CROP.wmax);
+  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + PREP_LDS_CROP.crop);
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  // stored frame of this sample: b itself, or frame_index[b] of F (several tracks on one frame), clamped so that no index reads out of bounds
-  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
-  const unsigned short* dep = depth + (size_t)f * Hs * Ws;
-  const unsigned char* col = rgb + (size_t)f * Hs * Ws * 3;
+  const PrepFrame fr = prep_frame(b, frame_index, F, Hs, Ws, depth, rgb);
+  const unsigned short* dep = fr.dep;
   const double* bb = bbox + 4 * b;
 
   // 1. centre of mass over the box: pixels outside the stored window read as 0, which is invalid depth, so only the intersection is visited
@@ -338,38 +419,21 @@ __global__ __launch_bounds__(PREP_NT) void prep_crop_kernel(const unsigned char*
     for (int q = 0; q < 4; ++q)
       for (int w = 0; w < PREP_NW; ++w) a[q] += red[q * PREP_NW + w];
     PrepGeom g;
-    prep_geom(a[0], a[1], a[2], a[3], bx, bb, cam + 4 * b, cube + 3 * b, S, g);
+    const double* cm = cam + 4 * b;
+    prep_geom(a[0], a[1], a[2], a[3], bx, bb, cm, cube + 3 * b, S, g);
     *gs = g;
-    for (int k = 0; k < 3; ++k) {
-      center[3 * b + k] = g.center[k];
-      com[3 * b + k] = g.com[k];
-      cube_out[3 * b + k] = (float)cube[3 * b + k];
-    }
-    for (int k = 0; k < 4; ++k) cam_out[4 * b + k] = (float)cam[4 * b + k];
-    const double m[9] = {g.scale, 0.0, g.m02, 0.0, g.scale, g.m12, 0.0, 0.0, 1.0};
-    for (int k = 0; k < 9; ++k) {
-      Md[9 * b + k] = m[k];
-      M[9 * b + k] = (float)m[k];
-    }
-    int* bo = bounds + 6 * b;
-    bo[0] = g.xs;
-    bo[1] = g.xe;
-    bo[2] = g.ys;
-    bo[3] = g.ye;
-    bo[4] = g.szw;
-    bo[5] = g.szh;
+    prep_publish(b, g, g.center, g.com, cube + 3 * b, cm[0], cm[1], cm[2], cm[3], g.scale, g.m02, g.m12, center, com, cube_out, cam_out, nullptr, nullptr, M, Md,
+                 bounds);
   }
   __syncthreads();
   const PrepGeom g = *gs;
   PREP_STAMP(1);
   // 3. gather, 4. normalize_depth
-  prep_gather_normalize(g, dep, col, 0, Hs, Ws, ox, oy, H, W, S, crop, wmax, img, img_rgb);
+  prep_gather_normalize(g, dep, fr.col, 0, Hs, Ws, ox, oy, H, W, S, crop, wmax, img, img_rgb);
   PREP_STAMP(3);
 }
 
 // kpf_prep_annot_u16: the crop by the dataset protocol (preprocess.prepare_annotated).  Phase 0 replaces the box reduction: the centre comes from the annotation.
-constexpr int ANNOT_XYZ = 65 * 3;           // float xyz of up to 64 joints + the centre they are normalised by
-constexpr int ANNOT_XYZ_BYTES = 800;        // (16-byte multiple)
 
 // Phase 0a of the dataset protocol, one lane per joint: the joint's xyz in float.  through_image: DexYCB's item takes the joints through the image and back,
 // mirrored or not; HO3D's item (the one with a given centre) uses them as they are
@@ -414,15 +478,12 @@ __global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char
                                                              double* __restrict__ Md, float* __restrict__ joint, float* __restrict__ joint_img,
                                                              double* __restrict__ cam64) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  static_assert(ANNOT_XYZ * 4 <= ANNOT_XYZ_BYTES && ANNOT_XYZ_BYTES % 16 == 0, "the joints outgrew their LDS slot");
-  float* xyz = reinterpret_cast<float*>(smem);                                                          // [65][3]
-  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + ANNOT_XYZ_BYTES);                                   // 16-byte aligned
-  unsigned* wmax = reinterpret_cast<unsigned*>(smem + ANNOT_XYZ_BYTES + 256);                           // [PREP_NW]
-  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + ANNOT_XYZ_BYTES + 256 + PREP_NW * 4);  // [S * S]
+  float* xyz = reinterpret_cast<float*>(smem);  // [65][3]
+  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + PREP_LDS_ANNOT.geom);
+  unsigned* wmax = reinterpret_cast<unsigned*>(smem + PREP_LDS_ANNOT.wmax);
+  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + PREP_LDS_ANNOT.crop);
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
-  const unsigned short* dep = depth + (size_t)f * Hs * Ws;
-  const unsigned char* col = rgb + (size_t)f * Hs * Ws * 3;
+  const PrepFrame fr = prep_frame(b, frame_index, F, Hs, Ws, depth, rgb);
   const int mir = mirror[b] ? 1 : 0;
   const float fx = cam[4 * b], fy = cam[4 * b + 1], fu = cam[4 * b + 2], fv = cam[4 * b + 3];
   PREP_STAMP(0);
@@ -435,45 +496,17 @@ __global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char
     PrepGeom g;
     annot_centre_geom(xyz, center_xyz ? center_xyz + 3 * b : nullptr, J, cam + 4 * b, cube + 3 * b, S, g);
     *gs = g;
-    for (int k = 0; k < 3; ++k) {
-      center[3 * b + k] = g.center[k];
-      com[3 * b + k] = g.com[k];
-      cube_out[3 * b + k] = (float)cube[3 * b + k];
-    }
-    for (int k = 0; k < 4; ++k) {
-      cam_out[4 * b + k] = cam[4 * b + k];
-      cam64[4 * b + k] = (double)cam[4 * b + k];
-    }
-    const double m[9] = {g.scale, 0.0, g.m02, 0.0, g.scale, g.m12, 0.0, 0.0, 1.0};
-    for (int k = 0; k < 9; ++k) {
-      Md[9 * b + k] = m[k];
-      M[9 * b + k] = (float)m[k];
-    }
-    int* bo = bounds + 6 * b;
-    bo[0] = g.xs;
-    bo[1] = g.xe;
-    bo[2] = g.ys;
-    bo[3] = g.ye;
-    bo[4] = g.szw;
-    bo[5] = g.szh;
+    prep_publish(b, g, g.center, g.com, cube + 3 * b, fx, fy, fu, fv, g.scale, g.m02, g.m12, center, com, cube_out, cam_out, cam64, nullptr, M, Md, bounds);
   }
   __syncthreads();
   const PrepGeom g = *gs;
   PREP_STAMP(1);
-  // 0c. the labels, one lane per joint
+  // 0c. the labels, one lane per joint: float up to the division by the half cube (a float32 division here), double from there
   if (wv == 0 && lane < J) {
     float lab[3] = {0.f, 0.f, 0.f}, uvd[3] = {0.f, 0.f, 0.f};
     if (joints) {
       for (int k = 0; k < 3; ++k) lab[k] = prep_fdiv(xyz[3 * lane + k] - xyz[3 * 64 + k], g.halfz);
-      // curLabel * (cube[0] / 2.0) + com3D: the reference's cube is an integer array, so this and the projection are double
-      const double hx = cube[3 * b] / 2.0;
-      const double px = (double)lab[0] * hx + (double)g.center[0], py = (double)lab[1] * hx + (double)g.center[1], pz = (double)lab[2] * hx + (double)g.center[2];
-      const float u = (float)(px * (double)fx / pz + (double)fu), v = (float)(py * (double)fy / pz + (double)fv), d = (float)pz;
-      const float cu = (float)(g.scale * (double)u + g.m02), cv = (float)(g.scale * (double)v + g.m12);  // transformPoints2D, stored as float
-      const float half = (float)((double)S / 2.0);
-      uvd[0] = prep_fdiv(cu, half) - 1.0f;
-      uvd[1] = prep_fdiv(cv, half) - 1.0f;
-      uvd[2] = (float)((double)(d - g.center[2]) / hx);
+      prep_label_to_image((double)lab[0], (double)lab[1], (double)lab[2], cube[3 * b] / 2.0, g.center, fx, fy, fu, fv, g.scale, g.m02, g.m12, S, uvd);
     }
     for (int k = 0; k < 3; ++k) {
       joint[((size_t)b * J + lane) * 3 + k] = lab[k];
@@ -481,26 +514,11 @@ __global__ __launch_bounds__(PREP_NT) void prep_annot_kernel(const unsigned char
     }
   }
   // 3. gather, 4. normalize_depth
-  prep_gather_normalize(g, dep, col, mir, Hs, Ws, ox, oy, H, W, S, crop, wmax, img, img_rgb);
+  prep_gather_normalize(g, fr.dep, fr.col, mir, Hs, Ws, ox, oy, H, W, S, crop, wmax, img, img_rgb);
   PREP_STAMP(3);
 }
 
-// ---- kpf_prep_augment_u16: the training item (preprocess.prepare_augmented).  Everything one lane decides about a sample's augmentation:
-struct AugGeom {
-  int warp;            // the RGB crop's warp: 0 none, 1 perspective (Ai), 2 affine (Ai[0..5] = i00 i01 i02 i10 i11 i12)
-  int warp_depth;      // the depth crop's: the same, or 0 for an all-zero crop
-  int zthresh;         // recropHand's z-threshold follows the depth warp
-  int lab;             // labels: 0 unchanged, 1 shifted by the centre's move, 2 rotated in the image plane
-  int has_color, status;
-  float zs, ze;                          // the z-threshold's planes
-  float far, near, comz, halfz, premax;  // normalize_img's float scalars (of the NEW centre and cube) and the pre-augmentation maximum
-  float c3old[3], center[3], comu, comv; // back-projected old / final centre; the old centre in the image
-  double Ai[9], c, s;
-  double hx, hz;                         // new_cube[0] / 2, new_cube[2] / 2
-  double scale, m02, m12;                // Mnew
-  double color[3];
-};
-
+// ---- kpf_prep_augment_u16: the training item (preprocess.prepare_augmented)
 __host__ __device__ inline bool aug_finite(double v) { return v - v == 0.0; }
 
 // loader.comToTransform for centre cuvd and cube `size`: the bounds in float (prep_geom_f32), the letterbox offset from the UNTRUNCATED resize size
@@ -691,7 +709,6 @@ __host__ __device__ inline double aug_uniform(unsigned base, unsigned i) {
   return (double)(((unsigned long long)w0 << 21) | (unsigned long long)(w1 >> 11)) * 1.1102230246251565e-16;  // 2^-53
 }
 
-constexpr int AUG_GEOM_BYTES = 320;
 __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned char* __restrict__ rgb, const unsigned short* __restrict__ depth,
                                                                const int* __restrict__ frame_index, int F, const float* __restrict__ joints,
                                                                const float* __restrict__ cam, const float* __restrict__ center_xyz,
@@ -705,16 +722,14 @@ __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned ch
                                                                float* __restrict__ joint_img, double* __restrict__ cam64, double* __restrict__ cube64,
                                                                int* __restrict__ aug_status) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  static_assert(sizeof(AugGeom) <= AUG_GEOM_BYTES && AUG_GEOM_BYTES % 16 == 0, "AugGeom outgrew its LDS slot");
-  float* xyz = reinterpret_cast<float*>(smem);                                             // [65][3]
-  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + ANNOT_XYZ_BYTES);                      // 16-byte aligned
-  AugGeom* as = reinterpret_cast<AugGeom*>(smem + ANNOT_XYZ_BYTES + 256);
-  unsigned* wmax = reinterpret_cast<unsigned*>(smem + ANNOT_XYZ_BYTES + 256 + AUG_GEOM_BYTES);  // [PREP_NW]
-  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + ANNOT_XYZ_BYTES + 256 + AUG_GEOM_BYTES + PREP_NW * 4);  // [S * S]
+  float* xyz = reinterpret_cast<float*>(smem);  // [65][3]
+  PrepGeom* gs = reinterpret_cast<PrepGeom*>(smem + PREP_LDS_AUGMENT.geom);
+  AugGeom* as = reinterpret_cast<AugGeom*>(smem + PREP_LDS_AUGMENT.aug);
+  unsigned* wmax = reinterpret_cast<unsigned*>(smem + PREP_LDS_AUGMENT.wmax);
+  unsigned short* crop = reinterpret_cast<unsigned short*>(smem + PREP_LDS_AUGMENT.crop);
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6, P = S * S;
-  const int f = frame_index ? min(max(frame_index[b], 0), F - 1) : b;
-  const unsigned short* dep = depth + (size_t)f * Hs * Ws;
-  const unsigned char* col = rgb + (size_t)f * Hs * Ws * 3;
+  const PrepFrame fr = prep_frame(b, frame_index, F, Hs, Ws, depth, rgb);
+  const unsigned char* col = fr.col;
   const int mir = mirror[b] ? 1 : 0;
   const float fx = cam[4 * b], fy = cam[4 * b + 1], fu = cam[4 * b + 2], fv = cam[4 * b + 3];
   PREP_STAMP(0);
@@ -730,7 +745,7 @@ __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned ch
   const PrepGeom g = *gs;
   PREP_STAMP(1);
   // 2. the z-clamped base depth crop into LDS and its maximum (RGB is read through the warp in phase 5)
-  const unsigned premax = prep_gather(g, dep, col, mir, Hs, Ws, ox, oy, H, W, S, crop, wmax, nullptr);
+  const unsigned premax = prep_gather(g, fr.dep, col, mir, Hs, Ws, ox, oy, H, W, S, crop, wmax, nullptr);
   // 3. one lane: the augmented geometry, and the sample's small outputs
   if (t == 0) {
     AugGeom a;
@@ -738,28 +753,8 @@ __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned ch
     float ncom[3];
     aug_geometry(g, cam + 4 * b, cube + 3 * b, mode[b], off + 3 * b, sc[b], rot[b], rot_cs + 2 * b, color ? color + 3 * b : nullptr, premax, S, a, ncube, ncom);
     *as = a;
-    for (int k = 0; k < 3; ++k) {
-      center[3 * b + k] = a.center[k];
-      com[3 * b + k] = (double)ncom[k];
-      cube_out[3 * b + k] = (float)ncube[k];
-      cube64[3 * b + k] = ncube[k];
-    }
-    for (int k = 0; k < 4; ++k) {
-      cam_out[4 * b + k] = cam[4 * b + k];
-      cam64[4 * b + k] = (double)cam[4 * b + k];
-    }
-    const double m[9] = {a.scale, 0.0, a.m02, 0.0, a.scale, a.m12, 0.0, 0.0, 1.0};
-    for (int k = 0; k < 9; ++k) {
-      Md[9 * b + k] = m[k];
-      M[9 * b + k] = (float)m[k];
-    }
-    int* bo = bounds + 6 * b;
-    bo[0] = g.xs;
-    bo[1] = g.xe;
-    bo[2] = g.ys;
-    bo[3] = g.ye;
-    bo[4] = g.szw;
-    bo[5] = g.szh;
+    const double ncom64[3] = {(double)ncom[0], (double)ncom[1], (double)ncom[2]};
+    prep_publish(b, g, a.center, ncom64, ncube, fx, fy, fu, fv, a.scale, a.m02, a.m12, center, com, cube_out, cam_out, cam64, cube64, M, Md, bounds);
     aug_status[b] = a.status;
   }
   __syncthreads();
@@ -768,8 +763,8 @@ __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned ch
     const int lab = as->lab;
     float l[3];
     for (int k = 0; k < 3; ++k) l[k] = xyz[3 * lane + k] - xyz[3 * 64 + k];
+    const float cn[3] = {as->center[0], as->center[1], as->center[2]};
     if (lab == 1) {
-      const float cn[3] = {as->center[0], as->center[1], as->center[2]};
       for (int k = 0; k < 3; ++k) l[k] = (l[k] + as->c3old[k]) - cn[k];
     } else if (lab == 2) {
       const float q0 = l[0] + as->c3old[0], q1 = l[1] + as->c3old[1], q2 = l[2] + as->c3old[2];
@@ -785,18 +780,11 @@ __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned ch
     }
     const double hx = as->hx, hz = as->hz;
     const double l0 = (double)l[0] / hz, l1 = (double)l[1] / hz, l2 = (double)l[2] / hz;
-    const double px = l0 * hx + (double)as->center[0], py = l1 * hx + (double)as->center[1], pz = l2 * hx + (double)as->center[2];
-    const float u = (float)(px * (double)fx / pz + (double)fu), v = (float)(py * (double)fy / pz + (double)fv), d = (float)pz;
-    const float cu = (float)(as->scale * (double)u + as->m02), cv = (float)(as->scale * (double)v + as->m12);
-    const float half = (float)((double)S / 2.0);
     float* jo = joint + ((size_t)b * J + lane) * 3;
-    float* ji = joint_img + ((size_t)b * J + lane) * 3;
     jo[0] = (float)l0;
     jo[1] = (float)l1;
     jo[2] = (float)l2;
-    ji[0] = prep_fdiv(cu, half) - 1.0f;
-    ji[1] = prep_fdiv(cv, half) - 1.0f;
-    ji[2] = (float)((double)(d - as->center[2]) / hx);
+    prep_label_to_image(l0, l1, l2, hx, cn, fx, fy, fu, fv, as->scale, as->m02, as->m12, S, joint_img + ((size_t)b * J + lane) * 3);
   }
   // 5. every destination pixel through the inverse map: depth from LDS (z-threshold, premax rule, normalisation in float), RGB from the frame
   const int warp = as->warp, warp_depth = as->warp_depth, zthresh = as->zthresh, has_color = as->has_color;
@@ -820,11 +808,7 @@ __global__ __launch_bounds__(PREP_NT) void prep_augment_kernel(const unsigned ch
       if (m1) v = zs;
       if (m2) v = 0.f;
     }
-    if (v == pmx) v = far;
-    if (v == 0.f) v = far;
-    if (v >= far) v = far;
-    if (v <= near) v = near;
-    img[(size_t)b * P + p] = __fdiv_rn(v - comz, halfz);
+    img[(size_t)b * P + p] = prep_normalize_f32(v, pmx, far, near, comz, halfz);
     float c3[3] = {0.f, 0.f, 0.f};
     size_t so;
     if (in && prep_window_offset(g, Y, X, mir, Hs, Ws, ox, oy, H, W, so))
@@ -1043,9 +1027,6 @@ __global__ __launch_bounds__(256) void prep_uncrop_mirror_kernel(const float* __
 }
 #endif  // __HIPCC__
 
-constexpr size_t kCropFixedLds = 4 * PREP_NW * 8 + 256 + PREP_NW * 4;
-constexpr size_t kAnnotFixedLds = 800 + 256 + PREP_NW * 4;  // ANNOT_XYZ_BYTES + the geometry + the wave maxima
-constexpr size_t kAugFixedLds = 800 + 256 + 320 + PREP_NW * 4;  // kAnnotFixedLds + AUG_GEOM_BYTES
 inline int host_pow2ceil(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -1056,19 +1037,25 @@ inline int host_pow2ceil(int v) {
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// what the launchers of the three crop kernels check alike (has_joints: the dataset kernels, one lane per joint)
+static int prep_crop_args(const char* name, int B, bool has_joints, int J, const int* frame_index, int F, int Hs, int Ws, int x0, int y0, int H, int W, int S) {
+  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
+  KPF_REQUIRE(!has_joints || (J > 0 && J <= 64), "%s: J = %d joints (one lane of a wave64 per joint: 1 .. 64)", name, J);
+  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
+  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
+  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
+  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
+  return KPF_OK;
+}
+
 // the one launch behind kpf_prep_crop_u16 (frame_index NULL, F = B: sample b reads frame b) and kpf_prep_crop_u16_indexed
 static int prep_crop_launch(const char* name, const unsigned char* rgb, const unsigned short* depth, const int* frame_index, int F, const double* bbox,
                             const double* cam, const double* cube, int B, int Hs, int Ws, int x0, int y0, int H, int W, int S, float* img, float* img_rgb,
                             float* center, float* M, float* cube_out, float* cam_para, double* com, int* bounds, double* M64, void* stream) {
   KPF_REQUIRE(rgb && depth && bbox && cam && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64, "%s: null pointer argument", name);
-  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
-  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
-  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
-  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
-  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
-  const size_t lds = kCropFixedLds + (size_t)S * S * 2;
-  hipLaunchKernelGGL(prep_crop_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, frame_index, F, bbox, cam, cube, Hs, Ws, x0, y0, H, W, S, img, img_rgb,
-                     center, M, cube_out, cam_para, com, bounds, M64);
+  if (const int rc = prep_crop_args(name, B, false, 0, frame_index, F, Hs, Ws, x0, y0, H, W, S)) return rc;
+  hipLaunchKernelGGL(prep_crop_kernel, dim3(B), dim3(PREP_NT), PREP_LDS_CROP.bytes(S), ST(stream), rgb, depth, frame_index, F, bbox, cam, cube, Hs, Ws, x0, y0, H, W, S,
+                     img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64);
   return kpf_check_launch(name);
 }
 
@@ -1120,15 +1107,9 @@ extern "C" int kpf_prep_annot_u16(const unsigned char* rgb, const unsigned short
   KPF_REQUIRE(rgb && depth && cam32 && mirror && cube && img && img_rgb && center && M && cube_out && cam_para && com && bounds && M64 && joint && joint_img && cam64,
               "%s: null pointer argument", name);
   KPF_REQUIRE(joints_mm || center_xyz, "%s: neither joints nor a centre (nothing to crop around)", name);
-  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
-  KPF_REQUIRE(J > 0 && J <= 64, "%s: J = %d joints (one lane of a wave64 per joint: 1 .. 64)", name, J);
-  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
-  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
-  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
-  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
-  const size_t lds = kAnnotFixedLds + (size_t)S * S * 2;
-  hipLaunchKernelGGL(prep_annot_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, frame_index, F, joints_mm, cam32, center_xyz, mirror, cube, J, Hs, Ws, x0,
-                     y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64, joint, joint_img, cam64);
+  if (const int rc = prep_crop_args(name, B, true, J, frame_index, F, Hs, Ws, x0, y0, H, W, S)) return rc;
+  hipLaunchKernelGGL(prep_annot_kernel, dim3(B), dim3(PREP_NT), PREP_LDS_ANNOT.bytes(S), ST(stream), rgb, depth, frame_index, F, joints_mm, cam32, center_xyz, mirror, cube,
+                     J, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64, joint, joint_img, cam64);
   return kpf_check_launch(name);
 }
 
@@ -1153,16 +1134,10 @@ extern "C" int kpf_prep_augment_u16(const unsigned char* rgb, const unsigned sho
               "%s: null pointer argument", name);
   KPF_REQUIRE(joints_mm, "%s: null joints (a training item has labels)", name);
   KPF_REQUIRE(mode && off && sc && rot && rot_cs, "%s: null augmentation parameter (mode, off, sc, rot and rot_cs are required; color may be NULL)", name);
-  KPF_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, "%s: bad shape (B %d, window %d x %d, frame %d x %d)", name, B, Hs, Ws, H, W);
-  KPF_REQUIRE(J > 0 && J <= 64, "%s: J = %d joints (one lane of a wave64 per joint: 1 .. 64)", name, J);
-  KPF_REQUIRE(F > 0 && (frame_index || F >= B), "%s: %d stored frames for %d samples%s", name, F, B, frame_index ? "" : " without a frame index");
-  KPF_REQUIRE(x0 >= 0 && y0 >= 0 && x0 + Ws <= W && y0 + Hs <= H, "%s: the %d x %d window at (%d, %d) leaves the %d x %d frame", name, Ws, Hs, x0, y0, W, H);
-  KPF_REQUIRE((long)Hs * Ws < (1L << 30), "%s: window of %d x %d pixels is too large", name, Hs, Ws);
-  KPF_REQUIRE(S > 0 && S * S <= PREP_MAX_PIX, "%s: S = %d unsupported (S * S <= %d: the LDS plan of kpf_prep_pcl_sample)", name, S, PREP_MAX_PIX);
-  const size_t lds = kAugFixedLds + (size_t)S * S * 2;
-  hipLaunchKernelGGL(prep_augment_kernel, dim3(B), dim3(PREP_NT), lds, ST(stream), rgb, depth, frame_index, F, joints_mm, cam32, center_xyz, mirror, cube, mode, off, sc,
-                     rot, rot_cs, color, J, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64, joint, joint_img, cam64, cube64,
-                     aug_status);
+  if (const int rc = prep_crop_args(name, B, true, J, frame_index, F, Hs, Ws, x0, y0, H, W, S)) return rc;
+  hipLaunchKernelGGL(prep_augment_kernel, dim3(B), dim3(PREP_NT), PREP_LDS_AUGMENT.bytes(S), ST(stream), rgb, depth, frame_index, F, joints_mm, cam32, center_xyz, mirror,
+                     cube, mode, off, sc, rot, rot_cs, color, J, Hs, Ws, x0, y0, H, W, S, img, img_rgb, center, M, cube_out, cam_para, com, bounds, M64, joint, joint_img,
+                     cam64, cube64, aug_status);
   return kpf_check_launch(name);
 }
 

@@ -247,6 +247,57 @@ def _crop_to_bounds(img, bounds, dsize, thresh_z):
     return ret, np.dot(off, np.dot(scale, trans))
 
 
+def _annotated_base(where, rgb, depth, joints_mm, cam, mirror, center_xyz, cube, S):
+    """What prepare_annotated and prepare_augmented (`where`, for the errors) do alike up to the two crops: the float32 intrinsics, the mirror, the joints'
+    round trip through the image, the centre and its projection, the bounds and both crops.  Returns (cam, W, joint_xyz, center_xyz, center_uvd, crop_rgb,
+    crop_d, M); joint_xyz is None without joints."""
+    rgb, depth = np.asarray(rgb), np.asarray(depth)
+    cam = tuple(np.float32(c) for c in cam)
+    if len(cam) != 4 or len(cube) != 3:
+        raise ValueError("%s: cam is (fx, fy, u0, v0) and cube three sizes in mm" % where)
+    W = depth.shape[1]
+    if mirror:
+        rgb, depth = rgb[:, ::-1].copy(), depth[:, ::-1].copy()
+    joint_xyz = None
+    if joints_mm is not None:
+        joints_mm = _f32(joints_mm)
+        if joints_mm.ndim != 2 or joints_mm.shape[1] != 3:
+            raise ValueError("%s: joints_mm must be [J][3] (got %s)" % (where, joints_mm.shape))
+        joint_xyz = joints_mm
+        if center_xyz is None or mirror:
+            # DexYCB's item takes the joints through the image and back, mirrored or not (an ulp from the annotation at times); HO3D's item, the one with
+            # a given centre, uses them as they are
+            joint_uvd = _project_f32(joints_mm, cam)
+            if mirror:
+                joint_uvd[:, 0] = np.float32(W) - joint_uvd[:, 0] - np.float32(1)
+            joint_xyz = _backproject_f32(joint_uvd, cam)
+    if center_xyz is None:
+        center_xyz = _mean_rows_f32(joint_xyz)
+    else:
+        center_xyz = _f32(center_xyz)
+        if center_xyz.shape != (3,):
+            raise ValueError("%s: center_xyz must be [3] (got %s)" % (where, center_xyz.shape))
+    center_uvd = _project_f32(center_xyz, cam)
+    bounds = annotated_bounds(center_uvd, cube, cam)
+    crop_rgb, _ = _crop_to_bounds(rgb, bounds, (S, S), thresh_z=False)
+    crop_d, M = _crop_to_bounds(depth, bounds, (S, S), thresh_z=True)
+    return cam, W, joint_xyz, center_xyz, center_uvd, crop_rgb, crop_d, M
+
+
+def _labels_to_image(lab64, hx, com3d, cam, M, S):
+    """The labels' tail, joint_img from the labels normalised by the half cube (float64 [J][3]): curLabel * (cube[0] / 2.0) + com3D with an int64 or float64
+    cube, so float64 from here to the stores into float32 arrays.  hx: cube[0] / 2.0."""
+    p = lab64 * hx + com3d.astype(np.float64)
+    fx, fy, fu, fv = (float(c) for c in cam)
+    uvd = np.stack([p[:, 0] * fx / p[:, 2] + fu, p[:, 1] * fy / p[:, 2] + fv, p[:, 2]], 1).astype(np.float32)
+    joint_img = uvd.copy()  # transformPoints2D: M . (u, v, 1) in float64, stored into the float32 array
+    joint_img[:, 0] = M[0, 0] * uvd[:, 0].astype(np.float64) + M[0, 2]
+    joint_img[:, 1] = M[1, 1] * uvd[:, 1].astype(np.float64) + M[1, 2]
+    joint_img[:, 0:2] = joint_img[:, 0:2] / np.float32(S / 2) - np.float32(1)
+    joint_img[:, 2] = (joint_img[:, 2] - com3d[2]).astype(np.float64) / hx
+    return joint_img
+
+
 def prepare_annotated(rgb, depth, joints_mm, cam, mirror=False, center_xyz=None, cube=(250, 250, 250), img_size=128, sample_num=1024, rng=None):
     """The reference's dataset items at test time (dataloader/loader.py:1113-1204 DexYCB, :1296-1416 HO3D; flip = 1): the crop around an ANNOTATED 3-D
     centre, left hands mirrored, and the labels.  joints_mm [J][3] float32 in camera space, mm, in the model's joint order (the caller applies
@@ -262,37 +313,8 @@ def prepare_annotated(rgb, depth, joints_mm, cam, mirror=False, center_xyz=None,
     rng = np.random.RandomState(0) if rng is None else rng
     if joints_mm is None and center_xyz is None:
         raise ValueError("prepare_annotated: neither joints nor a centre: nothing to crop around")
-    rgb, depth = np.asarray(rgb), np.asarray(depth)
-    cam = tuple(np.float32(c) for c in cam)
-    if len(cam) != 4 or len(cube) != 3:
-        raise ValueError("prepare_annotated: cam is (fx, fy, u0, v0) and cube three sizes in mm")
-    W = depth.shape[1]
-    if mirror:
-        rgb, depth = rgb[:, ::-1].copy(), depth[:, ::-1].copy()
-    joint_xyz = None
-    if joints_mm is not None:
-        joints_mm = _f32(joints_mm)
-        if joints_mm.ndim != 2 or joints_mm.shape[1] != 3:
-            raise ValueError("prepare_annotated: joints_mm must be [J][3] (got %s)" % (joints_mm.shape,))
-        joint_xyz = joints_mm
-        if center_xyz is None or mirror:
-            # DexYCB's item takes the joints through the image and back, mirrored or not (an ulp from the annotation at times); HO3D's item, the one with
-            # a given centre, uses them as they are
-            joint_uvd = _project_f32(joints_mm, cam)
-            if mirror:
-                joint_uvd[:, 0] = np.float32(W) - joint_uvd[:, 0] - np.float32(1)
-            joint_xyz = _backproject_f32(joint_uvd, cam)
-    if center_xyz is None:
-        center_xyz = _mean_rows_f32(joint_xyz)
-    else:
-        center_xyz = _f32(center_xyz)
-        if center_xyz.shape != (3,):
-            raise ValueError("prepare_annotated: center_xyz must be [3] (got %s)" % (center_xyz.shape,))
-    center_uvd = _project_f32(center_xyz, cam)
-    bounds = annotated_bounds(center_uvd, cube, cam)
-    dsize = (img_size, img_size)
-    crop_rgb, _ = _crop_to_bounds(rgb, bounds, dsize, thresh_z=False)
-    crop_d, M = _crop_to_bounds(depth, bounds, dsize, thresh_z=True)
+    cam, W, joint_xyz, center_xyz, center_uvd, crop_rgb, crop_d, M = _annotated_base("prepare_annotated", rgb, depth, joints_mm, cam, mirror, center_xyz, cube,
+                                                                                     img_size)
     img_n = normalize_depth(crop_d, center_uvd, cube)
     com3d = _backproject_f32(center_uvd, cam)
     half = np.float32(cube[2] / 2.0)
@@ -301,15 +323,7 @@ def prepare_annotated(rgb, depth, joints_mm, cam, mirror=False, center_xyz=None,
         joint, joint_img = np.zeros((J, 3), np.float32), np.zeros((J, 3), np.float32)
     else:
         joint = (joint_xyz - center_xyz) / half
-        # curLabel * (cube[0] / 2.0) + com3D with an int64 cube: float64 from here to the stores into float32 arrays
-        p = joint.astype(np.float64) * (cube[0] / 2.0) + com3d.astype(np.float64)
-        fx, fy, fu, fv = (float(c) for c in cam)
-        uvd = np.stack([p[:, 0] * fx / p[:, 2] + fu, p[:, 1] * fy / p[:, 2] + fv, p[:, 2]], 1).astype(np.float32)
-        joint_img = uvd.copy()  # transformPoints2D: M . (u, v, 1) in float64, stored into the float32 array
-        joint_img[:, 0] = M[0, 0] * uvd[:, 0].astype(np.float64) + M[0, 2]
-        joint_img[:, 1] = M[1, 1] * uvd[:, 1].astype(np.float64) + M[1, 2]
-        joint_img[:, 0:2] = joint_img[:, 0:2] / np.float32(img_size / 2) - np.float32(1)
-        joint_img[:, 2] = (joint_img[:, 2] - com3d[2]).astype(np.float64) / (cube[0] / 2.0)
+        joint_img = _labels_to_image(joint.astype(np.float64), cube[0] / 2.0, com3d, cam, M, img_size)
     cube64 = np.asarray(cube, np.float64)
     cam64 = tuple(float(c) for c in cam)
     pcl = sample_points(depth_to_pcl(img_n, com3d, cube64, M, cam64), sample_num, rng)
@@ -448,10 +462,6 @@ def prepare_augmented(rgb, depth, joints_mm, cam, aug, mirror=False, center_xyz=
     rng = np.random.RandomState(0) if rng is None else rng
     if joints_mm is None:
         raise ValueError("prepare_augmented: joints_mm is required: a training item has labels")
-    rgb, depth = np.asarray(rgb), np.asarray(depth)
-    cam = tuple(np.float32(c) for c in cam)
-    if len(cam) != 4 or len(cube) != 3:
-        raise ValueError("prepare_augmented: cam is (fx, fy, u0, v0) and cube three sizes in mm")
     mode = int(aug["mode"])
     off = np.asarray(aug["off"], np.float64)
     rot, sc = np.float64(aug["rot"]), np.float64(aug["sc"])
@@ -461,28 +471,8 @@ def prepare_augmented(rgb, depth, joints_mm, cam, aug, mirror=False, center_xyz=
     color = None if aug.get("color") is None else np.asarray(aug["color"], np.float64)
     if color is not None and color.shape != (3,):
         raise ValueError("prepare_augmented: aug['color'] is three factors")
-    S, W = int(img_size), depth.shape[1]
-    if mirror:
-        rgb, depth = rgb[:, ::-1].copy(), depth[:, ::-1].copy()
-    joints_mm = _f32(joints_mm)
-    if joints_mm.ndim != 2 or joints_mm.shape[1] != 3:
-        raise ValueError("prepare_augmented: joints_mm must be [J][3] (got %s)" % (joints_mm.shape,))
-    joint_xyz = joints_mm
-    if center_xyz is None or mirror:
-        joint_uvd = _project_f32(joints_mm, cam)
-        if mirror:
-            joint_uvd[:, 0] = np.float32(W) - joint_uvd[:, 0] - np.float32(1)
-        joint_xyz = _backproject_f32(joint_uvd, cam)
-    if center_xyz is None:
-        center_xyz = _mean_rows_f32(joint_xyz)
-    else:
-        center_xyz = _f32(center_xyz)
-        if center_xyz.shape != (3,):
-            raise ValueError("prepare_augmented: center_xyz must be [3] (got %s)" % (center_xyz.shape,))
-    com = _project_f32(center_xyz, cam)  # center_uvd, float32
-    bounds = annotated_bounds(com, cube, cam)
-    crop_rgb, _ = _crop_to_bounds(rgb, bounds, (S, S), thresh_z=False)
-    crop_d, M = _crop_to_bounds(depth, bounds, (S, S), thresh_z=True)
+    S = int(img_size)
+    cam, W, joint_xyz, center_xyz, com, crop_rgb, crop_d, M = _annotated_base("prepare_augmented", rgb, depth, joints_mm, cam, mirror, center_xyz, cube, S)
     gt = joint_xyz - center_xyz  # gt3Dcrop, float32
     premax = crop_d.max()
     cube64 = np.asarray(cube, np.float64)  # cube[k] / 2.0 is a float64 in every mode (an int64 array, or the list of Python floats of scaleHand)
@@ -567,15 +557,8 @@ def prepare_augmented(rgb, depth, joints_mm, cam, aug, mirror=False, center_xyz=
     d /= hz
     com3d = _backproject_f32(new_com, cam)
     lab64 = lab.astype(np.float64) / (new_cube[2] / 2.0)
-    p = lab64 * (new_cube[0] / 2.0) + com3d.astype(np.float64)
-    fx, fy, fu, fv = (float(v) for v in cam)
     with np.errstate(all="ignore"):
-        uvd = np.stack([p[:, 0] * fx / p[:, 2] + fu, p[:, 1] * fy / p[:, 2] + fv, p[:, 2]], 1).astype(np.float32)
-        joint_img = uvd.copy()
-        joint_img[:, 0] = Mnew[0, 0] * uvd[:, 0].astype(np.float64) + Mnew[0, 2]
-        joint_img[:, 1] = Mnew[1, 1] * uvd[:, 1].astype(np.float64) + Mnew[1, 2]
-        joint_img[:, 0:2] = joint_img[:, 0:2] / np.float32(S / 2) - np.float32(1)
-        joint_img[:, 2] = (joint_img[:, 2] - com3d[2]).astype(np.float64) / (new_cube[0] / 2.0)
+        joint_img = _labels_to_image(lab64, new_cube[0] / 2.0, com3d, cam, Mnew, S)
     cam64 = tuple(float(v) for v in cam)
     pcl = sample_points(depth_to_pcl(d, com3d, new_cube, Mnew, cam64), sample_num, rng)
     return dict(img_rgb=(crop_rgb_aug / np.float32(255.0)).transpose(2, 0, 1), img=d[None].astype(np.float32), pcl=pcl, center=com3d,

@@ -44,6 +44,62 @@ def _named(rgb, depth, bbox, cam, seed, frame_index):
     return named if frame_index is None else named + (("frame_index", frame_index),)
 
 
+def _check_tensors(where, table):
+    """table: rows (name, tensor) or (name, tensor, shape, dtype).  Every row must be a torch tensor, and of that shape and dtype where they are given."""
+    for name, t, *want in table:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch tensor on the GPU (got %s)" % (where, name, type(t).__name__))
+        if want and tuple(t.shape) != want[0]:
+            raise ValueError("%s: %s has shape %s, expected %s" % (where, name, tuple(t.shape), want[0]))
+        if want and t.dtype != want[1]:
+            raise TypeError("%s: %s must be %s (got %s)" % (where, name, want[1], t.dtype))
+
+
+def _check_frames(where, rgb, depth, origin, frame_size, frame_index):
+    """The stored frames, the frame index and the window of one batch (depth is uint16: each caller says why).  Returns (F, B, Hs, Ws, x0, y0, H, W): F stored
+    frames, B samples (the length of frame_index when there is one)."""
+    if rgb.dtype != torch.uint8:
+        raise TypeError("%s: rgb must be torch.uint8 (got %s)" % (where, rgb.dtype))
+    if depth.dim() != 3 or min(depth.shape) < 1:
+        raise ValueError("%s: depth must be a non-empty [B][Hs][Ws] (got %s)" % (where, tuple(depth.shape)))
+    F, Hs, Ws = (int(v) for v in depth.shape)
+    if tuple(rgb.shape) != (F, Hs, Ws, 3):
+        raise ValueError("%s: rgb %s does not match depth %s (expected [B][Hs][Ws][3])" % (where, tuple(rgb.shape), tuple(depth.shape)))
+    B = F
+    if frame_index is not None:
+        if frame_index.dtype != torch.int32:
+            raise TypeError("%s: frame_index must be torch.int32 (got %s): build it with make_frame_index" % (where, frame_index.dtype))
+        if frame_index.dim() != 1 or frame_index.shape[0] < 1:
+            raise ValueError("%s: frame_index has shape %s, expected [B]" % (where, tuple(frame_index.shape)))
+        B = int(frame_index.shape[0])
+    if (origin is None) != (frame_size is None):
+        raise ValueError("%s: origin=(x0, y0) and frame_size=(H, W) go together" % where)
+    x0, y0 = (0, 0) if origin is None else (int(origin[0]), int(origin[1]))
+    H, W = (Hs, Ws) if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
+    if x0 < 0 or y0 < 0 or x0 + Ws > W or y0 + Hs > H:
+        raise ValueError("%s: the %d x %d window at (%d, %d) leaves the %d x %d frame" % (where, Ws, Hs, x0, y0, W, H))
+    return F, B, Hs, Ws, x0, y0, H, W
+
+
+def _require_on(where, named, dev, host_path):
+    """Every tensor of named (None: an optional one left out) on the GPU `dev` and contiguous; host_path: the function of preprocess.py to use instead."""
+    for name, t in named:
+        if t is None:
+            continue
+        if t.device.type != "cuda" or t.device != dev:
+            raise RuntimeError("%s: %s is on %s; every input must be on the same GPU (there is no CPU fallback: preprocess.%s is the host path)"
+                               % (where, name, t.device, host_path))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous" % (where, name))
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+CROP_OUTPUTS = ("img", "img_rgb", "center", "M", "cube", "cam_para", "com", "bounds", "M64")  # the order the three crop entry points take them in
+
+
 def make_frame_index(indices, frames, device):
     """[B] int32 device tensor for prepare(..., frame_index=): track b reads stored frame indices[b] of `frames`.  The values are checked HERE, on the host
     list, before anything reaches a device (the kernel clamps as well, but a wrong index is a caller's bug, not a frame to crop)."""
@@ -83,57 +139,52 @@ class DevicePreprocessor:
     def check_inputs(rgb, depth, bbox, cam, seed, origin=None, frame_size=None, frame_index=None):
         """Validates one batch and returns (B, Hs, Ws, x0, y0, H, W).  Raises TypeError / ValueError with the reason.  frame_index ([B] int32, from
         make_frame_index): rgb and depth hold F stored frames and B, the number of samples, is the length of the index."""
-        for name, t in _named(rgb, depth, bbox, cam, seed, frame_index):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("DevicePreprocessor.prepare: %s must be a torch tensor on the GPU (got %s)" % (name, type(t).__name__))
+        where = "DevicePreprocessor.prepare"
+        _check_tensors(where, _named(rgb, depth, bbox, cam, seed, frame_index))
         if depth.dtype != torch.uint16:
-            raise TypeError("DevicePreprocessor.prepare: depth must be torch.uint16 millimetres (got %s); the host path's z-clamp for float depth differs "
-                            "and is not reproduced here: use preprocess.prepare_rgbd for float depth" % depth.dtype)
-        if rgb.dtype != torch.uint8:
-            raise TypeError("DevicePreprocessor.prepare: rgb must be torch.uint8 (got %s)" % rgb.dtype)
-        if depth.dim() != 3:
-            raise ValueError("DevicePreprocessor.prepare: depth must be [B][Hs][Ws] (got %s)" % (tuple(depth.shape),))
-        F, Hs, Ws = (int(v) for v in depth.shape)
-        if F < 1 or Hs < 1 or Ws < 1:
-            raise ValueError("DevicePreprocessor.prepare: empty depth %s" % (tuple(depth.shape),))
-        if tuple(rgb.shape) != (F, Hs, Ws, 3):
-            raise ValueError("DevicePreprocessor.prepare: rgb %s does not match depth %s (expected [B][Hs][Ws][3])" % (tuple(rgb.shape), tuple(depth.shape)))
-        B = F
-        if frame_index is not None:
-            if frame_index.dtype != torch.int32:
-                raise TypeError("DevicePreprocessor.prepare: frame_index must be torch.int32 (got %s): build it with make_frame_index" % frame_index.dtype)
-            if frame_index.dim() != 1 or frame_index.shape[0] < 1:
-                raise ValueError("DevicePreprocessor.prepare: frame_index has shape %s, expected [B]" % (tuple(frame_index.shape),))
-            B = int(frame_index.shape[0])
-        for name, t, shape, dt in (("bbox", bbox, (B, 4), torch.float64), ("cam", cam, (B, 4), torch.float64), ("seed", seed, (B,), torch.int64)):
-            if tuple(t.shape) != shape:
-                raise ValueError("DevicePreprocessor.prepare: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            if t.dtype != dt:
-                raise TypeError("DevicePreprocessor.prepare: %s must be %s (got %s)" % (name, dt, t.dtype))
-        if (origin is None) != (frame_size is None):
-            raise ValueError("DevicePreprocessor.prepare: origin=(x0, y0) and frame_size=(H, W) go together")
-        x0, y0 = (0, 0) if origin is None else (int(origin[0]), int(origin[1]))
-        H, W = (Hs, Ws) if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
-        if x0 < 0 or y0 < 0 or x0 + Ws > W or y0 + Hs > H:
-            raise ValueError("DevicePreprocessor.prepare: the %d x %d window at (%d, %d) leaves the %d x %d frame" % (Ws, Hs, x0, y0, W, H))
+            raise TypeError("%s: depth must be torch.uint16 millimetres (got %s); the host path's z-clamp for float depth differs "
+                            "and is not reproduced here: use preprocess.prepare_rgbd for float depth" % (where, depth.dtype))
+        _, B, Hs, Ws, x0, y0, H, W = _check_frames(where, rgb, depth, origin, frame_size, frame_index)
+        _check_tensors(where, (("bbox", bbox, (B, 4), torch.float64), ("cam", cam, (B, 4), torch.float64), ("seed", seed, (B,), torch.int64)))
         return B, Hs, Ws, x0, y0, H, W
 
-    def _buffers(self, dev, B, Hs, Ws):
-        key = (dev, B, Hs, Ws)
+    def _buffers(self, dev, B, Hs, Ws, kind, J=None):
+        """This object's outputs for one shape.  kind: "crop" (prepare), "annot" (prepare_annotated) or "augment" (prepare_augmented): each path keeps a
+        set of its own, so that the result of one outlives a call of another."""
+        key = (dev, B, Hs, Ws, kind, J)
         b = self._bufs.get(key)
         if b is None:
             S, n = self.img_size, self.sample_num
-            f32 = dict(device=dev, dtype=torch.float32)
+            f32, f64, i32 = (dict(device=dev, dtype=dt) for dt in (torch.float32, torch.float64, torch.int32))
             b = dict(img_rgb=torch.zeros(B, 3, S, S, **f32), img=torch.zeros(B, 1, S, S, **f32), pcl=torch.zeros(B, n, 3, **f32), center=torch.zeros(B, 3, **f32),
-                     M=torch.zeros(B, 3, 3, **f32), cube=torch.zeros(B, 3, **f32), cam_para=torch.zeros(B, 4, **f32),
-                     pcl_index=torch.zeros(B, n, device=dev, dtype=torch.int32), pcl_count=torch.zeros(B, device=dev, dtype=torch.int32),
-                     com=torch.zeros(B, 3, device=dev, dtype=torch.float64), bounds=torch.zeros(B, 6, device=dev, dtype=torch.int32),
-                     M64=torch.zeros(B, 3, 3, device=dev, dtype=torch.float64),
-                     _cube64=torch.tensor([self.cube] * B, device=dev, dtype=torch.float64))
+                     M=torch.zeros(B, 3, 3, **f32), cube=torch.zeros(B, 3, **f32), cam_para=torch.zeros(B, 4, **f32), pcl_index=torch.zeros(B, n, **i32),
+                     pcl_count=torch.zeros(B, **i32), com=torch.zeros(B, 3, **f64), bounds=torch.zeros(B, 6, **i32), M64=torch.zeros(B, 3, 3, **f64),
+                     _cube64=torch.tensor([self.cube] * B, **f64))
+            if kind != "crop":
+                b.update(joint=torch.zeros(B, J, 3, **f32), joint_img=torch.zeros(B, J, 3, **f32), _cam64=torch.zeros(B, 4, **f64),
+                         _right=torch.zeros(B, device=dev, dtype=torch.uint8))
+            if kind == "augment":
+                b.update(cube64=torch.zeros(B, 3, **f64), aug_status=torch.zeros(B, **i32), _pcl_seed=torch.zeros(B, device=dev, dtype=torch.int64),
+                         _aug=dict(mode=torch.zeros(B, **i32), off=torch.zeros(B, 3, **f64), sc=torch.zeros(B, **f64), rot=torch.zeros(B, **f64),
+                                   rot_cs=torch.zeros(B, 2, **f64), color=torch.zeros(B, 3, **f64)))
             if self.debug_candidates:
                 b["candidates"] = torch.zeros(B, S * S, 3, **f32)
             self._bufs[key] = b
         return b
+
+    def _sample(self, l, o, cube64, cam64_ptr, seed, st):
+        """kpf_prep_pcl_sample on the crop in o: the point cloud, its candidate indices and the candidate count."""
+        cand = o["candidates"].data_ptr() if self.debug_candidates else None
+        lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), cube64.data_ptr(), cam64_ptr, seed.data_ptr(),
+                                        int(o["pcl_count"].shape[0]), self.img_size, self.sample_num, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(),
+                                        o["pcl_count"].data_ptr(), cand, st), "kpf_prep_pcl_sample")
+
+    @staticmethod
+    def _result(o, **extra):
+        """The buffers a caller sees (not the ones named _...), plus what the path adds."""
+        out = {k: v for k, v in o.items() if not k.startswith("_")}
+        out.update(extra)
+        return out
 
     def prepare(self, rgb, depth, bbox, cam, seed, origin=None, frame_size=None, frame_index=None):
         """rgb [B][Hs][Ws][3] uint8, depth [B][Hs][Ws] uint16 (mm), bbox [B][4] float64 (x, y, w, h; x, y the top-left corner), cam [B][4] float64
@@ -145,30 +196,19 @@ class DevicePreprocessor:
         frame frame_index[b], and bbox, cam and seed stay [B].  Without it sample b reads frame b."""
         B, Hs, Ws, x0, y0, H, W = self.check_inputs(rgb, depth, bbox, cam, seed, origin, frame_size, frame_index)
         dev = depth.device
-        for name, t in _named(rgb, depth, bbox, cam, seed, frame_index):
-            if t.device.type != "cuda" or t.device != dev:
-                raise RuntimeError("DevicePreprocessor.prepare: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
-                                   "preprocess.prepare_rgbd is the host path)" % (name, t.device))
-            if not t.is_contiguous():
-                raise ValueError("DevicePreprocessor.prepare: %s must be contiguous" % name)
+        _require_on("DevicePreprocessor.prepare", _named(rgb, depth, bbox, cam, seed, frame_index), dev, "prepare_rgbd")
         l = lib.load()
-        o = self._buffers(dev, B, Hs, Ws)
-        S, n = self.img_size, self.sample_num
+        o = self._buffers(dev, B, Hs, Ws, "crop")
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            outs = (o["img"].data_ptr(), o["img_rgb"].data_ptr(), o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(), o["cam_para"].data_ptr(),
-                    o["com"].data_ptr(), o["bounds"].data_ptr(), o["M64"].data_ptr(), st)
+            tail = (bbox.data_ptr(), cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, self.img_size, *[o[k].data_ptr() for k in CROP_OUTPUTS], st)
             if frame_index is None:
-                lib.check(l.kpf_prep_crop_u16(rgb.data_ptr(), depth.data_ptr(), bbox.data_ptr(), cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, S,
-                                              *outs), "kpf_prep_crop_u16")
+                lib.check(l.kpf_prep_crop_u16(rgb.data_ptr(), depth.data_ptr(), *tail), "kpf_prep_crop_u16")
             else:
-                lib.check(l.kpf_prep_crop_u16_indexed(rgb.data_ptr(), depth.data_ptr(), frame_index.data_ptr(), int(depth.shape[0]), bbox.data_ptr(),
-                                                      cam.data_ptr(), o["_cube64"].data_ptr(), B, Hs, Ws, x0, y0, H, W, S, *outs), "kpf_prep_crop_u16_indexed")
-            cand = o["candidates"].data_ptr() if self.debug_candidates else None
-            lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["_cube64"].data_ptr(), cam.data_ptr(),
-                                            seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
-                      "kpf_prep_pcl_sample")
-        return {k: v for k, v in o.items() if not k.startswith("_")}
+                lib.check(l.kpf_prep_crop_u16_indexed(rgb.data_ptr(), depth.data_ptr(), frame_index.data_ptr(), int(depth.shape[0]), *tail),
+                          "kpf_prep_crop_u16_indexed")
+            self._sample(l, o, o["_cube64"], cam.data_ptr(), seed, st)
+        return self._result(o)
 
     # -- the dataset protocol
     @staticmethod
@@ -177,27 +217,11 @@ class DevicePreprocessor:
         where = "DevicePreprocessor.prepare_annotated"
         if joints_mm is None and center_xyz is None:
             raise ValueError("%s: neither joints_mm nor center_xyz: nothing to crop around" % where)
-        named = [("rgb", rgb), ("depth", depth), ("cam", cam), ("seed", seed)] + [(k, v) for k, v in (
-            ("joints_mm", joints_mm), ("mirror", mirror), ("center_xyz", center_xyz), ("frame_index", frame_index)) if v is not None]
-        for name, t in named:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("%s: %s must be a torch tensor on the GPU (got %s)" % (where, name, type(t).__name__))
+        _check_tensors(where, [("rgb", rgb), ("depth", depth), ("cam", cam), ("seed", seed)] + [(k, v) for k, v in (
+            ("joints_mm", joints_mm), ("mirror", mirror), ("center_xyz", center_xyz), ("frame_index", frame_index)) if v is not None])
         if depth.dtype != torch.uint16:
             raise TypeError("%s: depth must be torch.uint16 millimetres (got %s): the z-clamp truncates the near plane to the sensor's type" % (where, depth.dtype))
-        if rgb.dtype != torch.uint8:
-            raise TypeError("%s: rgb must be torch.uint8 (got %s)" % (where, rgb.dtype))
-        if depth.dim() != 3 or min(depth.shape) < 1:
-            raise ValueError("%s: depth must be a non-empty [B][Hs][Ws] (got %s)" % (where, tuple(depth.shape)))
-        F, Hs, Ws = (int(v) for v in depth.shape)
-        if tuple(rgb.shape) != (F, Hs, Ws, 3):
-            raise ValueError("%s: rgb %s does not match depth %s (expected [B][Hs][Ws][3])" % (where, tuple(rgb.shape), tuple(depth.shape)))
-        B = F
-        if frame_index is not None:
-            if frame_index.dtype != torch.int32:
-                raise TypeError("%s: frame_index must be torch.int32 (got %s): build it with make_frame_index" % (where, frame_index.dtype))
-            if frame_index.dim() != 1 or frame_index.shape[0] < 1:
-                raise ValueError("%s: frame_index has shape %s, expected [B]" % (where, tuple(frame_index.shape)))
-            B = int(frame_index.shape[0])
+        _, B, Hs, Ws, x0, y0, H, W = _check_frames(where, rgb, depth, origin, frame_size, frame_index)
         J = 21
         if joints_mm is not None:
             if joints_mm.dim() != 3 or joints_mm.shape[0] != B or joints_mm.shape[2] != 3 or joints_mm.shape[1] < 1:
@@ -209,36 +233,8 @@ class DevicePreprocessor:
         checks += [("joints_mm", joints_mm, (B, J, 3), torch.float32)] if joints_mm is not None else []
         checks += [("center_xyz", center_xyz, (B, 3), torch.float32)] if center_xyz is not None else []
         checks += [("mirror", mirror, (B,), torch.uint8)] if mirror is not None else []
-        for name, t, shape, dt in checks:
-            if tuple(t.shape) != shape:
-                raise ValueError("%s: %s has shape %s, expected %s" % (where, name, tuple(t.shape), shape))
-            if t.dtype != dt:
-                raise TypeError("%s: %s must be %s (got %s)" % (where, name, dt, t.dtype))
-        if (origin is None) != (frame_size is None):
-            raise ValueError("%s: origin=(x0, y0) and frame_size=(H, W) go together" % where)
-        x0, y0 = (0, 0) if origin is None else (int(origin[0]), int(origin[1]))
-        H, W = (Hs, Ws) if frame_size is None else (int(frame_size[0]), int(frame_size[1]))
-        if x0 < 0 or y0 < 0 or x0 + Ws > W or y0 + Hs > H:
-            raise ValueError("%s: the %d x %d window at (%d, %d) leaves the %d x %d frame" % (where, Ws, Hs, x0, y0, W, H))
+        _check_tensors(where, checks)
         return B, J, Hs, Ws, x0, y0, H, W
-
-    def _annot_buffers(self, dev, B, Hs, Ws, J, kind="annot"):
-        key = (dev, B, Hs, Ws, kind, J)
-        b = self._bufs.get(key)
-        if b is None:
-            S, n = self.img_size, self.sample_num
-            f32 = dict(device=dev, dtype=torch.float32)
-            b = dict(img_rgb=torch.zeros(B, 3, S, S, **f32), img=torch.zeros(B, 1, S, S, **f32), pcl=torch.zeros(B, n, 3, **f32), center=torch.zeros(B, 3, **f32),
-                     M=torch.zeros(B, 3, 3, **f32), cube=torch.zeros(B, 3, **f32), cam_para=torch.zeros(B, 4, **f32),
-                     pcl_index=torch.zeros(B, n, device=dev, dtype=torch.int32), pcl_count=torch.zeros(B, device=dev, dtype=torch.int32),
-                     com=torch.zeros(B, 3, device=dev, dtype=torch.float64), bounds=torch.zeros(B, 6, device=dev, dtype=torch.int32),
-                     M64=torch.zeros(B, 3, 3, device=dev, dtype=torch.float64), joint=torch.zeros(B, J, 3, **f32), joint_img=torch.zeros(B, J, 3, **f32),
-                     _cube64=torch.tensor([self.cube] * B, device=dev, dtype=torch.float64), _cam64=torch.zeros(B, 4, device=dev, dtype=torch.float64),
-                     _right=torch.zeros(B, device=dev, dtype=torch.uint8))
-            if self.debug_candidates:
-                b["candidates"] = torch.zeros(B, S * S, 3, **f32)
-            self._bufs[key] = b
-        return b
 
     def prepare_annotated(self, rgb, depth, joints_mm, cam, seed, mirror=None, center_xyz=None, origin=None, frame_size=None, frame_index=None):
         """The reference's dataset items at test time on the device (preprocess.prepare_annotated, bit for bit): the crop around an annotated 3-D centre, left
@@ -249,34 +245,18 @@ class DevicePreprocessor:
         tensor given, or zeros) and frame_w (int, the width the mirror acts on); uncrop() takes a mirrored sample's u back to the camera's frame."""
         B, J, Hs, Ws, x0, y0, H, W = self.check_annotated(rgb, depth, joints_mm, cam, seed, mirror, center_xyz, origin, frame_size, frame_index)
         dev = depth.device
-        for name, t in (("rgb", rgb), ("depth", depth), ("joints_mm", joints_mm), ("cam", cam), ("seed", seed), ("mirror", mirror), ("center_xyz", center_xyz),
-                        ("frame_index", frame_index)):
-            if t is None:
-                continue
-            if t.device.type != "cuda" or t.device != dev:
-                raise RuntimeError("DevicePreprocessor.prepare_annotated: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
-                                   "preprocess.prepare_annotated is the host path)" % (name, t.device))
-            if not t.is_contiguous():
-                raise ValueError("DevicePreprocessor.prepare_annotated: %s must be contiguous" % name)
+        _require_on("DevicePreprocessor.prepare_annotated", (("rgb", rgb), ("depth", depth), ("joints_mm", joints_mm), ("cam", cam), ("seed", seed), ("mirror", mirror),
+                                                              ("center_xyz", center_xyz), ("frame_index", frame_index)), dev, "prepare_annotated")
         l = lib.load()
-        o = self._annot_buffers(dev, B, Hs, Ws, J)
-        S, n = self.img_size, self.sample_num
+        o = self._buffers(dev, B, Hs, Ws, "annot", J)
         mir = o["_right"] if mirror is None else mirror
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            lib.check(l.kpf_prep_annot_u16(rgb.data_ptr(), depth.data_ptr(), ptr(frame_index), int(depth.shape[0]), ptr(joints_mm), cam.data_ptr(), ptr(center_xyz),
-                                           mir.data_ptr(), o["_cube64"].data_ptr(), B, J, Hs, Ws, x0, y0, H, W, S, o["img"].data_ptr(), o["img_rgb"].data_ptr(),
-                                           o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(), o["cam_para"].data_ptr(), o["com"].data_ptr(),
-                                           o["bounds"].data_ptr(), o["M64"].data_ptr(), o["joint"].data_ptr(), o["joint_img"].data_ptr(), o["_cam64"].data_ptr(),
-                                           st), "kpf_prep_annot_u16")
-            cand = o["candidates"].data_ptr() if self.debug_candidates else None
-            lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["_cube64"].data_ptr(), o["_cam64"].data_ptr(),
-                                            seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
-                      "kpf_prep_pcl_sample")
-        out = {k: v for k, v in o.items() if not k.startswith("_")}
-        out.update(mirror=mir, frame_w=W)
-        return out
+            lib.check(l.kpf_prep_annot_u16(rgb.data_ptr(), depth.data_ptr(), _ptr(frame_index), int(depth.shape[0]), _ptr(joints_mm), cam.data_ptr(), _ptr(center_xyz),
+                                           mir.data_ptr(), o["_cube64"].data_ptr(), B, J, Hs, Ws, x0, y0, H, W, self.img_size,
+                                           *[o[k].data_ptr() for k in CROP_OUTPUTS + ("joint", "joint_img", "_cam64")], st), "kpf_prep_annot_u16")
+            self._sample(l, o, o["_cube64"], o["_cam64"].data_ptr(), seed, st)
+        return self._result(o, mirror=mir, frame_w=W)
 
     # -- training augmentation by the dataset protocol
     AUG_KEYS = (("mode", (), torch.int32), ("off", (3,), torch.float64), ("sc", (), torch.float64), ("rot", (), torch.float64), ("rot_cs", (2,), torch.float64))
@@ -297,28 +277,8 @@ class DevicePreprocessor:
             if not isinstance(aug, dict):
                 raise TypeError("%s: aug must be a dict of device tensors (mode, off, sc, rot, rot_cs and optionally color), got %s" % (where, type(aug).__name__))
             keys = DevicePreprocessor.AUG_KEYS + ((("color", (3,), torch.float64),) if aug.get("color") is not None else ())
-            for k, tail, dt in keys:
-                t = aug.get(k)
-                if not isinstance(t, torch.Tensor):
-                    raise TypeError("%s: aug[%r] must be a torch tensor on the GPU (got %s)" % (where, k, type(t).__name__))
-                if tuple(t.shape) != (B,) + tail:
-                    raise ValueError("%s: aug[%r] has shape %s, expected %s" % (where, k, tuple(t.shape), (B,) + tail))
-                if t.dtype != dt:
-                    raise TypeError("%s: aug[%r] must be %s (got %s)" % (where, k, dt, t.dtype))
+            _check_tensors(where, [("aug[%r]" % k, aug.get(k), (B,) + tail, dt) for k, tail, dt in keys])
         return shape
-
-    def _aug_buffers(self, dev, B, Hs, Ws, J):
-        key = (dev, B, Hs, Ws, "augment", J)
-        b = self._bufs.get(key)
-        if b is None:
-            b = dict(self._annot_buffers(dev, B, Hs, Ws, J, kind="augment-outputs"))  # (its own set: prepare_annotated's results stay)
-            f64 = dict(device=dev, dtype=torch.float64)
-            b.update(cube64=torch.zeros(B, 3, **f64), aug_status=torch.zeros(B, device=dev, dtype=torch.int32),
-                     _pcl_seed=torch.zeros(B, device=dev, dtype=torch.int64),
-                     _aug=dict(mode=torch.zeros(B, device=dev, dtype=torch.int32), off=torch.zeros(B, 3, **f64), sc=torch.zeros(B, **f64), rot=torch.zeros(B, **f64),
-                               rot_cs=torch.zeros(B, 2, **f64), color=torch.zeros(B, 3, **f64)))
-            self._bufs[key] = b
-        return b
 
     def prepare_augmented(self, rgb, depth, joints_mm, cam, seed, aug=None, mirror=None, center_xyz=None, origin=None, frame_size=None, frame_index=None,
                           sigma_com=10, sigma_sc=0.2, rot_range=180, color_factor=0):
@@ -336,19 +296,10 @@ class DevicePreprocessor:
         dev = depth.device
         named = [("rgb", rgb), ("depth", depth), ("joints_mm", joints_mm), ("cam", cam), ("seed", seed), ("mirror", mirror), ("center_xyz", center_xyz),
                  ("frame_index", frame_index)] + [("aug[%r]" % k, v) for k, v in (aug or {}).items()]
-        for name, t in named:
-            if t is None:
-                continue
-            if t.device.type != "cuda" or t.device != dev:
-                raise RuntimeError("DevicePreprocessor.prepare_augmented: %s is on %s; every input must be on the same GPU (there is no CPU fallback: "
-                                   "preprocess.prepare_augmented is the host path)" % (name, t.device))
-            if not t.is_contiguous():
-                raise ValueError("DevicePreprocessor.prepare_augmented: %s must be contiguous" % name)
+        _require_on("DevicePreprocessor.prepare_augmented", named, dev, "prepare_augmented")
         l = lib.load()
-        o = self._aug_buffers(dev, B, Hs, Ws, J)
-        S, n = self.img_size, self.sample_num
+        o = self._buffers(dev, B, Hs, Ws, "augment", J)
         mir = o["_right"] if mirror is None else mirror
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             pcl_seed = seed
@@ -364,20 +315,13 @@ class DevicePreprocessor:
                 used = {k: aug[k] for k in ("mode", "off", "sc", "rot", "rot_cs")}
                 if aug.get("color") is not None:
                     used["color"] = aug["color"]
-            lib.check(l.kpf_prep_augment_u16(rgb.data_ptr(), depth.data_ptr(), ptr(frame_index), int(depth.shape[0]), joints_mm.data_ptr(), cam.data_ptr(),
-                                             ptr(center_xyz), mir.data_ptr(), o["_cube64"].data_ptr(), used["mode"].data_ptr(), used["off"].data_ptr(),
-                                             used["sc"].data_ptr(), used["rot"].data_ptr(), used["rot_cs"].data_ptr(), ptr(used.get("color")), B, J, Hs, Ws, x0, y0,
-                                             H, W, S, o["img"].data_ptr(), o["img_rgb"].data_ptr(), o["center"].data_ptr(), o["M"].data_ptr(), o["cube"].data_ptr(),
-                                             o["cam_para"].data_ptr(), o["com"].data_ptr(), o["bounds"].data_ptr(), o["M64"].data_ptr(), o["joint"].data_ptr(),
-                                             o["joint_img"].data_ptr(), o["_cam64"].data_ptr(), o["cube64"].data_ptr(), o["aug_status"].data_ptr(), st),
+            lib.check(l.kpf_prep_augment_u16(rgb.data_ptr(), depth.data_ptr(), _ptr(frame_index), int(depth.shape[0]), joints_mm.data_ptr(), cam.data_ptr(),
+                                             _ptr(center_xyz), mir.data_ptr(), o["_cube64"].data_ptr(), *[used[k].data_ptr() for k, _, _ in self.AUG_KEYS],
+                                             _ptr(used.get("color")), B, J, Hs, Ws, x0, y0, H, W, self.img_size,
+                                             *[o[k].data_ptr() for k in CROP_OUTPUTS + ("joint", "joint_img", "_cam64", "cube64", "aug_status")], st),
                       "kpf_prep_augment_u16")
-            cand = o["candidates"].data_ptr() if self.debug_candidates else None
-            lib.check(l.kpf_prep_pcl_sample(o["img"].data_ptr(), o["center"].data_ptr(), o["M64"].data_ptr(), o["cube64"].data_ptr(), o["_cam64"].data_ptr(),
-                                            pcl_seed.data_ptr(), B, S, n, o["pcl"].data_ptr(), o["pcl_index"].data_ptr(), o["pcl_count"].data_ptr(), cand, st),
-                      "kpf_prep_pcl_sample")
-        out = {k: v for k, v in o.items() if not k.startswith("_")}
-        out.update(mirror=mir, frame_w=W, aug=used, augmented=True)
-        return out
+            self._sample(l, o, o["cube64"], o["_cam64"].data_ptr(), pcl_seed, st)
+        return self._result(o, mirror=mir, frame_w=W, aug=used, augmented=True)
 
     def uncrop(self, joints_nl, prep):
         """joints_nl [B][J][3] float32 normalised to the cube (the model's xyz outputs) + a prepare() result (or any dict with center, M, cube, cam_para)
