@@ -296,6 +296,41 @@ int kpf_mano_forward_f32(const float* pose6d, int ld6, const float* betas, int l
                          const float* posedirs_t, const float* v_template, const float* j_regressor, const float* skin_weights,
                          const float* hands_mean, float* verts, float* joints, float* rotmat, float* pose_aa, int B, void* stream);
 
+/* Backward of kpf_mano_forward_f32 (ABI 26).  Gradient inputs may each be NULL (= zero):
+ * d_verts [B][778][3], d_joints [B][21][3] (head order, as the forward writes them),
+ * d_rotmat [B][16][3][3], d_pose_aa [B][48].
+ * Writes (overwrites, never accumulates) d_pose6d rows [B][ldd6] (first 96 columns)
+ * and d_betas rows [B][lddb] (first 10); other columns untouched.
+ * The forward is recomputed in LDS (no saved workspace); the gradient is torch autograd's of the same formulas (a clamped F.normalize and a selected
+ * isnan pass no gradient), except at an exact identity rotation, where autograd gives NaN and this gives the derivative of the k = 2 branch the forward
+ * takes there.  Fixed-order reductions: a sample's bits depend neither on B nor on its position nor on a replay. */
+int kpf_mano_backward_f32(const float* pose6d, int ld6, const float* betas, int ldb,
+    const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+    const float* skin_weights, const float* hands_mean,
+    const float* d_verts, const float* d_joints, const float* d_rotmat, const float* d_pose_aa,
+    float* d_pose6d, int ldd6, float* d_betas, int lddb, int B, void* stream);
+
+/* Fit the MANO layer to 21 target joints per sample (ABI 26): one workgroup per sample, all `iters` Adam iterations inside the one launch.
+ * Per sample  L = (1 / sum w) sum_i w_i |J_map[i](theta, beta) + t - y_i|^2 + lambda_shape |beta|^2 + lambda_pose |theta[3:]|^2  in mm^2, minimised by
+ * torch.optim.Adam's update (no weight decay, no amsgrad; moments zero at the start of every call; step k counts from 1 in the bias corrections;
+ * step = lr m^ / (sqrt(v^) + eps)) with one learning rate each for pose, shape and translation.  init_trans != 0 (and iters > 0) first sets
+ * t = sum w_i (y_i - J_i) / sum w.  pose_aa is the head's mano_pose_aa (hands_mean is added inside); rotmat[j] = rodrigues(pose_aa[j]).
+ * status [B] bits: 1 sum w == 0; 2 a target with w > 0 is not finite — in both cases the state keeps its bits and the outputs evaluate it
+ * (residual 0 for bit 1).  A target of weight 0 is selected out, never multiplied.  residual [B][2]: the mean weighted joint distance in mm at the
+ * first state (after init_trans) and at the final one.  Same determinism as the backward. */
+typedef struct kpf_mano_fit_cfg {
+  int iters;                       /* 0 <= iters <= 1000; 0 only evaluates */
+  float lr_pose, lr_shape, lr_trans, beta1, beta2, eps;
+  float lambda_shape, lambda_pose; int init_trans;
+  int joint_map[21];               /* target row i <-> head-order model joint joint_map[i]; a permutation */
+} kpf_mano_fit_cfg;                /* HOST struct */
+int kpf_mano_fit_f32(const float* target /*[B][21][3] mm*/, const float* weight /*[B][21] >= 0, or NULL = ones*/,
+    const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+    const float* skin_weights, const float* hands_mean, const kpf_mano_fit_cfg* cfg,
+    float* pose_aa /*[B][48] in/out*/, float* betas /*[B][10] in/out*/, float* trans /*[B][3] mm in/out*/,
+    float* verts /*[B][778][3] or NULL*/, float* joints /*[B][21][3], target order*/, float* rotmat /*[B][16][9] or NULL*/,
+    float* residual /*[B][2]*/, int* status /*[B]*/, int B, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Reduced-precision path (BASELINE configs[2] bf16, configs[4] fp16): same operators on 16-bit NHWC activations.  `dtype` is
  * KPF_DT_BF16 or KPF_DT_F16; LayerNorm / bias / layer-scale parameters and the depthwise taps stay fp32.
@@ -937,7 +972,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 25
+#define KPF_ABI_VERSION 26
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

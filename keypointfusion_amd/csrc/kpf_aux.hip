@@ -1,7 +1,7 @@
 // Stand-alone heads of the reference that KPFusion.forward does not call but the north star names:
 //   CBAM channel / spatial gates   (model/cbam.py:26-94)            -> pool, gate, compress, spatial-gate, apply kernels
 //   Hourglass glue                 (model/hourglass.py:122-149)     -> 2x2 max-pool, nearest-x2 upsample fused with the skip add
-//   MANO layer + rotation algebra  (model/mano_head.py:144-225, util/manopth/manopth/manolayer.py:106-273) -> one kernel per batch
+//   (the MANO layer of a19 is csrc/kpf_mano.hip)
 // All HBM-bound elementwise / reduction work on NHWC activations (channel quads contiguous -> 16-byte lanes, coalesced).
 #include <math.h>
 
@@ -241,194 +241,6 @@ __global__ __launch_bounds__(256) void upnearest2x_add_kernel(const float* __res
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// MANO: 6D rotations -> rotation matrices -> axis-angle -> (Rodrigues again, as the reference does) -> blend shapes, joint
-// regression, kinematic chain, linear-blend skinning.  One 256-thread workgroup per sample; the sample's 778 x 3 vertices live
-// in LDS from the shape blend to the final skinning.  Blend-shape bases are read transposed ([k][778*3]) so lanes coalesce.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int NV = 778, NJ = 16, NC = NV * 3;
-__constant__ int kManoParent[16] = {-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11, 0, 13, 14};
-// joints3d[i] = jtr21[ORDER[OBMAN2MANO[i]]] with jtr21 = [16 chain joints, 5 finger-tip vertices]
-// (manolayer.py:251-261 then model/mano_head.py:7-16,221)
-__constant__ int kManoOut[21] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 17, 18, 20, 19, 16};
-__constant__ int kManoTip[5] = {745, 317, 444, 556, 673};
-
-__device__ void rot6d_to_mat(const float* x, float* R) {  // model/mano_head.py:144-153 (b1,b2,b3 are columns)
-  float a1[3] = {x[0], x[1], x[2]}, a2[3] = {x[3], x[4], x[5]};
-  float n1 = fmaxf(sqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]), 1e-12f);
-  float b1[3] = {a1[0] / n1, a1[1] / n1, a1[2] / n1};
-  const float d = b1[0] * a2[0] + b1[1] * a2[1] + b1[2] * a2[2];
-  float u[3] = {a2[0] - d * b1[0], a2[1] - d * b1[1], a2[2] - d * b1[2]};
-  float n2 = fmaxf(sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), 1e-12f);
-  float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-  float b3[3] = {b1[1] * b2[2] - b1[2] * b2[1], b1[2] * b2[0] - b1[0] * b2[2], b1[0] * b2[1] - b1[1] * b2[0]};
-  for (int r = 0; r < 3; ++r) {
-    R[r * 3 + 0] = b1[r];
-    R[r * 3 + 1] = b2[r];
-    R[r * 3 + 2] = b3[r];
-  }
-}
-
-__device__ void mat_to_aa(const float* R, float* aa) {  // model/mano_head.py:84-141 (on the transpose), :49-81, :171-173
-  // t = R^T: t[i][j] = R[j][i]
-#define T_(i, j) R[(j) * 3 + (i)]
-  const float m00 = T_(0, 0), m11 = T_(1, 1), m22 = T_(2, 2);
-  float q[4], t;
-  if (m22 < 1e-6f) {
-    if (m00 > m11) {
-      t = 1 + m00 - m11 - m22;
-      q[0] = T_(1, 2) - T_(2, 1); q[1] = t; q[2] = T_(0, 1) + T_(1, 0); q[3] = T_(2, 0) + T_(0, 2);
-    } else {
-      t = 1 - m00 + m11 - m22;
-      q[0] = T_(2, 0) - T_(0, 2); q[1] = T_(0, 1) + T_(1, 0); q[2] = t; q[3] = T_(1, 2) + T_(2, 1);
-    }
-  } else {
-    if (m00 < -m11) {
-      t = 1 - m00 - m11 + m22;
-      q[0] = T_(0, 1) - T_(1, 0); q[1] = T_(2, 0) + T_(0, 2); q[2] = T_(1, 2) + T_(2, 1); q[3] = t;
-    } else {
-      t = 1 + m00 + m11 + m22;
-      q[0] = t; q[1] = T_(1, 2) - T_(2, 1); q[2] = T_(2, 0) - T_(0, 2); q[3] = T_(0, 1) - T_(1, 0);
-    }
-  }
-#undef T_
-  const float inv = 0.5f / sqrtf(t);
-  for (int i = 0; i < 4; ++i) q[i] *= inv;
-  const float s2 = q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-  const float s = sqrtf(s2), c = q[0];
-  const float two_theta = 2.0f * (c < 0.0f ? atan2f(-s, -c) : atan2f(s, c));
-  const float k = s2 > 0.0f ? two_theta / s : 2.0f;
-  for (int i = 0; i < 3; ++i) {
-    const float v = q[i + 1] * k;
-    aa[i] = isnan(v) ? 0.0f : v;
-  }
-}
-
-__device__ void rodrigues(const float* aa, float* R) {  // util/manopth/manopth/rodrigues_layer.py:16-57
-  const float ax = aa[0] + 1e-8f, ay = aa[1] + 1e-8f, az = aa[2] + 1e-8f;
-  const float ang = sqrtf(ax * ax + ay * ay + az * az);
-  const float h = ang * 0.5f, sn = sinf(h), cs = cosf(h);
-  float q[4] = {cs, sn * (aa[0] / ang), sn * (aa[1] / ang), sn * (aa[2] / ang)};
-  const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const float w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
-  const float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-  const float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-  R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;     R[2] = 2 * wy + 2 * xz;
-  R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2;   R[5] = 2 * yz - 2 * wx;
-  R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;     R[8] = w2 - x2 - y2 + z2;
-}
-
-struct ManoArgs {
-  const float* pose6d;  // [B][ld6] (first 96 used)
-  const float* betas;   // [B][ldb] (first 10 used)
-  int ld6, ldb;
-  const float *shapeT, *poseT, *vtmpl, *jreg, *skin, *hands_mean;  // [10][NC], [135][NC], [NC], [16][778], [778][16], [45]
-  float *verts, *joints, *rotmat, *aa;                             // [B][778][3], [B][21][3], [B][16][9], [B][48]
-};
-
-__global__ __launch_bounds__(256) void mano_kernel(ManoArgs a) {
-  __shared__ float vsh[NC];        // v_shaped -> v_posed -> posed vertices (metres)
-  __shared__ float Rj[NJ][9];      // rotations the MANO layer uses (Rodrigues of the axis-angle pose)
-  __shared__ float pmap[135];
-  __shared__ float beta[10];
-  __shared__ float Jr[NJ][3];
-  __shared__ float G[NJ][12], G2[NJ][12];  // global joint transforms (3x4), and with the rest pose removed
-  const int b = blockIdx.x, t = threadIdx.x;
-  if (t < 10) beta[t] = a.betas[(long)b * a.ldb + t];
-  if (t < NJ) {
-    float R[9], aa[3];
-    rot6d_to_mat(a.pose6d + (long)b * a.ld6 + t * 6, R);
-    mat_to_aa(R, aa);
-    for (int i = 0; i < 9; ++i) a.rotmat[((long)b * NJ + t) * 9 + i] = R[i];
-    for (int i = 0; i < 3; ++i) a.aa[(long)b * 48 + t * 3 + i] = aa[i];
-    if (t > 0)
-      for (int i = 0; i < 3; ++i) aa[i] = a.hands_mean[(t - 1) * 3 + i] + aa[i];
-    rodrigues(aa, Rj[t]);
-    if (t > 0)
-      for (int i = 0; i < 9; ++i) pmap[(t - 1) * 9 + i] = Rj[t][i] - ((i == 0 || i == 4 || i == 8) ? 1.0f : 0.0f);
-  }
-  __syncthreads();
-  for (int c = t; c < NC; c += 256) {  // shape blend
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) v = fmaf(a.shapeT[(long)k * NC + c], beta[k], v);
-    vsh[c] = v + a.vtmpl[c];
-  }
-  __syncthreads();
-  {  // joint regression from the shaped (un-posed) vertices: 48 dot products of length 778, 12 per wave
-    const int wave = t >> 6, lane = t & 63;
-    for (int o = wave; o < NJ * 3; o += 4) {
-      const int j = o / 3, d = o - j * 3;
-      float s = 0.f;
-      for (int v = lane; v < NV; v += 64) s = fmaf(a.jreg[(long)j * NV + v], vsh[v * 3 + d], s);
-      s = wave_sum(s);
-      if (lane == 0) Jr[j][d] = s;
-    }
-  }
-  __syncthreads();
-  for (int c = t; c < NC; c += 256) {  // pose blend (in place: each coordinate is touched by exactly one thread)
-    float v = 0.f;
-    for (int k = 0; k < 135; ++k) v = fmaf(a.poseT[(long)k * NC + c], pmap[k], v);
-    vsh[c] += v;
-  }
-  if (t == 0) {  // kinematic chain, parents precede children
-    for (int j = 0; j < NJ; ++j) {
-      const int p = kManoParent[j];
-      float loc[12];
-      for (int r = 0; r < 3; ++r) {
-        loc[r * 4 + 0] = Rj[j][r * 3 + 0];
-        loc[r * 4 + 1] = Rj[j][r * 3 + 1];
-        loc[r * 4 + 2] = Rj[j][r * 3 + 2];
-        loc[r * 4 + 3] = p < 0 ? Jr[j][r] : Jr[j][r] - Jr[p][r];
-      }
-      if (p < 0) {
-        for (int i = 0; i < 12; ++i) G[j][i] = loc[i];
-      } else {
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 4; ++c) {
-            float s = G[p][r * 4 + 0] * loc[0 * 4 + c] + G[p][r * 4 + 1] * loc[1 * 4 + c] + G[p][r * 4 + 2] * loc[2 * 4 + c];
-            if (c == 3) s += G[p][r * 4 + 3];
-            G[j][r * 4 + c] = s;
-          }
-      }
-      for (int r = 0; r < 3; ++r) {
-        const float corr = G[j][r * 4 + 0] * Jr[j][0] + G[j][r * 4 + 1] * Jr[j][1] + G[j][r * 4 + 2] * Jr[j][2];
-        G2[j][r * 4 + 0] = G[j][r * 4 + 0];
-        G2[j][r * 4 + 1] = G[j][r * 4 + 1];
-        G2[j][r * 4 + 2] = G[j][r * 4 + 2];
-        G2[j][r * 4 + 3] = G[j][r * 4 + 3] - corr;
-      }
-    }
-  }
-  __syncthreads();
-  for (int v = t; v < NV; v += 256) {  // linear-blend skinning
-    float T[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) T[i] = 0.f;
-    for (int j = 0; j < NJ; ++j) {
-      const float w = a.skin[(long)v * NJ + j];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) T[i] = fmaf(w, G2[j][i], T[i]);
-    }
-    const float px = vsh[v * 3 + 0], py = vsh[v * 3 + 1], pz = vsh[v * 3 + 2];
-    float o[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = T[r * 4 + 0] * px + T[r * 4 + 1] * py + T[r * 4 + 2] * pz + T[r * 4 + 3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      vsh[v * 3 + r] = o[r];
-      a.verts[((long)b * NV + v) * 3 + r] = o[r] * 1000.0f;
-    }
-  }
-  __syncthreads();
-  if (t < 21 * 3) {
-    const int i = t / 3, d = t - i * 3;
-    const int src = kManoOut[i];
-    const float v = src < NJ ? G[src][d * 4 + 3] : vsh[kManoTip[src - NJ] * 3 + d];
-    a.joints[((long)b * 21 + i) * 3 + d] = v * 1000.0f;
-  }
-}
-
 }  // namespace
 
 extern "C" long kpf_cbam_workspace_floats(int B, int HW, int C) {
@@ -502,18 +314,3 @@ extern "C" int kpf_upnearest2x_add_f32(const float* low, const float* up1, float
   return kpf_check_launch("kpf_upnearest2x_add_f32");
 }
 
-extern "C" int kpf_mano_forward_f32(const float* pose6d, int ld6, const float* betas, int ldb, const float* shapedirs_t,
-                                    const float* posedirs_t, const float* v_template, const float* j_regressor, const float* skin_weights,
-                                    const float* hands_mean, float* verts, float* joints, float* rotmat, float* pose_aa, int B,
-                                    void* stream) {
-  KPF_REQUIRE(pose6d && betas && shapedirs_t && posedirs_t && v_template && j_regressor && skin_weights && hands_mean && verts && joints &&
-                  rotmat && pose_aa,
-              "kpf_mano_forward_f32: null pointer");
-  KPF_REQUIRE(B > 0 && ld6 >= 96 && ldb >= 10, "kpf_mano_forward_f32: bad shape B=%d ld6=%d ldb=%d", B, ld6, ldb);
-  ManoArgs a;
-  a.pose6d = pose6d; a.betas = betas; a.ld6 = ld6; a.ldb = ldb;
-  a.shapeT = shapedirs_t; a.poseT = posedirs_t; a.vtmpl = v_template; a.jreg = j_regressor; a.skin = skin_weights; a.hands_mean = hands_mean;
-  a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.aa = pose_aa;
-  hipLaunchKernelGGL(mano_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  return kpf_check_launch("kpf_mano_forward_f32");
-}

@@ -146,6 +146,15 @@ class PoseNetPlan:
 # ----------------------------------------------------------------------------------------------------------------
 # a19 MANO regression head (model/mano_head.py:177-225)
 # ----------------------------------------------------------------------------------------------------------------
+def mano_model_arrays(sd, device, p="mano_layer."):
+    """The ManoLayer buffers in the layout of the kpf_mano_* entries (include/kpf.h): (shapedirs_t [10][2334], posedirs_t [135][2334], v_template [2334],
+    j_regressor [16][778], skin_weights [778][16], hands_mean [45]), fp32 on `device`."""
+    f = lambda k: sd[p + k].detach().float().to(device)  # noqa: E731
+    return (f("th_shapedirs").reshape(778 * 3, 10).t().contiguous(), f("th_posedirs").reshape(778 * 3, 135).t().contiguous(),
+            f("th_v_template").reshape(778 * 3).contiguous(), f("th_J_regressor").contiguous(), f("th_weights").contiguous(),
+            f("th_hands_mean").reshape(45).contiguous())
+
+
 class ManoHeadPlan:
     def __init__(self, sd, device):
         self.base = []
@@ -157,13 +166,7 @@ class ManoHeadPlan:
         w = torch.cat([sd["pose_reg.weight"], sd["shape_reg.weight"]], 0)
         b = torch.cat([sd["pose_reg.bias"], sd["shape_reg.bias"]], 0)
         self.reg = PackedConv(w, b, device)
-        f = lambda k: sd["mano_layer." + k].detach().float().to(device)  # noqa: E731
-        self.shape_t = f("th_shapedirs").reshape(778 * 3, 10).t().contiguous()
-        self.pose_t = f("th_posedirs").reshape(778 * 3, 135).t().contiguous()
-        self.vtmpl = f("th_v_template").reshape(778 * 3).contiguous()
-        self.jreg = f("th_J_regressor").contiguous()
-        self.skin = f("th_weights").contiguous()
-        self.hands_mean = f("th_hands_mean").reshape(45).contiguous()
+        self.shape_t, self.pose_t, self.vtmpl, self.jreg, self.skin, self.hands_mean = mano_model_arrays(sd, device)
 
     def __call__(self, features):
         lib = L.load()

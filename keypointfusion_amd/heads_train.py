@@ -2,8 +2,10 @@
 MANO regression head model/mano_head.py:177-225) — autograd-connected outputs on the module's own Parameters, like KPFusion's train graph: every convolution /
 Linear runs forward, data- and weight-gradient on the HIP GEMM kernels (training.conv2d_nhwc / linear_hip), BatchNorm uses batch statistics and updates its
 running estimates on the HIP kernels (training.batchnorm_relu_rows; F.batch_norm for CBAM's one-channel norm, which the row kernels' quad width does not
-cover), activations stay NHWC between them; pooling, nearest up-sampling, gates and the MANO layer's rigid-body algebra (Rodrigues, blend shapes, linear-blend
-skinning: a few hundred small batched products) are torch ops under autograd.  The reference's heads are ordinary autograd modules (model/cbam.py:84-94) that
+cover), activations stay NHWC between them; pooling, nearest up-sampling and gates are torch ops under autograd.  The MANO layer's rigid-body algebra
+(Rodrigues, blend shapes, linear-blend skinning) is, by choice, either torch ops under autograd (layer="torch", the default: a few hundred small batched
+products) or ManoLayerHip (layer="hip"): kpf_mano_forward_f32 forward and kpf_mano_backward_f32 backward, one launch each, same gradients.
+The reference's heads are ordinary autograd modules (model/cbam.py:84-94) that
 KPFusion.forward never calls; these forwards exist so that a caller who wires them into a training loop gets gradients instead of a
 NotImplementedError.  Eval mode keeps the inference plans of heads.py."""
 import torch
@@ -162,8 +164,58 @@ def _mano_layer(t, pose_aa, betas, p="mano_layer"):
     return verts * 1000, jtr * 1000
 
 
-def mano_head_train_forward(module, features):
-    """model/mano_head.py:208-225 in train mode: the reference's result dict, autograd-connected to the MLP's Parameters."""
+class ManoLayerHip(torch.autograd.Function):
+    """The head's tail (6D rotations -> rotation matrices -> axis-angle -> MANO layer) as one launch each way: kpf_mano_forward_f32, and
+    kpf_mano_backward_f32, which recomputes the forward on chip (nothing is saved but the two inputs).  pose6d [B, 96], betas [B, 10] and the packed model
+    arrays of heads.mano_model_arrays -> (verts [B, 778, 3] mm, joints [B, 21, 3] mm in the head's order, rotmat [B, 16, 3, 3], pose_aa [B, 48]); gradients
+    go to pose6d and betas only.  They are autograd's of _rot6d_to_mat / _mat_to_aa / _mano_layer below, except at an exact identity rotation, where autograd
+    gives NaN and the kernel the finite limit."""
+
+    @staticmethod
+    def forward(ctx, pose6d, betas, *model):
+        from . import lib as L
+        p6, bt = pose6d.detach().float().contiguous(), betas.detach().float().contiguous()
+        B, dev = p6.shape[0], p6.device
+        assert p6.shape == (B, 96) and bt.shape == (B, 10) and len(model) == 6
+        verts, joints = torch.empty(B, 778, 3, device=dev), torch.empty(B, 21, 3, device=dev)
+        rotmat, aa = torch.empty(B, 16, 3, 3, device=dev), torch.empty(B, 48, device=dev)
+        L.check(L.load().kpf_mano_forward_f32(p6.data_ptr(), 96, bt.data_ptr(), 10, *[m.data_ptr() for m in model], verts.data_ptr(), joints.data_ptr(),
+                                              rotmat.data_ptr(), aa.data_ptr(), B, torch.cuda.current_stream().cuda_stream), "kpf_mano_forward_f32")
+        ctx.save_for_backward(p6, bt, *model)
+        ctx.dtypes = (pose6d.dtype, betas.dtype)
+        ctx.set_materialize_grads(False)  # an output nobody differentiated arrives as None and goes to the kernel as a null pointer
+        return verts, joints, rotmat, aa
+
+    @staticmethod
+    def backward(ctx, d_verts, d_joints, d_rotmat, d_aa):
+        from . import lib as L
+        p6, bt, *model = ctx.saved_tensors
+        B = p6.shape[0]
+        grads = [None if g is None else g.float().contiguous() for g in (d_verts, d_joints, d_rotmat, d_aa)]
+        d6, db = torch.empty_like(p6), torch.empty_like(bt)
+        L.check(L.load().kpf_mano_backward_f32(p6.data_ptr(), 96, bt.data_ptr(), 10, *[m.data_ptr() for m in model],
+                                               *[None if g is None else g.data_ptr() for g in grads], d6.data_ptr(), 96, db.data_ptr(), 10, B,
+                                               torch.cuda.current_stream().cuda_stream), "kpf_mano_backward_f32")
+        return (d6.to(ctx.dtypes[0]), db.to(ctx.dtypes[1])) + (None,) * 6
+
+
+def _mano_model(module, device):
+    """heads.mano_model_arrays of the module's ManoLayer buffers; packed again only when a buffer was replaced or written (the hand model is constant)."""
+    from .heads import mano_model_arrays
+    t = _params(module)
+    src = [t["mano_layer.th_" + k] for k in ("shapedirs", "posedirs", "v_template", "J_regressor", "weights", "hands_mean")]
+    key = (device, tuple((s.data_ptr(), s._version) for s in src))
+    ent = module.__dict__.get("_mano_model_arrays")
+    if ent is None or ent[0] != key:
+        ent = module.__dict__["_mano_model_arrays"] = (key, mano_model_arrays(t, device))
+    return ent[1]
+
+
+def mano_head_train_forward(module, features, layer="torch"):
+    """model/mano_head.py:208-225 in train mode: the reference's result dict, autograd-connected to the MLP's Parameters.  layer = "torch": the hand model
+    as torch ops under autograd; "hip": ManoLayerHip, one launch forward and one backward."""
+    if layer not in ("torch", "hip"):
+        raise ValueError("layer must be 'torch' or 'hip', not %r" % (layer,))
     t = _params(module)
     h = features.float()
     i = 0
@@ -172,6 +224,9 @@ def mano_head_train_forward(module, features):
         i += 2
     pose6d = linear_hip(h.contiguous(), t["pose_reg.weight"], t["pose_reg.bias"])
     shape = linear_hip(h.contiguous(), t["shape_reg.weight"], t["shape_reg.bias"])
+    if layer == "hip":
+        verts, joints, R, aa = ManoLayerHip.apply(pose6d, shape, *_mano_model(module, features.device))
+        return {"verts3d": verts, "joints3d": joints, "mano_shape": shape, "mano_pose": R, "mano_pose_aa": aa}
     R = _rot6d_to_mat(pose6d.reshape(-1, 6))
     aa = _mat_to_aa(R).reshape(-1, 48)
     verts, joints = _mano_layer(t, aa, shape)

@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 25  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 26  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -54,6 +54,11 @@ class ColsumDesc(C.Structure):  # kpf_colsum_desc (include/kpf.h)
 class WgradReduceDesc(C.Structure):  # kpf_wgrad_reduce_desc (include/kpf.h)
     _fields_ = [("part", C.c_void_p), ("dbpart", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("g_ws", C.c_long)] + [
         (n, C.c_int) for n in "S N K Cin KHW nkb ndb groups Cin_out N_out kind first_block".split()]
+
+
+class ManoFitCfg(C.Structure):  # kpf_mano_fit_cfg (include/kpf.h)
+    _fields_ = [("iters", C.c_int)] + [(n, C.c_float) for n in "lr_pose lr_shape lr_trans beta1 beta2 eps lambda_shape lambda_pose".split()] + [
+        ("init_trans", C.c_int), ("joint_map", C.c_int * 21)]
 
 
 class WgradPlan(C.Structure):  # kpf_wgrad_plan (include/kpf.h)
@@ -124,6 +129,8 @@ _SIGS = {
     "kpf_maxpool2x2_f32": [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_upnearest2x_add_f32": [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P],
     "kpf_mano_forward_f32": [_P, C.c_int, _P, C.c_int] + [_P] * 10 + [C.c_int, _P],
+    "kpf_mano_backward_f32": [_P, C.c_int, _P, C.c_int] + [_P] * 10 + [_P, C.c_int, _P, C.c_int, C.c_int, _P],
+    "kpf_mano_fit_f32": [_P] * 8 + [C.POINTER(ManoFitCfg)] + [_P] * 8 + [C.c_int, _P],
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],
     "kpf_xattn_weight_floats": [],

@@ -68,6 +68,7 @@ class mano_regHead(SpecModule):
             raise ValueError("unexpected MANO kinematic tree %s" % parents)
         self.fingertip_vertex_idx = [728, 353, 442, 576, 694]  # model/mano_head.py:182 (attribute kept; unused by forward)
         self.pose6d_size, self.mano_pose_size = 16 * 6, 16 * 3
+        self.hip_mano_layer = False  # train mode: True runs the hand model and its gradient as one HIP launch each (heads_train.ManoLayerHip) instead of torch ops
         self._materialise(mano_head_spec(feature_size, tuple(mano_neurons)), seed, prefix="mano_head.", values=mano_layer_buffers(mano_model),
                           buffers=("mano_layer.",))
 
@@ -76,7 +77,7 @@ class mano_regHead(SpecModule):
         if self.training:  # autograd-connected outputs on this module's Parameters (keypointfusion_amd/heads_train.py: convolutions / Linears on the HIP GEMM)
             from ..heads_train import mano_head_train_forward
             with torch.cuda.device(features.device):
-                return mano_head_train_forward(self, features)
+                return mano_head_train_forward(self, features, layer="hip" if self.hip_mano_layer else "torch")
         from ..heads import ManoHeadPlan
         plan = self._plan(features.device, lambda sd, dev: ManoHeadPlan(sd, dev))
         with torch.cuda.device(features.device):

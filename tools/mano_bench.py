@@ -1,0 +1,76 @@
+"""Timing of the MANO layer in HIP: the MANO head's train step (forward + backward to the features and the MLP's parameters) at B = 32 with the
+hand model as torch ops under autograd (layer="torch") against heads_train.ManoLayerHip (layer="hip"), and the joint fit mano_fit.ManoFitter at B = 1 and 32
+with iters = 10 and 50.  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
+
+    python tools/mano_bench.py
+    python tools/mano_bench.py --reps 50
+
+Synthetic hand model and weights.  Times are host clocks around `reps` calls that end in one device synchronise, after a warm-up.  No figure here is a pass bar."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _timed(fn, reps, torch):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mano_bench.json"))
+    args = ap.parse_args()
+
+    import torch
+    from keypointfusion_amd.heads_train import mano_head_train_forward
+    from keypointfusion_amd.mano_fit import ManoFitter
+    from keypointfusion_amd.model.mano_head import mano_regHead
+
+    dev = torch.device("cuda:0")
+    rec = {"tool": "mano_bench", "reps": args.reps}
+    m = mano_regHead().to(dev).train()
+    gen = torch.Generator().manual_seed(0)
+    feats = torch.randn(32, 1024, generator=gen).to(dev)
+    keys = ("verts3d", "joints3d", "mano_shape", "mano_pose", "mano_pose_aa")
+    for layer in ("torch", "hip"):
+        def step():
+            x = feats.clone().requires_grad_(True)
+            out = mano_head_train_forward(m, x, layer=layer)
+            sum(out[k].sum() for k in keys).backward()
+            m.zero_grad(set_to_none=True)
+
+        rec["head_train_step_ms_B32_%s" % layer] = _timed(step, args.reps, torch)
+
+    # the fit: targets are the synthetic hand's own joints at a random pose, moved half a metre in front of the camera
+    with torch.no_grad():
+        pose = m.eval()(feats)
+    target = (pose["joints3d"] + torch.tensor([30.0, -20.0, 600.0], device=dev)).contiguous()
+    for B in (1, 32):
+        for iters in (10, 50):
+            fitter = ManoFitter(m, dev, iters=iters)
+            y = target[:B].contiguous()
+            rec["fit_ms_B%d_iters%d" % (B, iters)] = _timed(lambda: fitter.fit(y), args.reps, torch)
+            out = fitter.fit(y)
+            rec["fit_residual_mm_B%d_iters%d" % (B, iters)] = [float(v) for v in out["residual"].mean(0)]
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
