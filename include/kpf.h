@@ -331,6 +331,44 @@ int kpf_mano_fit_f32(const float* target /*[B][21][3] mm*/, const float* weight 
     float* verts /*[B][778][3] or NULL*/, float* joints /*[B][21][3], target order*/, float* rotmat /*[B][16][9] or NULL*/,
     float* residual /*[B][2]*/, int* status /*[B]*/, int B, void* stream);
 
+/* The fit above with a vertex term (ABI 27).  Per sample, in mm^2:
+ *   L = [sw > 0] (1/sw) sum_i w_i |J_map[i] + t - y_i|^2 + lambda_verts [sv > 0] (1/sv) sum_v u_v |V_v + t - c_v|^2
+ *     + lambda_shape |beta|^2 + lambda_pose |theta[3:]|^2
+ * with vert_target c [B][778][3] in mm, vert_weight u [B][778] >= 0, sw = sum w, sv = sum u.  A term whose weights sum to 0 contributes nothing; a
+ * target under weight 0 (joint or vertex) is selected out, never multiplied.  vert_target == vert_weight == NULL: no vertex term, and every output is
+ * bit for bit kpf_mano_fit_f32's (residual columns 0-1; columns 2-3 are 0).  target == NULL, or weights all 0, with a vertex term: a vertex-only fit.
+ * init_trans uses the joints when sw > 0, otherwise t = sum u_v (c_v - V_v) / sv.  residual [B][4]: the mean weighted joint distance at the first
+ * state (after init_trans) and at the final one, then the mean weighted vertex distance at the same two states; a term without weight reports 0.
+ * status [B] bits: 1 BOTH weight sums are 0; 2 a joint or vertex target under a positive weight is not finite -- either way the state keeps its bits
+ * and the outputs evaluate it.  Each iteration skins all 778 vertices; the vertex gradient and the translation's are reduced in a fixed order (wave
+ * butterfly, then the four waves in order), no atomics: bits depend neither on B nor on the sample's position nor on a replay.  The output of
+ * kpf_mano_assoc_f32 is this entry's vertex input; a ground-truth mesh is passed with u = 1. */
+typedef struct kpf_mano_fit_mesh_cfg {
+  int iters;                       /* as kpf_mano_fit_cfg, field for field ... */
+  float lr_pose, lr_shape, lr_trans, beta1, beta2, eps;
+  float lambda_shape, lambda_pose; int init_trans;
+  int joint_map[21];
+  float lambda_verts;              /* ... plus the vertex term's factor, >= 0 */
+} kpf_mano_fit_mesh_cfg;           /* HOST struct */
+int kpf_mano_fit_mesh_f32(const float* target /*[B][21][3] mm, or NULL*/, const float* weight /*[B][21] >= 0, or NULL = ones*/,
+    const float* vert_target /*[B][778][3] mm, or NULL*/, const float* vert_weight /*[B][778] >= 0, or NULL; both or neither*/,
+    const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+    const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_cfg* cfg,
+    float* pose_aa /*[B][48] in/out*/, float* betas /*[B][10] in/out*/, float* trans /*[B][3] mm in/out*/,
+    float* verts /*[B][778][3] or NULL*/, float* joints /*[B][21][3], target order*/, float* rotmat /*[B][16][9] or NULL*/,
+    float* residual /*[B][4]*/, int* status /*[B]*/, int B, void* stream);
+
+/* Depth points -> per-vertex targets (ABI 27), one workgroup per hand.  points [B][N][3] in camera-space mm (the frame of the tracker's cam_mm),
+ * 1 <= N <= 4096 (any other N is refused and nothing is written); point_weight [B][N] or NULL = ones; verts [B][778][3] (a fit's verts);
+ * max_dist2: squared gate in mm^2.  idx [B][N]: the nearest vertex or -1; vert_target / vert_weight: per vertex the weighted centroid and the summed
+ * weight of the points assigned to it (0 and 0 where there are none); stats [B][2]: the number of matched points and their mean distance to their
+ * vertex in mm.  Arithmetic, every operation individually rounded (no fma): dx = p.x - v.x, ...; d2 = (dx*dx + dy*dy) + dz*dz; the argmin runs over
+ * v = 0..777 ascending with a strict < (from d2 = +inf at v = 0); a point is matched iff its weight > 0, its coordinates are finite and
+ * d2 <= max_dist2; per vertex W = sum w_n and S = sum w_n * p_n over its points in ascending n, c = S / W; stats[1] = (sum over matched n, ascending,
+ * of sqrt(d2_n)) / count.  A numpy-fp32 restatement gives the same bits. */
+int kpf_mano_assoc_f32(const float* points, const float* point_weight, const float* verts, float max_dist2,
+    int* idx, float* vert_target, float* vert_weight, float* stats, int B, int N, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Reduced-precision path (BASELINE configs[2] bf16, configs[4] fp16): same operators on 16-bit NHWC activations.  `dtype` is
  * KPF_DT_BF16 or KPF_DT_F16; LayerNorm / bias / layer-scale parameters and the depthwise taps stay fp32.
@@ -972,7 +1010,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 26
+#define KPF_ABI_VERSION 27
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -2,7 +2,9 @@
 //   kpf_mano_forward_f32   6D rotations + betas -> vertices, joints, rotations, axis-angle            (eval path of heads.ManoHeadPlan)
 //   kpf_mano_backward_f32  its derivative: recomputes the forward in LDS, then walks the stages backwards (heads_train.ManoLayerHip)
 //   kpf_mano_fit_f32       Adam on pose / shape / translation against 21 target joints, every iteration inside the one launch (mano_fit.ManoFitter)
-// The three share the stage functions below; the forward's arithmetic is the text it had in kpf_aux.hip (tests/test_heads_gpu.py pins its bits).
+//   kpf_mano_fit_mesh_f32  the same fit with a vertex term (778 weighted vertex targets): the second instantiation of the fit kernel
+//   kpf_mano_assoc_f32     depth points -> nearest vertex, per-vertex centroid and weight: the vertex targets of the fit above (its own kernel, further down)
+// The fits share the stage functions below; the forward's arithmetic is the text it had in kpf_aux.hip (tests/test_heads_gpu.py pins its bits).
 // Every reduction has a fixed order (wave butterflies, then a fixed sum over the four waves) and there are no atomics: a replay is bit-identical and a
 // sample's bits do not depend on B or on its position in the batch.
 #include <math.h>
@@ -526,8 +528,11 @@ __global__ __launch_bounds__(256) void mano_backward_kernel(ManoBwdArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 struct ManoFitArgs {
   const float *target, *weight;
+  const float *vtarget, *vweight;  // [B][778][3] mm, [B][778] >= 0: the vertex term (the instantiation with VT only)
   ManoModel m;
   kpf_mano_fit_cfg c;
+  float lambda_verts;
+  int res_ld;                      // 2: residual [B][2] (joints before / after); 4: [B][4], the vertex distances before / after in columns 2, 3
   float *pose, *betas, *trans, *verts, *joints, *rotmat, *residual;
   int* status;
 };
@@ -540,10 +545,57 @@ struct ManoFitLds {
   float tip[5][3];
   float sw;
   int status;
+  float red[4][4];                      // the four waves' partial sums of a reduction over the vertices
+  float sv;                             // the sum of the vertex weights
+  double redd[4][3];                    // the same for the one reduction in double (init_trans from the vertices)
 };
 
-// P -> the model's 21 joints (f.Jm); s holds the forward state afterwards.  Ends with a barrier.
-__device__ __forceinline__ void mano_fit_eval(const ManoModel& m, ManoLds& s, ManoFitLds& f, int t) {
+// Sum of up to four per-thread values over the workgroup in a fixed order: the xor butterfly inside each wave, then the four waves' partials in wave order
+// (as mano_backward_lds reduces d G2).  All 256 threads; out[i] is valid in every thread.  Barriers before the partials are overwritten and after they are written.
+template <int N>
+__device__ __forceinline__ void mano_block_sum(ManoFitLds& f, int t, const float* in, float* out) {
+  const int wave = t >> 6, lane = t & 63;
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const float sum = wave_sum(in[i]);
+    if (lane == 0) f.red[wave][i] = sum;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; ++i) out[i] = ((f.red[0][i] + f.red[1][i]) + f.red[2][i]) + f.red[3][i];
+}
+
+// The same for three doubles
+__device__ __forceinline__ void mano_block_sum3d(ManoFitLds& f, int t, const double* in, double* out) {
+  const int wave = t >> 6, lane = t & 63;
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double v = in[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) f.redd[wave][i] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 3; ++i) out[i] = ((f.redd[0][i] + f.redd[1][i]) + f.redd[2][i]) + f.redd[3][i];
+}
+
+// Vertex v of the state in s, in mm without the translation, into vm[v]: lanes over vertices, as the final skinning
+__device__ __forceinline__ void mano_fit_skin_all(const ManoModel& m, const ManoLds& s, float* vm, int t) {
+  for (int v = t; v < NV; v += 256) {
+    float o[3];
+    mano_skin_vertex(m, s, v, o);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) vm[v * 3 + r] = o[r] * 1000.0f;
+  }
+}
+
+// P -> the model's 21 joints (f.Jm); s holds the forward state afterwards.  With the vertex term every vertex is skinned (vm[778][3], mm, without the
+// translation) and the tips are read from there; without it only the five tips are.  Ends with a barrier.
+template <bool VT>
+__device__ __forceinline__ void mano_fit_eval(const ManoModel& m, ManoLds& s, ManoFitLds& f, float* vm, int t) {
   if (t < 10) s.beta[t] = f.P[48 + t];
   if (t < NJ) {
     float aa[3] = {f.P[t * 3 + 0], f.P[t * 3 + 1], f.P[t * 3 + 2]};
@@ -552,13 +604,21 @@ __device__ __forceinline__ void mano_fit_eval(const ManoModel& m, ManoLds& s, Ma
     mano_set_rotation(s, t, aa);
   }
   mano_blend_chain(m, s, t);
-  if (t < 5) mano_skin_vertex(m, s, kManoTip[t], f.tip[t]);
+  if constexpr (VT) {
+    mano_fit_skin_all(m, s, vm, t);
+  } else {
+    if (t < 5) mano_skin_vertex(m, s, kManoTip[t], f.tip[t]);
+  }
   __syncthreads();
   if (t < 21 * 3) {
     const int i = t / 3, d = t - i * 3;
     const int src = kManoOut[i];
-    const float v = src < NJ ? s.G[src][d * 4 + 3] : f.tip[src - NJ][d];
-    f.Jm[i][d] = v * 1000.0f;
+    if constexpr (VT) {
+      f.Jm[i][d] = src < NJ ? s.G[src][d * 4 + 3] * 1000.0f : vm[kManoTip[src - NJ] * 3 + d];
+    } else {
+      const float v = src < NJ ? s.G[src][d * 4 + 3] : f.tip[src - NJ][d];
+      f.Jm[i][d] = v * 1000.0f;
+    }
   }
   __syncthreads();
 }
@@ -574,11 +634,67 @@ __device__ __forceinline__ float mano_fit_residual(const ManoFitLds& f) {  // me
   return sum / f.sw;
 }
 
+// The vertex term's share of one thread: vertices t, t + 256, ... of vm (mm, without the translation) against the targets and weights in global memory (they
+// stay in L2; LDS holds none of them).  A target under weight 0 is selected out, never multiplied.
+//   mano_vert_weights   -> in[0] = sum of the positive weights, in[1] = how many targets under a positive weight are not finite
+//   mano_vert_offset    -> in[d] = sum u_v (c_v - V_v)[d], in double           (init_trans of a vertex-only fit)
+//   mano_vert_distance  -> sum u_v |V_v + t - c_v|                             (the residual's numerator)
+//   mano_vert_gradient  -> vm[v] = d L / d (posed vertex v, metres) = 2 lambda u_v (V_v + t - c_v) / sv * 1000, every slot written exactly once,
+//                          in[d] = this thread's share of d L / d t
+__device__ __forceinline__ void mano_vert_weights(const float* c, const float* u, int t, float* in) {
+  in[0] = in[1] = 0.f;
+  for (int v = t; v < NV; v += 256) {
+    const float w = u[v];
+    if (!(w > 0.0f)) continue;
+    in[0] += w;
+    if (!(isfinite(c[v * 3 + 0]) && isfinite(c[v * 3 + 1]) && isfinite(c[v * 3 + 2]))) in[1] += 1.0f;
+  }
+}
+
+__device__ __forceinline__ void mano_vert_offset(const float* c, const float* u, const float* vm, int t, double* in) {
+  in[0] = in[1] = in[2] = 0.0;
+  for (int v = t; v < NV; v += 256) {
+    const float w = u[v];
+    if (!(w > 0.0f)) continue;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) in[d] = fma((double)w, (double)c[v * 3 + d] - (double)vm[v * 3 + d], in[d]);
+  }
+}
+
+__device__ __forceinline__ float mano_vert_distance(const float* c, const float* u, const float* vm, const float* tr, int t) {
+  float sum = 0.f;
+  for (int v = t; v < NV; v += 256) {
+    const float w = u[v];
+    if (!(w > 0.0f)) continue;
+    const float r0 = vm[v * 3 + 0] + tr[0] - c[v * 3 + 0], r1 = vm[v * 3 + 1] + tr[1] - c[v * 3 + 1], r2 = vm[v * 3 + 2] + tr[2] - c[v * 3 + 2];
+    sum = fmaf(w, sqrtf(r0 * r0 + r1 * r1 + r2 * r2), sum);
+  }
+  return sum;
+}
+
+__device__ __forceinline__ void mano_vert_gradient(const float* c, const float* u, float* vm, const float* tr, float lambda, float sv, int t, float* in) {
+  in[0] = in[1] = in[2] = 0.f;
+  for (int v = t; v < NV; v += 256) {
+    const float w = u[v];
+    const bool on = w > 0.0f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float gv = on ? 2.0f * lambda * w * (vm[v * 3 + d] + tr[d] - c[v * 3 + d]) / sv : 0.0f;
+      vm[v * 3 + d] = gv * 1000.0f;
+      in[d] += gv;
+    }
+  }
+}
+
+// VT: with the vertex term.  Without it the kernel is the joint fit as it was: every statement of that path is the one it had, and so are its bits.
+template <bool VT>
 __global__ __launch_bounds__(256) void mano_fit_kernel(ManoFitArgs a) {
   __shared__ ManoLds s;
   __shared__ ManoGradLds g;
   __shared__ ManoFitLds f;
   const int b = blockIdx.x, t = threadIdx.x;
+  const float* vc = VT ? a.vtarget + (long)b * NC : nullptr;
+  const float* vu = VT ? a.vweight + (long)b * NV : nullptr;
   if (t < 48) f.P[t] = a.pose[(long)b * 48 + t];
   else if (t < 58) f.P[t] = a.betas[(long)b * 10 + (t - 48)];
   else if (t < 61) f.P[t] = a.trans[(long)b * 3 + (t - 58)];
@@ -586,9 +702,15 @@ __global__ __launch_bounds__(256) void mano_fit_kernel(ManoFitArgs a) {
   if (t >= 64 && t < 64 + 21) {
     // every sum over the joints below runs in the model's order: a permuted joint_map with equally permuted targets gives the same bits
     const int i = t - 64, h = a.c.joint_map[i];
-    const float w = a.weight ? a.weight[(long)b * 21 + i] : 1.0f;
+    const float w = a.target ? (a.weight ? a.weight[(long)b * 21 + i] : 1.0f) : 0.0f;  // no joint targets (the mesh entry allows it): every joint weight is 0
     f.W[h] = w;
     for (int d = 0; d < 3; ++d) f.Y[h][d] = w > 0.0f ? a.target[((long)b * 21 + i) * 3 + d] : 0.0f;  // a target of weight 0 is selected out, not multiplied
+  }
+  float vstat[2] = {0.f, 0.f};  // sum of the vertex weights, non-finite vertex targets under a positive weight
+  if constexpr (VT) {
+    float in[2];
+    mano_vert_weights(vc, vu, t, in);
+    mano_block_sum<2>(f, t, in, vstat);
   }
   __syncthreads();
   if (t == 0) {
@@ -599,46 +721,85 @@ __global__ __launch_bounds__(256) void mano_fit_kernel(ManoFitArgs a) {
       sw += f.W[i];
       if (!(isfinite(f.Y[i][0]) && isfinite(f.Y[i][1]) && isfinite(f.Y[i][2]))) st |= 2;
     }
-    if (!(sw > 0.0f)) st |= 1;
+    if (VT && vstat[1] > 0.0f) st |= 2;
+    if (!(sw > 0.0f) && !(VT && vstat[0] > 0.0f)) st |= 1;  // with the vertex term: both weight sums are 0
     f.sw = sw;
+    f.sv = vstat[0];
     f.status = st;
   }
   __syncthreads();
   const bool ok = f.status == 0;  // otherwise: no init, no iteration, the state keeps its bits and the outputs evaluate it
   const int iters = ok ? a.c.iters : 0;
-  mano_fit_eval(a.m, s, f, t);
+  mano_fit_eval<VT>(a.m, s, f, g.dv, t);
   if (iters > 0 && a.c.init_trans) {  // "before iteration 1": iters == 0 only evaluates
-    if (t < 3) {
-      float sum = 0.f;
-      for (int i = 0; i < 21; ++i)
-        if (f.W[i] > 0.0f) sum = fmaf(f.W[i], f.Y[i][t] - f.Jm[i][t], sum);
-      f.P[58 + t] = sum / f.sw;
+    if constexpr (!VT) {
+      if (t < 3) {
+        float sum = 0.f;
+        for (int i = 0; i < 21; ++i)
+          if (f.W[i] > 0.0f) sum = fmaf(f.W[i], f.Y[i][t] - f.Jm[i][t], sum);
+        f.P[58 + t] = sum / f.sw;
+      }
+    } else if (f.sw > 0.0f) {
+      // With the vertex term the mean offset is summed in double and rounded once: at half a metre one float ulp is 6e-5 mm, a sum of 21 such offsets in
+      // float is off by about that, and an error of t is the same for every vertex -- it does not average out of the pose gradient as a vertex's own
+      // rounding does, and was the largest term of the first step's pose error
+      if (t < 3) {
+        double sum = 0.0, den = 0.0;
+        for (int i = 0; i < 21; ++i)
+          if (f.W[i] > 0.0f) {
+            sum = fma((double)f.W[i], (double)f.Y[i][t] - (double)f.Jm[i][t], sum);
+            den += (double)f.W[i];
+          }
+        f.P[58 + t] = (float)(sum / den);
+      }
+    } else {  // no joint carries weight: the translation comes from the vertices
+      double in[3], off[3];
+      mano_vert_offset(vc, vu, g.dv, t, in);
+      mano_block_sum3d(f, t, in, off);
+      if (t < 3) f.P[58 + t] = (float)((t == 0 ? off[0] : (t == 1 ? off[1] : off[2])) / (double)f.sv);
     }
     __syncthreads();
   }
-  if (t == 0) a.residual[(long)b * 2 + 0] = mano_fit_residual(f);
+  if (t == 0) a.residual[(long)b * a.res_ld + 0] = mano_fit_residual(f);
+  if constexpr (VT) {
+    float in = mano_vert_distance(vc, vu, g.dv, &f.P[58], t), sum;
+    mano_block_sum<1>(f, t, &in, &sum);
+    if (t == 0) a.residual[(long)b * a.res_ld + 2] = f.sv > 0.0f ? sum / f.sv : 0.0f;
+  } else {
+    if (t == 0 && a.res_ld == 4) a.residual[(long)b * 4 + 2] = 0.0f;
+  }
   const double b1 = (double)a.c.beta1, b2 = (double)a.c.beta2;
   const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2);
   double b1k = 1.0, b2k = 1.0;
   for (int it = 1; it <= iters; ++it) {
-    if (it > 1) mano_fit_eval(a.m, s, f, t);
+    if (it > 1) mano_fit_eval<VT>(a.m, s, f, g.dv, t);
     // L = (1 / sum w) sum_i w_i |J_map[i] + t - y_i|^2 + lambda_shape |beta|^2 + lambda_pose |theta[3:]|^2, mm^2
+    // (with the vertex term: + lambda_verts (1 / sum u) sum_v u_v |V_v + t - c_v|^2)
     if (t < 63) {
       const int i = t / 3, d = t - i * 3;
       f.gJ[i][d] = f.W[i] > 0.0f ? 2.0f * f.W[i] * (f.Jm[i][d] + f.P[58 + d] - f.Y[i][d]) / f.sw : 0.0f;
     }
-    for (int c = t; c < NC; c += 256) g.dv[c] = 0.0f;
+    float vt[3] = {0.f, 0.f, 0.f};  // the vertex term's d L / d t
+    if constexpr (VT) {
+      float in[3];
+      mano_vert_gradient(vc, vu, g.dv, &f.P[58], a.lambda_verts, f.sv, t, in);  // g.dv: the vertices of this state -> their gradient, in place
+      mano_block_sum<3>(f, t, in, vt);
+    } else {
+      for (int c = t; c < NC; c += 256) g.dv[c] = 0.0f;
+    }
     __syncthreads();
     if (t < 63) {  // x1000 output scale and the scatter to chain joints and tip vertices (kManoOut is a permutation: every slot is written once)
       const int i = t / 3, d = t - i * 3;
       const int src = kManoOut[i];
       const float v = f.gJ[i][d] * 1000.0f;
       if (src < NJ) g.dtg[src][d] = v;
+      else if constexpr (VT) g.dv[kManoTip[src - NJ] * 3 + d] += v;  // a tip vertex: its own term, then its joint row's (one thread per slot)
       else g.dv[kManoTip[src - NJ] * 3 + d] = v;
     }
     if (t >= 64 && t < 67) {
       float sum = 0.f;
       for (int i = 0; i < 21; ++i) sum += f.gJ[i][t - 64];
+      if constexpr (VT) sum += t == 64 ? vt[0] : (t == 65 ? vt[1] : vt[2]);
       f.Gd[58 + (t - 64)] = sum;
     }
     __syncthreads();
@@ -667,10 +828,17 @@ __global__ __launch_bounds__(256) void mano_fit_kernel(ManoFitArgs a) {
     }
     __syncthreads();
   }
-  if (iters > 0) mano_fit_eval(a.m, s, f, t);
+  if (iters > 0) mano_fit_eval<VT>(a.m, s, f, g.dv, t);
   if (t == 0) {
-    a.residual[(long)b * 2 + 1] = mano_fit_residual(f);
+    a.residual[(long)b * a.res_ld + 1] = mano_fit_residual(f);
     a.status[b] = f.status;
+  }
+  if constexpr (VT) {
+    float in = mano_vert_distance(vc, vu, g.dv, &f.P[58], t), sum;
+    mano_block_sum<1>(f, t, &in, &sum);
+    if (t == 0) a.residual[(long)b * a.res_ld + 3] = f.sv > 0.0f ? sum / f.sv : 0.0f;
+  } else {
+    if (t == 0 && a.res_ld == 4) a.residual[(long)b * 4 + 3] = 0.0f;
   }
   if (ok) {
     if (t < 48) a.pose[(long)b * 48 + t] = f.P[t];
@@ -693,6 +861,95 @@ __global__ __launch_bounds__(256) void mano_fit_kernel(ManoFitArgs a) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) a.verts[((long)b * NV + v) * 3 + r] = o[r] * 1000.0f + f.P[58 + r];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Association: each depth point's nearest vertex, and per vertex the weighted centroid and summed weight of its points -- the vertex targets of the fit
+// above, built without atomics.  One workgroup per hand.  Every operation is individually rounded (no contraction) and every sum runs in ascending index
+// order, so that a numpy-fp32 restatement gives the same bits (tests/mano_mesh_cases.py::associate_host).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int ASSOC_MAXN = 4096;
+
+struct ManoAssocArgs {
+  const float *points, *pweight, *verts;  // [B][N][3], [B][N] or null, [B][778][3]
+  float max_dist2;
+  int N;
+  int* idx;                               // [B][N]
+  float *vtarget, *vweight, *stats;       // [B][778][3], [B][778], [B][2]
+};
+
+struct ManoAssocLds {
+  float v[NC];
+  int idx[ASSOC_MAXN];
+  float dist[ASSOC_MAXN];  // a matched point's distance to its vertex, mm
+};
+
+__global__ __launch_bounds__(256) void mano_assoc_kernel(ManoAssocArgs a) {
+#pragma clang fp contract(off)
+  __shared__ ManoAssocLds s;
+  const int b = blockIdx.x, t = threadIdx.x, N = a.N;
+  const float* P = a.points + (long)b * N * 3;
+  const float* PW = a.pweight ? a.pweight + (long)b * N : nullptr;
+  for (int c = t; c < NC; c += 256) s.v[c] = a.verts[(long)b * NC + c];
+  __syncthreads();
+  for (int n = t; n < N; n += 256) {  // the nearest vertex: ascending v, strict <
+    const float px = P[n * 3 + 0], py = P[n * 3 + 1], pz = P[n * 3 + 2];
+    const float w = PW ? PW[n] : 1.0f;
+    float best = INFINITY;
+    int bi = 0;
+    for (int v = 0; v < NV; ++v) {
+      const float dx = __fsub_rn(px, s.v[v * 3 + 0]), dy = __fsub_rn(py, s.v[v * 3 + 1]), dz = __fsub_rn(pz, s.v[v * 3 + 2]);
+      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+      if (d2 < best) {
+        best = d2;
+        bi = v;
+      }
+    }
+    const bool matched = w > 0.0f && isfinite(px) && isfinite(py) && isfinite(pz) && best <= a.max_dist2;
+    s.idx[n] = matched ? bi : -1;
+    // sqrtf, not __fsqrt_rn: this toolchain's __fsqrt_rn is the native (approximate) root unless OCML_BASIC_ROUNDED_OPERATIONS is defined, sqrtf is the
+    // correctly rounded one -- the one numpy computes
+    s.dist[n] = matched ? sqrtf(best) : 0.0f;
+    a.idx[(long)b * N + n] = matched ? bi : -1;
+  }
+  __syncthreads();
+  {  // this thread's vertices t, t + 256, t + 512, (t + 768): one pass over the points in ascending order serves all of them
+    float W[4] = {0.f, 0.f, 0.f, 0.f}, S[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+    for (int n = 0; n < N; ++n) {
+      const int i = s.idx[n];
+      if (i < 0 || (i & 255) != t) continue;
+      const float w = PW ? PW[n] : 1.0f;
+      const float px = P[n * 3 + 0], py = P[n * 3 + 1], pz = P[n * 3 + 2];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if ((i >> 8) == k) {
+          W[k] = __fadd_rn(W[k], w);
+          S[k][0] = __fadd_rn(S[k][0], __fmul_rn(w, px));
+          S[k][1] = __fadd_rn(S[k][1], __fmul_rn(w, py));
+          S[k][2] = __fadd_rn(S[k][2], __fmul_rn(w, pz));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int v = t + k * 256;
+      if (v >= NV) continue;
+      const bool any = W[k] > 0.0f;
+      a.vweight[(long)b * NV + v] = any ? W[k] : 0.0f;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) a.vtarget[((long)b * NV + v) * 3 + d] = any ? __fdiv_rn(S[k][d], W[k]) : 0.0f;
+    }
+  }
+  if (t == 255) {  // the matched points' count and mean distance, summed in ascending point order
+    float sum = 0.f;
+    int cnt = 0;
+    for (int n = 0; n < N; ++n)
+      if (s.idx[n] >= 0) {
+        sum = __fadd_rn(sum, s.dist[n]);
+        ++cnt;
+      }
+    a.stats[(long)b * 2 + 0] = (float)cnt;
+    a.stats[(long)b * 2 + 1] = cnt > 0 ? __fdiv_rn(sum, (float)cnt) : 0.0f;
+  }
 }
 
 }  // namespace
@@ -730,29 +987,71 @@ extern "C" int kpf_mano_backward_f32(const float* pose6d, int ld6, const float* 
   return kpf_check_launch("kpf_mano_backward_f32");
 }
 
+// The two fit entries: `name` prefixes every refusal; vert_target / vert_weight select the instantiation with the vertex term
+static int mano_fit_launch(const char* name, const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+                           const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor, const float* skin_weights,
+                           const float* hands_mean, const kpf_mano_fit_cfg* cfg, float lambda_verts, float* pose_aa, float* betas, float* trans, float* verts,
+                           float* joints, float* rotmat, float* residual, int res_ld, int* status, int B, void* stream) {
+  KPF_REQUIRE(shapedirs_t && posedirs_t && v_template && j_regressor && skin_weights && hands_mean && cfg && pose_aa && betas && trans && joints &&
+                  residual && status,
+              "%s: null pointer", name);
+  KPF_REQUIRE(B > 0, "%s: bad shape B=%d", name, B);
+  KPF_REQUIRE(cfg->iters >= 0 && cfg->iters <= 1000, "%s: iters=%d outside [0, 1000]", name, cfg->iters);
+  KPF_REQUIRE(cfg->beta1 >= 0.f && cfg->beta1 < 1.f && cfg->beta2 >= 0.f && cfg->beta2 < 1.f && cfg->eps >= 0.f,
+              "%s: bad Adam constants beta1=%g beta2=%g eps=%g", name, cfg->beta1, cfg->beta2, cfg->eps);
+  unsigned seen = 0;
+  for (int i = 0; i < 21; ++i) {
+    KPF_REQUIRE(cfg->joint_map[i] >= 0 && cfg->joint_map[i] < 21, "%s: joint_map[%d]=%d outside [0, 21)", name, i, cfg->joint_map[i]);
+    seen |= 1u << cfg->joint_map[i];
+  }
+  KPF_REQUIRE(seen == (1u << 21) - 1, "%s: joint_map is not a permutation", name);
+  ManoFitArgs a;
+  a.target = target; a.weight = weight; a.vtarget = vert_target; a.vweight = vert_weight;
+  a.m = ManoModel{shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights, hands_mean};
+  a.c = *cfg;
+  a.lambda_verts = lambda_verts; a.res_ld = res_ld;
+  a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
+  a.status = status;
+  if (vert_target && vert_weight) hipLaunchKernelGGL(mano_fit_kernel<true>, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(mano_fit_kernel<false>, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch(name);
+}
+
 extern "C" int kpf_mano_fit_f32(const float* target, const float* weight, const float* shapedirs_t, const float* posedirs_t, const float* v_template,
                                 const float* j_regressor, const float* skin_weights, const float* hands_mean, const kpf_mano_fit_cfg* cfg,
                                 float* pose_aa, float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status,
                                 int B, void* stream) {
-  KPF_REQUIRE(target && shapedirs_t && posedirs_t && v_template && j_regressor && skin_weights && hands_mean && cfg && pose_aa && betas && trans &&
-                  joints && residual && status,
-              "kpf_mano_fit_f32: null pointer");
-  KPF_REQUIRE(B > 0, "kpf_mano_fit_f32: bad shape B=%d", B);
-  KPF_REQUIRE(cfg->iters >= 0 && cfg->iters <= 1000, "kpf_mano_fit_f32: iters=%d outside [0, 1000]", cfg->iters);
-  KPF_REQUIRE(cfg->beta1 >= 0.f && cfg->beta1 < 1.f && cfg->beta2 >= 0.f && cfg->beta2 < 1.f && cfg->eps >= 0.f,
-              "kpf_mano_fit_f32: bad Adam constants beta1=%g beta2=%g eps=%g", cfg->beta1, cfg->beta2, cfg->eps);
-  unsigned seen = 0;
-  for (int i = 0; i < 21; ++i) {
-    KPF_REQUIRE(cfg->joint_map[i] >= 0 && cfg->joint_map[i] < 21, "kpf_mano_fit_f32: joint_map[%d]=%d outside [0, 21)", i, cfg->joint_map[i]);
-    seen |= 1u << cfg->joint_map[i];
-  }
-  KPF_REQUIRE(seen == (1u << 21) - 1, "kpf_mano_fit_f32: joint_map is not a permutation");
-  ManoFitArgs a;
-  a.target = target; a.weight = weight;
-  a.m = ManoModel{shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights, hands_mean};
-  a.c = *cfg;
-  a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
-  a.status = status;
-  hipLaunchKernelGGL(mano_fit_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  return kpf_check_launch("kpf_mano_fit_f32");
+  KPF_REQUIRE(target, "kpf_mano_fit_f32: null pointer");
+  return mano_fit_launch("kpf_mano_fit_f32", target, weight, nullptr, nullptr, shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights, hands_mean, cfg,
+                         0.0f, pose_aa, betas, trans, verts, joints, rotmat, residual, 2, status, B, stream);
+}
+
+extern "C" int kpf_mano_fit_mesh_f32(const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+                                     const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+                                     const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_cfg* cfg, float* pose_aa, float* betas,
+                                     float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status, int B, void* stream) {
+  KPF_REQUIRE(cfg, "kpf_mano_fit_mesh_f32: null pointer");
+  KPF_REQUIRE((vert_target == nullptr) == (vert_weight == nullptr), "kpf_mano_fit_mesh_f32: vert_target and vert_weight go together");
+  KPF_REQUIRE(cfg->lambda_verts >= 0.f, "kpf_mano_fit_mesh_f32: lambda_verts=%g is negative", cfg->lambda_verts);
+  kpf_mano_fit_cfg c;
+  c.iters = cfg->iters;
+  c.lr_pose = cfg->lr_pose; c.lr_shape = cfg->lr_shape; c.lr_trans = cfg->lr_trans;
+  c.beta1 = cfg->beta1; c.beta2 = cfg->beta2; c.eps = cfg->eps;
+  c.lambda_shape = cfg->lambda_shape; c.lambda_pose = cfg->lambda_pose;
+  c.init_trans = cfg->init_trans;
+  for (int i = 0; i < 21; ++i) c.joint_map[i] = cfg->joint_map[i];
+  return mano_fit_launch("kpf_mano_fit_mesh_f32", target, weight, vert_target, vert_weight, shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights,
+                         hands_mean, &c, cfg->lambda_verts, pose_aa, betas, trans, verts, joints, rotmat, residual, 4, status, B, stream);
+}
+
+extern "C" int kpf_mano_assoc_f32(const float* points, const float* point_weight, const float* verts, float max_dist2, int* idx, float* vert_target,
+                                  float* vert_weight, float* stats, int B, int N, void* stream) {
+  KPF_REQUIRE(points && verts && idx && vert_target && vert_weight && stats, "kpf_mano_assoc_f32: null pointer");
+  KPF_REQUIRE(B > 0 && N >= 1 && N <= ASSOC_MAXN, "kpf_mano_assoc_f32: bad shape B=%d N=%d (1 <= N <= %d)", B, N, ASSOC_MAXN);
+  KPF_REQUIRE(!(max_dist2 < 0.f) && max_dist2 == max_dist2, "kpf_mano_assoc_f32: max_dist2=%g", max_dist2);
+  ManoAssocArgs a;
+  a.points = points; a.pweight = point_weight; a.verts = verts; a.max_dist2 = max_dist2; a.N = N;
+  a.idx = idx; a.vtarget = vert_target; a.vweight = vert_weight; a.stats = stats;
+  hipLaunchKernelGGL(mano_assoc_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch("kpf_mano_assoc_f32");
 }

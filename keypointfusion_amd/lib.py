@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 26  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 27  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -59,6 +59,10 @@ class WgradReduceDesc(C.Structure):  # kpf_wgrad_reduce_desc (include/kpf.h)
 class ManoFitCfg(C.Structure):  # kpf_mano_fit_cfg (include/kpf.h)
     _fields_ = [("iters", C.c_int)] + [(n, C.c_float) for n in "lr_pose lr_shape lr_trans beta1 beta2 eps lambda_shape lambda_pose".split()] + [
         ("init_trans", C.c_int), ("joint_map", C.c_int * 21)]
+
+
+class ManoFitMeshCfg(C.Structure):  # kpf_mano_fit_mesh_cfg (include/kpf.h): kpf_mano_fit_cfg's fields, then lambda_verts
+    _fields_ = ManoFitCfg._fields_ + [("lambda_verts", C.c_float)]
 
 
 class WgradPlan(C.Structure):  # kpf_wgrad_plan (include/kpf.h)
@@ -131,6 +135,8 @@ _SIGS = {
     "kpf_mano_forward_f32": [_P, C.c_int, _P, C.c_int] + [_P] * 10 + [C.c_int, _P],
     "kpf_mano_backward_f32": [_P, C.c_int, _P, C.c_int] + [_P] * 10 + [_P, C.c_int, _P, C.c_int, C.c_int, _P],
     "kpf_mano_fit_f32": [_P] * 8 + [C.POINTER(ManoFitCfg)] + [_P] * 8 + [C.c_int, _P],
+    "kpf_mano_fit_mesh_f32": [_P] * 10 + [C.POINTER(ManoFitMeshCfg)] + [_P] * 8 + [C.c_int, _P],
+    "kpf_mano_assoc_f32": [_P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, _P],
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],
     "kpf_xattn_weight_floats": [],

@@ -8,7 +8,12 @@ torch.optim.Adam's update (no weight decay, no amsgrad, moments zero at the star
 Why eps defaults to 1.0 and not torch's 1e-8: with 1e-8 Adam's first steps are lr * sign(g), so a component whose gradient is rounding noise — the
 translation right after init_trans, whose gradient is analytically zero — moves by a full step in a direction the noise picks.  On the CPU restatement of
 this fit (tests/mano_cases.py) fp32 and float64 then part by 1 mm in the joints and 4 mm in the vertices after 10 steps; with eps = 1.0 (gradients are in
-mm, so 1.0 is small against any gradient that matters) they agree to 1e-4 mm, and convergence is the same: 8.5 -> 1.5 mm in 50 steps against 8.5 -> 1.4 mm."""
+mm, so 1.0 is small against any gradient that matters) they agree to 1e-4 mm, and convergence is the same: 8.5 -> 1.5 mm in 50 steps against 8.5 -> 1.4 mm.
+
+Joints put the mesh where 21 points on the skeleton can: the shape is barely observable and nothing ties the skin to the sensor.  fit_mesh adds a vertex term
+(kpf_mano_fit_mesh_f32: 778 weighted vertex targets, a ground-truth mesh or the output of associate), associate gives every depth point its nearest vertex and
+every vertex the weighted centroid of its points (kpf_mano_assoc_f32; sum_n w_n |V - p_n|^2 and W |V - c|^2 have the same gradient, so the fit needs no
+atomics), and fit_cloud alternates the two on the depth points the preprocessing already sampled (cloud_mm).  DESIGN.md 4.12."""
 import torch
 
 from . import lib as L
@@ -34,7 +39,8 @@ class ManoFitter:
             raise ValueError("joint_map must be a permutation of 0..20")
         self.cfg = L.ManoFitCfg(int(iters), float(lr[0]), float(lr[1]), float(lr[2]), float(betas[0]), float(betas[1]), float(eps), float(lambda_shape),
                                 float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
-        self._bufs = {}
+        self.mesh_cfg = L.ManoFitMeshCfg(*[getattr(self.cfg, n) for n, _ in L.ManoFitCfg._fields_], 1.0)
+        self._bufs, self._mesh_bufs, self._assoc_bufs = {}, {}, {}
 
     def new_state(self, B):
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
@@ -80,3 +86,118 @@ class ManoFitter:
                                               torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_f32")
         return {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
                 "residual": o["residual"], "status": o["status"]}
+
+    def _check_state(self, state, B):
+        for s, n in zip(state, (48, 10, 3)):
+            if not (s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and tuple(s.shape) == (B, n)):
+                raise ValueError("state must be contiguous float32 tensors [B, 48], [B, 10], [B, 3] on the device")
+
+    @staticmethod
+    def _check(t, shape, name):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+            raise ValueError("%s must be a contiguous float32 %s tensor on the device" % (name, list(shape)))
+
+    def fit_mesh(self, joints_mm=None, weight=None, vert_target=None, vert_weight=None, state=None, init_trans=True, lambda_verts=1.0, iters=None):
+        """fit with a vertex term: + lambda_verts (1 / sum u) sum_v u_v |V_v + t - c_v|^2, vert_target c [B, 778, 3] in mm and vert_weight u [B, 778] >= 0
+        (both or neither; neither is exactly fit).  joints_mm=None, or a weight of all zeros, is a vertex-only fit; then init_trans takes the translation
+        from the vertices.  iters=None: the fitter's.  Returns what fit returns, with residual [B, 4]: the mean weighted joint distance before and after, then
+        the mean weighted vertex distance before and after (0 for a term without weight); status bit 1 needs BOTH weight sums to be 0, bit 2 a non-finite
+        joint or vertex target under a positive weight.  Own output tensors per batch size, apart from fit's; one launch, no host wait."""
+        if (vert_target is None) != (vert_weight is None):
+            raise ValueError("vert_target and vert_weight go together")
+        given = [t for t in (joints_mm, vert_target, state[0] if state is not None else None) if t is not None]
+        if not given:
+            raise ValueError("fit_mesh needs joints_mm, vert_target or a state to take the batch size from")
+        B = given[0].shape[0]
+        if joints_mm is not None:
+            self._check(joints_mm, (B, 21, 3), "joints_mm")
+        if weight is not None:
+            self._check(weight, (B, 21), "weight")
+        if vert_target is not None:
+            self._check(vert_target, (B, 778, 3), "vert_target")
+            self._check(vert_weight, (B, 778), "vert_weight")
+        if B not in self._mesh_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            self._mesh_bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 4),
+                                  "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B)}
+        o = self._mesh_bufs[B]
+        if state is None:
+            state = o["state"]
+            for s in state:
+                s.zero_()
+        pose, betas, trans = state
+        self._check_state(state, B)
+        c = self.mesh_cfg
+        c.iters = self.cfg.iters if iters is None else int(iters)
+        c.init_trans = 1 if init_trans else 0
+        c.lambda_verts = float(lambda_verts)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_fit_mesh_f32(ptr(joints_mm), ptr(weight), ptr(vert_target), ptr(vert_weight), *[m.data_ptr() for m in self.model],
+                                                   L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
+                                                   o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(), B,
+                                                   torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_mesh_f32")
+        return {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
+                "residual": o["residual"], "status": o["status"]}
+
+    def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0):
+        """points_mm [B, N, 3] (camera-space mm, 1 <= N <= 4096), verts3d [B, 778, 3] (a fit's), point_weight [B, N] >= 0 or None (= ones), max_dist: the gate
+        in mm (float("inf"): none) -> idx [B, N] int32 (each point's nearest vertex, -1 if its weight is 0, a coordinate is not finite or the vertex is
+        farther than max_dist), vert_target [B, 778, 3] and vert_weight [B, 778] (per vertex the weighted centroid and the summed weight of its points; 0
+        and 0 without any), stats [B, 2] (matched points, their mean distance in mm).  The fitter's own tensors per (B, N); one launch, no host wait."""
+        B, N = int(points_mm.shape[0]), int(points_mm.shape[1]) if points_mm.dim() == 3 else -1
+        self._check(points_mm, (B, N, 3), "points_mm")
+        self._check(verts3d, (B, 778, 3), "verts3d")
+        if point_weight is not None:
+            self._check(point_weight, (B, N), "point_weight")
+        if not 1 <= N <= 4096:
+            raise ValueError("associate takes 1 <= N <= 4096 points per hand, not %d" % N)
+        key = (B, N, _slot)
+        if key not in self._assoc_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            self._assoc_bufs[key] = {"idx": torch.empty(B, N, device=self.device, dtype=torch.int32), "vert_target": e(B, 778, 3), "vert_weight": e(B, 778),
+                                     "stats": e(B, 2)}
+        o = self._assoc_bufs[key]
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_assoc_f32(points_mm.data_ptr(), None if point_weight is None else point_weight.data_ptr(), verts3d.data_ptr(),
+                                                float(max_dist) * float(max_dist), o["idx"].data_ptr(), o["vert_target"].data_ptr(),
+                                                o["vert_weight"].data_ptr(), o["stats"].data_ptr(), B, N, torch.cuda.current_stream().cuda_stream),
+                    "kpf_mano_assoc_f32")
+        return dict(o)
+
+    def fit_cloud(self, joints_mm, points_mm, weight=None, point_weight=None, state=None, init_trans=True, rounds=3, iters_cloud=None, max_dist=20.0,
+                  lambda_verts=1.0):
+        """Joints, then the depth points: one fit on the joints, then `rounds` times associate followed by fit_mesh (warm start, init_trans=False, the joints
+        kept in the objective, iters_cloud iterations each; None = the fitter's), and last one associate on the final vertices: 2 * rounds + 2 launches and no
+        host wait.  Returns the last fit's outputs plus cloud_before and cloud_after (the stats of the first and the last association: matched points and
+        their mean distance to the mesh in mm) and the last association's idx, vert_target and vert_weight.  rounds=0 is fit plus one associate."""
+        out = self.fit(joints_mm, weight, state=state, init_trans=init_trans)
+        state = (out["mano_pose_aa"], out["mano_shape"], out["trans"])
+        first = None
+        for r in range(int(rounds)):
+            a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0)
+            first = a if first is None else first
+            out = self.fit_mesh(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
+                                iters=iters_cloud)
+        last = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=2)
+        out = dict(out)
+        out.update(cloud_before=(last if first is None else first)["stats"], cloud_after=last["stats"], idx=last["idx"], vert_target=last["vert_target"],
+                   vert_weight=last["vert_weight"])
+        return out
+
+
+def cloud_mm(prep):
+    """The depth points the preprocessing sampled for the model, back in camera-space mm: (points [B, n, 3], point_weight [B, n]) as device tensors, the
+    inputs of ManoFitter.associate / fit_cloud.  points = prep["pcl"] * prep["cube"][:, None] / 2 + prep["center"][:, None]; the weight is 1, and 0 for every
+    point of a hand whose prep["pcl_count"] is 0 (its cloud is all zeros, which would sit at the crop's centre).
+
+    The frame: preprocess.depth_to_pcl back-projects a crop pixel as x = (u - u0) / fx * d, y = +(v - v0) / fy * d (flip = 1), z = d and normalises it by
+    (xyz - center) / (cube / 2), center being image_to_3d of the centre of mass with the same sign; kpf_prep_pcl_sample restates exactly that.  The tracker's
+    cam_mm (kpf_track.hip) is joints * cube / 2 + center of the model's cube-normalised joints, which the same kernel projects with u = x fx / z + u0,
+    v = y fy / z + v0.  So both are the one camera frame, y growing with the image row, no sign change between them, and this cloud can be compared with
+    cam_mm and with a fit to it as it stands.  Two things to know: the sampler clips a point to the cube ([-1, 1] per axis), so a point outside it lies on
+    a face of the cube and not on the surface -- the gate of associate (max_dist) is what keeps such points from pulling the mesh; and a cloud smaller than n
+    repeats its points."""
+    pts = prep["pcl"] * prep["cube"][:, None] / 2 + prep["center"][:, None]
+    w = (prep["pcl_count"] > 0).to(pts.dtype)[:, None].expand(pts.shape[0], pts.shape[1]).contiguous()
+    return pts.contiguous(), w

@@ -158,12 +158,14 @@ class TrackedStream:
                                                     cam_mm.data_ptr(), self.bbox_used.data_ptr(), self.status.data_ptr(),
                                                     torch.cuda.current_stream(self.dev).cuda_stream), "kpf_track_step_f32")
         return dict(frame_px=frame_px, crop_px=crop_px, cam_mm=cam_mm, bbox_used=self.bbox_used, bbox=self.bbox, status=self.status, lost=self.lost,
-                    com=prep["com"], bounds=prep["bounds"], pcl_count=prep["pcl_count"], joints=joints)
+                    com=prep["com"], bounds=prep["bounds"], pcl_count=prep["pcl_count"], joints=joints,
+                    pcl=prep["pcl"], cube=prep["cube"], center=prep["center"])  # what mano_fit.cloud_mm needs: the sampled depth points and their frame
 
     def step(self, rgb, depth):
         """rgb [F][H][W][3] uint8, depth [F][H][W] uint16 (mm) device tensors -> dict of STATIC device tensors, valid in stream order until the next step
         overwrites them: frame_px, crop_px [B][J][3] (u, v px, d mm), cam_mm [B][J][3], bbox_used [B][4] (this frame's box), bbox (the next frame's),
-        status, lost [B] int32, and the prepare record com [B][3] float64, bounds [B][6], pcl_count [B] (+ joints, the forward's normalised output)."""
+        status, lost [B] int32, and the prepare record com [B][3] float64, bounds [B][6], pcl_count [B] (+ joints, the forward's normalised output, and pcl
+        [B][n][3], cube, center [B][3]: the sampled depth points normalised to the cube, mano_fit.cloud_mm(out) puts them back in camera space)."""
         for name, t, want in (("rgb", rgb, self._rgb), ("depth", depth, self._depth)):
             if not isinstance(t, torch.Tensor) or t.dtype != want.dtype or tuple(t.shape) != tuple(want.shape):
                 raise ValueError("TrackedStream.step: %s must be %s %s (got %s)" % (name, want.dtype, tuple(want.shape),

@@ -1,6 +1,7 @@
 """Timing of the MANO layer in HIP: the MANO head's train step (forward + backward to the features and the MLP's parameters) at B = 32 with the
 hand model as torch ops under autograd (layer="torch") against heads_train.ManoLayerHip (layer="hip"), and the joint fit mano_fit.ManoFitter at B = 1 and 32
-with iters = 10 and 50.  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
+with iters = 10 and 50; and the fit with a vertex term, the association of 1024 points and the chain fit_cloud (3 rounds) at B = 1 and 32
+with iters = 50.  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
     python tools/mano_bench.py --reps 50
@@ -64,6 +65,20 @@ def main():
             rec["fit_ms_B%d_iters%d" % (B, iters)] = _timed(lambda: fitter.fit(y), args.reps, torch)
             out = fitter.fit(y)
             rec["fit_residual_mm_B%d_iters%d" % (B, iters)] = [float(v) for v in out["residual"].mean(0)]
+    # the mesh fit: the vertex targets are the hand's own vertices; the cloud is 1024 of them with 0.5 mm of noise
+    verts = (pose["verts3d"] + torch.tensor([30.0, -20.0, 600.0], device=dev)).contiguous()
+    pick = torch.randint(0, 778, (1024,), generator=gen).to(dev)
+    points = (verts[:, pick] + 0.5 * torch.randn(32, 1024, 3, generator=gen).to(dev)).contiguous()
+    ones = torch.ones(32, 778, device=dev)
+    for B in (1, 32):
+        fitter = ManoFitter(m, dev, iters=50)
+        y, vt, u, pts = target[:B].contiguous(), verts[:B].contiguous(), ones[:B].contiguous(), points[:B].contiguous()
+        rec["fit_mesh_ms_B%d_iters50" % B] = _timed(lambda: fitter.fit_mesh(y, None, vt, u), args.reps, torch)
+        rec["fit_mesh_residual_mm_B%d_iters50" % B] = [float(v) for v in fitter.fit_mesh(y, None, vt, u)["residual"].mean(0)]
+        rec["associate_ms_B%d_N1024" % B] = _timed(lambda: fitter.associate(pts, vt), args.reps, torch)
+        rec["fit_cloud_ms_B%d_iters50_rounds3" % B] = _timed(lambda: fitter.fit_cloud(y, pts), args.reps, torch)
+        out = fitter.fit_cloud(y, pts)
+        rec["fit_cloud_mm_B%d_iters50_rounds3" % B] = [float(out["cloud_before"][:, 1].mean()), float(out["cloud_after"][:, 1].mean())]
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:
