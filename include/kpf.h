@@ -358,6 +358,30 @@ int kpf_mano_fit_mesh_f32(const float* target /*[B][21][3] mm, or NULL*/, const 
     float* verts /*[B][778][3] or NULL*/, float* joints /*[B][21][3], target order*/, float* rotmat /*[B][16][9] or NULL*/,
     float* residual /*[B][4]*/, int* status /*[B]*/, int B, void* stream);
 
+/* The joint fit by damped Gauss-Newton (ABI 28): kpf_mano_fit_f32's objective, state, targets, weights, joint_map, outputs and status convention, one
+ * workgroup per sample, every iteration inside the one launch, no atomics, fixed-order sums.  With p = (pose 0..47, betas 48..57, trans 58..60):
+ *   r_i = sqrt(w_i / sw) (J_map[i](theta, beta) + t - y_i)   63 rows, mm; a row under weight 0 is selected out
+ *   J = d r / d p (63 x 61),  Lambda = diag(0 x3, lambda_pose x45, lambda_shape x10, 0 x3)
+ *   A = J^T J + Lambda + mu diag(J^T J) + nu I,  g = J^T r + Lambda p,  A delta = g by Cholesky,  p <- p - delta
+ * with a fixed damping and no accept/reject step.  init_trans != 0 (and iters > 0) first sets t to the weighted mean offset, summed in double and rounded
+ * once.  history [B][iters + 1] or NULL: the mean weighted joint distance before iteration 1 and after each iteration (first and last entry are
+ * residual's).  jacobian [B][63][61] or NULL: the unweighted d (J_map[i] + t) / d p of the state on entry, in mm, rows in target order.
+ * status bits 1 and 2 as kpf_mano_fit_f32; bit 4: a pivot of the factorisation was not > 0 or not finite -- the iteration stops, the state holds the
+ * last completed iteration (after init_trans), the outputs evaluate it and the remaining history entries repeat its distance. */
+typedef struct kpf_mano_fit_gn_cfg {
+  int iters;                       /* 0 <= iters <= 64; 0 only evaluates */
+  float mu, nu;                    /* Marquardt's relative damping and the absolute floor on the diagonal, both >= 0 */
+  float lambda_shape, lambda_pose; int init_trans;
+  int joint_map[21];               /* as kpf_mano_fit_cfg */
+} kpf_mano_fit_gn_cfg;             /* HOST struct */
+int kpf_mano_fit_gn_f32(const float* target /*[B][21][3] mm*/, const float* weight /*[B][21] >= 0, or NULL = ones*/,
+    const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+    const float* skin_weights, const float* hands_mean, const kpf_mano_fit_gn_cfg* cfg,
+    float* pose_aa /*[B][48] in/out*/, float* betas /*[B][10] in/out*/, float* trans /*[B][3] mm in/out*/,
+    float* verts /*[B][778][3] or NULL*/, float* joints /*[B][21][3], target order*/, float* rotmat /*[B][16][9] or NULL*/,
+    float* residual /*[B][2]*/, int* status /*[B]*/, float* history /*[B][iters + 1] or NULL*/, float* jacobian /*[B][63][61] or NULL*/,
+    int B, void* stream);
+
 /* Depth points -> per-vertex targets (ABI 27), one workgroup per hand.  points [B][N][3] in camera-space mm (the frame of the tracker's cam_mm),
  * 1 <= N <= 4096 (any other N is refused and nothing is written); point_weight [B][N] or NULL = ones; verts [B][778][3] (a fit's verts);
  * max_dist2: squared gate in mm^2.  idx [B][N]: the nearest vertex or -1; vert_target / vert_weight: per vertex the weighted centroid and the summed
@@ -1010,7 +1034,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 27
+#define KPF_ABI_VERSION 28
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -3,6 +3,7 @@
 //   kpf_mano_backward_f32  its derivative: recomputes the forward in LDS, then walks the stages backwards (heads_train.ManoLayerHip)
 //   kpf_mano_fit_f32       Adam on pose / shape / translation against 21 target joints, every iteration inside the one launch (mano_fit.ManoFitter)
 //   kpf_mano_fit_mesh_f32  the same fit with a vertex term (778 weighted vertex targets): the second instantiation of the fit kernel
+//   kpf_mano_fit_gn_f32    the joint fit by damped Gauss-Newton: forward-mode Jacobian, normal matrix and Cholesky solve in LDS (its own kernel, further down)
 //   kpf_mano_assoc_f32     depth points -> nearest vertex, per-vertex centroid and weight: the vertex targets of the fit above (its own kernel, further down)
 // The fits share the stage functions below; the forward's arithmetic is the text it had in kpf_aux.hip (tests/test_heads_gpu.py pins its bits).
 // Every reduction has a fixed order (wave butterflies, then a fixed sum over the four waves) and there are no atomics: a replay is bit-identical and a
@@ -864,6 +865,398 @@ __global__ __launch_bounds__(256) void mano_fit_kernel(ManoFitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Gauss-Newton fit: the joint fit's objective, state, targets and outputs, minimised by damped Gauss-Newton steps.  Per iteration:
+//   r_i = sqrt(w_i / sw) (J_map[i] + t - y_i), 63 rows in mm;  J = d r / d p, 63 x 61, forward-mode, one column per lane;
+//   A = J^T J + Lambda + mu diag(J^T J) + nu I,  g = J^T r + Lambda p,  A delta = g by Cholesky in LDS,  p <- p - delta.
+// Stages of an iteration: mano_fit_eval (the Adam fit's, shared), mano_gn_tangent (J and r), the normal matrix (1891 lower entries and g, each a sum over
+// the 63 rows in ascending order, held in registers by the thread that formed it), the factorisation (square-root-free Cholesky, one barrier per column,
+// the forward substitution rides along as row 61), the back substitution (wave 0, shuffles).  No atomics; every sum has a fixed order.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int GN_P = 61, GN_R = 63, GN_SLOTS = 8;  // 61 * 62 / 2 + 61 = 1952 entries of the system over 256 threads
+
+struct ManoGnArgs {
+  const float *target, *weight;
+  ManoModel m;
+  kpf_mano_fit_gn_cfg c;
+  float *pose, *betas, *trans, *verts, *joints, *rotmat, *residual;
+  int* status;
+  float *history, *jacobian;  // [B][iters + 1], [B][63][61]; each may be null
+};
+
+struct ManoGnLds {
+  float J[GN_R][GN_P];       // d r / d p: rows in the MODEL's joint order (row h * 3 + d), already scaled by sqrt(w_h / sw); a row under weight 0 is 0
+  float A[GN_P + 1][GN_P];   // lower triangle: column k as elimination step k finds it (A[k][k] the pivot d_k), L = A D^-1/2; row 61: g, eliminated alike
+  float R[GN_R];             // r
+  float SQ[21];              // sqrt(w_h / sw), model order
+  int inv[21];               // model joint h is target row inv[h]
+  float dJrS[10][NJ][3];     // j_regressor . shapedirs[k]: d Jr / d beta_k, a constant of the hand model (computed once per launch)
+  float tipT[5][12];         // the five tips' blended transforms sum_j w[tip][j] G2[j] at the current state
+  float tipW[5][NJ];         // their skinning weights
+  int fail;
+};
+
+__device__ __forceinline__ float gn_lambda(const kpf_mano_fit_gn_cfg& c, int j) {  // Lambda's diagonal
+  return (j >= 3 && j < 48) ? c.lambda_pose : ((j >= 48 && j < 58) ? c.lambda_shape : 0.0f);
+}
+
+// d rodrigues(aa) / d aa[k]: the tangent of the formula above operation by operation, its +1e-8 included (at aa == 0 the axis n = aa / |aa + 1e-8| is 0
+// and its tangent 1 / |aa + 1e-8|: the product with sin(h) is the finite 1/2 the limit has)
+__device__ __forceinline__ void rodrigues_tangent(const float* aa, int k, float* dR) {
+  const float ap[3] = {aa[0] + 1e-8f, aa[1] + 1e-8f, aa[2] + 1e-8f};
+  const float ang = sqrtf(ap[0] * ap[0] + ap[1] * ap[1] + ap[2] * ap[2]);
+  const float dang = (k == 0 ? ap[0] : (k == 1 ? ap[1] : ap[2])) / ang;
+  const float h = ang * 0.5f, sn = sinf(h), cs = cosf(h), dh = 0.5f * dang;
+  float q[4], dq[4];
+  q[0] = cs;
+  dq[0] = -sn * dh;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float n = aa[i] / ang;
+    const float dn = (i == k ? 1.0f : 0.0f) / ang - aa[i] * dang / (ang * ang);
+    q[i + 1] = sn * n;
+    dq[i + 1] = cs * dh * n + sn * dn;
+  }
+  const float nq = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const float dnq = (q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3]) / nq;
+  const float w = q[0] / nq, x = q[1] / nq, y = q[2] / nq, z = q[3] / nq;
+  const float dw = (dq[0] - w * dnq) / nq, dx = (dq[1] - x * dnq) / nq, dy = (dq[2] - y * dnq) / nq, dz = (dq[3] - z * dnq) / nq;
+  dR[0] = 2.0f * (w * dw + x * dx - y * dy - z * dz);
+  dR[1] = 2.0f * (x * dy + y * dx - w * dz - z * dw);
+  dR[2] = 2.0f * (w * dy + y * dw + x * dz + z * dx);
+  dR[3] = 2.0f * (w * dz + z * dw + x * dy + y * dx);
+  dR[4] = 2.0f * (w * dw - x * dx + y * dy - z * dz);
+  dR[5] = 2.0f * (y * dz + z * dy - w * dx - x * dw);
+  dR[6] = 2.0f * (x * dz + z * dx - w * dy - y * dw);
+  dR[7] = 2.0f * (w * dx + x * dw + y * dz + z * dy);
+  dR[8] = 2.0f * (w * dw - x * dx - y * dy + z * dz);
+}
+
+// What column `col` is: a pose column turns joint `a` about axis component `k`, a shape column moves beta_k, a translation column moves t_k
+struct ManoGnColumn {
+  int a;        // the joint whose rotation moves, or -1
+  int shape;    // the beta that moves, or -1
+  float dR[9];  // d Rj[a]
+};
+
+// The tangent of posed vertex v (metres) along one column, given dT = sum_j w[v][j] d G2[j] (accumulated by the caller while it walks the chain) and
+// T = sum_j w[v][j] G2[j]:  d o = dT [p; 1] + T[:, :3] d p,  p = v_posed[v], d p = posedirs rows of the joint that turns . dR  |  shapedirs[k][v]  |  0.
+// A stage function of the vertex index: the five tips use it today, a vertex term would call it for any v.
+__device__ __forceinline__ void mano_gn_vertex_tangent(const ManoModel& m, const ManoLds& s, int v, const ManoGnColumn& col, const float* dT, const float* T,
+                                                       float* o) {
+  float dp[3] = {0.f, 0.f, 0.f};
+  if (col.a > 0) {  // pmap = Rj[1:] - I: the nine entries of joint a
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const float* row = m.poseT + (long)((col.a - 1) * 9 + i) * NC + v * 3;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) dp[d] = fmaf(row[d], col.dR[i], dp[d]);
+    }
+  } else if (col.shape >= 0) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) dp[d] = m.shapeT[(long)col.shape * NC + v * 3 + d];
+  }
+  const float px = s.v[v * 3 + 0], py = s.v[v * 3 + 1], pz = s.v[v * 3 + 2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    o[r] = (dT[r * 4 + 0] * px + dT[r * 4 + 1] * py + dT[r * 4 + 2] * pz + dT[r * 4 + 3]) +
+           (T[r * 4 + 0] * dp[0] + T[r * 4 + 1] * dp[1] + T[r * 4 + 2] * dp[2]);
+}
+
+// J and r of the state in s / f (after mano_fit_eval).  Lanes 0..60 of wave 0 each build one column forward-mode: the tangent transform is carried down
+// the chain (a joint's parent is the root or the joint before it, so the root's and the previous joint's tangents in registers are enough) and the five
+// tips' blended tangent transforms are accumulated on the way.  gout: null, or [63][61] for the unweighted columns in target-row order.
+// All 256 threads; ends with a barrier.
+__device__ __forceinline__ void mano_gn_tangent(const ManoModel& m, const ManoLds& s, const ManoFitLds& f, ManoGnLds& n, int t, float* gout) {
+  if (t >= 64 && t < 64 + 60) {  // the tips' blended transforms of this state, j ascending as mano_skin_transform
+    const int k = (t - 64) / 12, i = (t - 64) % 12;
+    float sum = 0.f;
+    for (int j = 0; j < NJ; ++j) sum = fmaf(n.tipW[k][j], s.G2[j][i], sum);
+    n.tipT[k][i] = sum;
+  }
+  if (t >= 128 && t < 128 + GN_R) {
+    const int h = (t - 128) / 3, d = (t - 128) % 3;
+    n.R[t - 128] = f.W[h] > 0.0f ? n.SQ[h] * (f.Jm[h][d] + f.P[58 + d] - f.Y[h][d]) : 0.0f;
+  }
+  __syncthreads();
+  if (t < GN_P) {
+    ManoGnColumn col;
+    col.a = t < 48 ? t / 3 : -1;
+    col.shape = (t >= 48 && t < 58) ? t - 48 : -1;
+    const int td = t >= 58 ? t - 58 : -1;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) col.dR[i] = 0.f;
+    if (col.a >= 0) {
+      float aa[3] = {f.P[col.a * 3 + 0], f.P[col.a * 3 + 1], f.P[col.a * 3 + 2]};
+      if (col.a > 0)
+        for (int i = 0; i < 3; ++i) aa[i] = m.hands_mean[(col.a - 1) * 3 + i] + aa[i];
+      rodrigues_tangent(aa, t - col.a * 3, col.dR);
+    }
+    auto put = [&](int h, int r, float metres) {  // model joint h, coordinate r: the column's entry in mm
+      const float v = metres * 1000.0f + (r == td ? 1.0f : 0.0f);
+      n.J[h * 3 + r][t] = f.W[h] > 0.0f ? n.SQ[h] * v : 0.0f;
+      if (gout) gout[(n.inv[h] * 3 + r) * GN_P + t] = v;
+    };
+    float dG0[12], dGq[12], dG[12], acc[5][12];  // the root's, the previous joint's and this joint's tangent transform; the tips' blended ones
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+      for (int i = 0; i < 12; ++i) acc[k][i] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dG0[i] = dGq[i] = 0.f;
+    for (int j = 0; j < NJ; ++j) {
+      const int p = kManoParent[j];
+      float dJ[3] = {0.f, 0.f, 0.f}, drel[3] = {0.f, 0.f, 0.f};
+      if (col.shape >= 0) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          dJ[r] = n.dJrS[col.shape][j][r];
+          drel[r] = p < 0 ? dJ[r] : dJ[r] - n.dJrS[col.shape][p][r];
+        }
+      }
+      const bool turns = j == col.a;
+      if (p < 0) {  // G[0] = [Rj[0] | Jr[0]]
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) dG[r * 4 + c] = turns ? col.dR[r * 3 + c] : 0.f;
+          dG[r * 4 + 3] = drel[r];
+        }
+      } else {  // G[j] = G[p] loc, loc = [Rj[j] | Jr[j] - Jr[p]]:  d G[j] = d G[p] loc + G[p] d loc
+        float rel[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) rel[r] = s.Jr[j][r] - s.Jr[p][r];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const float e0 = p == 0 ? dG0[r * 4 + 0] : dGq[r * 4 + 0], e1 = p == 0 ? dG0[r * 4 + 1] : dGq[r * 4 + 1];
+          const float e2 = p == 0 ? dG0[r * 4 + 2] : dGq[r * 4 + 2], e3 = p == 0 ? dG0[r * 4 + 3] : dGq[r * 4 + 3];
+          const float g0 = s.G[p][r * 4 + 0], g1 = s.G[p][r * 4 + 1], g2 = s.G[p][r * 4 + 2];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            float sum = e0 * s.Rj[j][0 * 3 + c] + e1 * s.Rj[j][1 * 3 + c] + e2 * s.Rj[j][2 * 3 + c];
+            if (turns) sum += g0 * col.dR[0 * 3 + c] + g1 * col.dR[1 * 3 + c] + g2 * col.dR[2 * 3 + c];
+            dG[r * 4 + c] = sum;
+          }
+          dG[r * 4 + 3] = (e0 * rel[0] + e1 * rel[1] + e2 * rel[2] + e3) + (g0 * drel[0] + g1 * drel[1] + g2 * drel[2]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r) put(j, r, dG[r * 4 + 3]);  // chain joint j is joints3d row j (kManoOut[i] == i for i < 16)
+      // G2[j] = [Rg | tg - Rg Jr[j]]
+      float d2[12];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        d2[r * 4 + 0] = dG[r * 4 + 0];
+        d2[r * 4 + 1] = dG[r * 4 + 1];
+        d2[r * 4 + 2] = dG[r * 4 + 2];
+        d2[r * 4 + 3] = dG[r * 4 + 3] - (dG[r * 4 + 0] * s.Jr[j][0] + dG[r * 4 + 1] * s.Jr[j][1] + dG[r * 4 + 2] * s.Jr[j][2]) -
+                        (s.G[j][r * 4 + 0] * dJ[0] + s.G[j][r * 4 + 1] * dJ[1] + s.G[j][r * 4 + 2] * dJ[2]);
+      }
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const float w = n.tipW[k][j];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) acc[k][i] = fmaf(w, d2[i], acc[k][i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 12; ++i) {
+        if (j == 0) dG0[i] = dG[i];
+        dGq[i] = dG[i];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      float o[3];
+      mano_gn_vertex_tangent(m, s, kManoTip[k], col, acc[k], n.tipT[k], o);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) put(kManoTipRow[k], r, o[r]);
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
+  __shared__ ManoLds s;
+  __shared__ ManoFitLds f;
+  __shared__ ManoGnLds n;
+  const int b = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  // the state, the targets and the status: the Adam fit's text
+  if (t < 48) f.P[t] = a.pose[(long)b * 48 + t];
+  else if (t < 58) f.P[t] = a.betas[(long)b * 10 + (t - 48)];
+  else if (t < 61) f.P[t] = a.trans[(long)b * 3 + (t - 58)];
+  if (t >= 64 && t < 64 + 21) {
+    const int i = t - 64, h = a.c.joint_map[i];
+    const float w = a.weight ? a.weight[(long)b * 21 + i] : 1.0f;
+    f.W[h] = w;
+    n.inv[h] = i;
+    for (int d = 0; d < 3; ++d) f.Y[h][d] = w > 0.0f ? a.target[((long)b * 21 + i) * 3 + d] : 0.0f;  // a target of weight 0 is selected out, not multiplied
+  }
+  if (t >= 128 && t < 128 + 5 * NJ) n.tipW[(t - 128) / NJ][(t - 128) % NJ] = a.m.skin[(long)kManoTip[(t - 128) / NJ] * NJ + (t - 128) % NJ];
+  if (t == 255) n.fail = 0;
+  __syncthreads();
+  if (t == 0) {
+    float sw = 0.f;
+    int st = 0;
+    for (int i = 0; i < 21; ++i) {
+      if (!(f.W[i] > 0.0f)) continue;
+      sw += f.W[i];
+      if (!(isfinite(f.Y[i][0]) && isfinite(f.Y[i][1]) && isfinite(f.Y[i][2]))) st |= 2;
+    }
+    if (!(sw > 0.0f)) st |= 1;
+    f.sw = sw;
+    f.sv = 0.0f;
+    f.status = st;
+  }
+  __syncthreads();
+  const bool ok = f.status == 0;  // otherwise: no init, no iteration, the state keeps its bits and the outputs evaluate it
+  const int iters = ok ? a.c.iters : 0;
+  float* hist = a.history ? a.history + (long)b * (a.c.iters + 1) : nullptr;
+  float* jac = a.jacobian ? a.jacobian + (long)b * GN_R * GN_P : nullptr;
+  if (t < 21) n.SQ[t] = (ok && f.W[t] > 0.0f) ? sqrtf(f.W[t] / f.sw) : 0.0f;
+  if (iters > 0 || jac) {  // d Jr / d beta: 48 dot products of length 778 per beta, a wave per beta
+    for (int k = wave; k < 10; k += 4) {
+      float acc[NJ * 3];
+#pragma unroll
+      for (int o = 0; o < NJ * 3; ++o) acc[o] = 0.f;
+      for (int v = lane; v < NV; v += 64) {
+        const float sx = a.m.shapeT[(long)k * NC + v * 3 + 0], sy = a.m.shapeT[(long)k * NC + v * 3 + 1], sz = a.m.shapeT[(long)k * NC + v * 3 + 2];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const float w = a.m.jreg[(long)j * NV + v];
+          acc[j * 3 + 0] = fmaf(w, sx, acc[j * 3 + 0]);
+          acc[j * 3 + 1] = fmaf(w, sy, acc[j * 3 + 1]);
+          acc[j * 3 + 2] = fmaf(w, sz, acc[j * 3 + 2]);
+        }
+      }
+#pragma unroll
+      for (int o = 0; o < NJ * 3; ++o) {
+        const float sum = wave_sum(acc[o]);
+        if (lane == 0) n.dJrS[k][o / 3][o % 3] = sum;
+      }
+    }
+  }
+  mano_fit_eval<false>(a.m, s, f, nullptr, t);
+  if (iters > 0 && a.c.init_trans) {  // summed in double and rounded once, as the mesh fit does
+    if (t < 3) {
+      double sum = 0.0, den = 0.0;
+      for (int i = 0; i < 21; ++i)
+        if (f.W[i] > 0.0f) {
+          sum = fma((double)f.W[i], (double)f.Y[i][t] - (double)f.Jm[i][t], sum);
+          den += (double)f.W[i];
+        }
+      f.P[58 + t] = (float)(sum / den);
+    }
+    __syncthreads();
+  }
+  if (t == 0) a.residual[(long)b * 2 + 0] = mano_fit_residual(f);
+  if (iters == 0 && jac) mano_gn_tangent(a.m, s, f, n, t, jac);  // only evaluates: the entry Jacobian is still reported
+  // This thread's entries of the 62 x 61 system (rows 0..60: the lower triangle of A; row 61: g), the same for every iteration: i | j << 8, or -1.
+  // Rows a and 60 - a of the triangle hold 62 entries together: 31 pairs (row 30 pairs with itself), then the 61 entries of g.
+  int slot[GN_SLOTS];
+#pragma unroll
+  for (int q = 0; q < GN_SLOTS; ++q) {
+    const int e = t + 256 * q, pr = e / 62, k = e - pr * 62;
+    int i = -1, j = 0;
+    if (e >= 31 * 62) {
+      if (e < 31 * 62 + GN_P) {
+        i = GN_P;
+        j = e - 31 * 62;
+      }
+    } else if (!(pr == 30 && k >= 31)) {
+      j = k < GN_P - pr ? pr : 60 - pr;                          // the column (the smaller index)
+      i = k < GN_P - pr ? pr + k : 60 - pr + (k - (GN_P - pr));  // the row (>= j)
+    }
+    slot[q] = i < 0 ? -1 : (i | (j << 8));
+  }
+  int done = 0, st4 = 0;
+  for (int it = 1; it <= iters; ++it) {
+    if (it > 1) mano_fit_eval<false>(a.m, s, f, nullptr, t);
+    if (t == 0 && hist) hist[it - 1] = mano_fit_residual(f);
+    mano_gn_tangent(a.m, s, f, n, t, it == 1 ? jac : nullptr);
+    // the normal matrix's lower triangle with the damped diagonal, and g as row 61: every thread forms its entries, each a sum over the 63 rows in
+    // ascending order, and keeps them in registers through the factorisation
+    float val[GN_SLOTS];
+#pragma unroll
+    for (int q = 0; q < GN_SLOTS; ++q) {
+      const int i = slot[q] & 255, j = slot[q] >> 8;
+      val[q] = 0.f;
+      if (slot[q] < 0) continue;
+      float sum = 0.f;
+      if (i == GN_P) {
+        for (int r = 0; r < GN_R; ++r) sum = fmaf(n.J[r][j], n.R[r], sum);
+        sum = fmaf(gn_lambda(a.c, j), f.P[j], sum);
+      } else {
+        for (int r = 0; r < GN_R; ++r) sum = fmaf(n.J[r][j], n.J[r][i], sum);
+        if (i == j) sum = fmaf(a.c.mu, sum, sum + gn_lambda(a.c, j)) + a.c.nu;
+      }
+      val[q] = sum;
+      if (j == 0) n.A[i][0] = sum;
+    }
+    __syncthreads();
+    // Cholesky in its square-root-free form, right-looking, one barrier per column: A = C D^-1 C^T with C's column k the column as elimination step k
+    // finds it (its head is the pivot d_k), so that L = C D^-1/2.  Step k subtracts c_ik c_jk / d_k from every entry right of column k; an entry is
+    // written to LDS once, when the step before its column has made it final.  Row 61 takes part like any other: it ends as C D^-1/2 z, z = L^-1 g.
+    for (int k = 0; k < GN_P; ++k) {
+      const float dk = n.A[k][k];
+      if (t == 0 && !(dk > 0.0f && isfinite(dk))) n.fail = 1;
+#pragma unroll
+      for (int q = 0; q < GN_SLOTS; ++q) {
+        const int i = slot[q] & 255, j = slot[q] >> 8;
+        if (j > k) {  // an empty slot has j < 0
+          val[q] = fmaf(-n.A[i][k], n.A[j][k] / dk, val[q]);
+          if (j == k + 1) n.A[i][j] = val[q];
+        }
+      }
+      __syncthreads();
+    }
+    if (n.fail) {  // a pivot that is not > 0 or not finite: stop, the state holds the last completed iteration
+      st4 = 4;
+      break;
+    }
+    if (wave == 0) {  // back substitution C^T delta = (row 61): lane i holds row 61's entry i and d_i, delta_k travels by a shuffle
+      float z = t < GN_P ? n.A[GN_P][t] : 0.0f, delta = 0.0f;
+      const float d = t < GN_P ? n.A[t][t] : 1.0f;
+      for (int k = GN_P - 1; k >= 0; --k) {
+        const float dk = __shfl(z, k, 64) / __shfl(d, k, 64);
+        if (t == k) delta = dk;
+        if (t < k) z = fmaf(-n.A[k][t], dk, z);
+      }
+      if (t < GN_P) f.P[t] = f.P[t] - delta;
+    }
+    done = it;
+    __syncthreads();
+  }
+  if (done > 0) mano_fit_eval<false>(a.m, s, f, nullptr, t);
+  if (t == 0) {
+    const float res = mano_fit_residual(f);
+    a.residual[(long)b * 2 + 1] = res;
+    a.status[b] = f.status | st4;
+    if (hist)  // after a stop the state no longer moves: the remaining entries repeat the last one
+      for (int it = (st4 ? done : iters); it <= a.c.iters; ++it) hist[it] = res;
+  }
+  if (ok) {
+    if (t < 48) a.pose[(long)b * 48 + t] = f.P[t];
+    else if (t < 58) a.betas[(long)b * 10 + (t - 48)] = f.P[t];
+    else if (t < 61) a.trans[(long)b * 3 + (t - 58)] = f.P[t];
+  }
+  if (t < 63) {
+    const int i = t / 3, d = t - i * 3;
+    a.joints[((long)b * 21 + i) * 3 + d] = f.Jm[a.c.joint_map[i]][d] + f.P[58 + d];
+  }
+  if (a.rotmat && t >= 64 && t < 64 + NJ) {  // rodrigues(pose_aa[j]): without hands_mean
+    float R[9];
+    rodrigues(&f.P[(t - 64) * 3], R);
+    for (int i = 0; i < 9; ++i) a.rotmat[((long)b * NJ + (t - 64)) * 9 + i] = R[i];
+  }
+  if (a.verts)
+    for (int v = t; v < NV; v += 256) {
+      float o[3];
+      mano_skin_vertex(a.m, s, v, o);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) a.verts[((long)b * NV + v) * 3 + r] = o[r] * 1000.0f + f.P[58 + r];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Association: each depth point's nearest vertex, and per vertex the weighted centroid and summed weight of its points -- the vertex targets of the fit
 // above, built without atomics.  One workgroup per hand.  Every operation is individually rounded (no contraction) and every sum runs in ascending index
 // order, so that a numpy-fp32 restatement gives the same bits (tests/mano_mesh_cases.py::associate_host).
@@ -1042,6 +1435,33 @@ extern "C" int kpf_mano_fit_mesh_f32(const float* target, const float* weight, c
   for (int i = 0; i < 21; ++i) c.joint_map[i] = cfg->joint_map[i];
   return mano_fit_launch("kpf_mano_fit_mesh_f32", target, weight, vert_target, vert_weight, shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights,
                          hands_mean, &c, cfg->lambda_verts, pose_aa, betas, trans, verts, joints, rotmat, residual, 4, status, B, stream);
+}
+
+extern "C" int kpf_mano_fit_gn_f32(const float* target, const float* weight, const float* shapedirs_t, const float* posedirs_t, const float* v_template,
+                                   const float* j_regressor, const float* skin_weights, const float* hands_mean, const kpf_mano_fit_gn_cfg* cfg,
+                                   float* pose_aa, float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status,
+                                   float* history, float* jacobian, int B, void* stream) {
+  const char* name = "kpf_mano_fit_gn_f32";
+  KPF_REQUIRE(target && shapedirs_t && posedirs_t && v_template && j_regressor && skin_weights && hands_mean && cfg && pose_aa && betas && trans && joints &&
+                  residual && status,
+              "%s: null pointer", name);
+  KPF_REQUIRE(B > 0, "%s: bad shape B=%d", name, B);
+  KPF_REQUIRE(cfg->iters >= 0 && cfg->iters <= 64, "%s: iters=%d outside [0, 64]", name, cfg->iters);
+  KPF_REQUIRE(cfg->mu >= 0.f && cfg->nu >= 0.f && isfinite(cfg->mu) && isfinite(cfg->nu), "%s: bad damping mu=%g nu=%g", name, cfg->mu, cfg->nu);
+  unsigned seen = 0;
+  for (int i = 0; i < 21; ++i) {
+    KPF_REQUIRE(cfg->joint_map[i] >= 0 && cfg->joint_map[i] < 21, "%s: joint_map[%d]=%d outside [0, 21)", name, i, cfg->joint_map[i]);
+    seen |= 1u << cfg->joint_map[i];
+  }
+  KPF_REQUIRE(seen == (1u << 21) - 1, "%s: joint_map is not a permutation", name);
+  ManoGnArgs a;
+  a.target = target; a.weight = weight;
+  a.m = ManoModel{shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights, hands_mean};
+  a.c = *cfg;
+  a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
+  a.status = status; a.history = history; a.jacobian = jacobian;
+  hipLaunchKernelGGL(mano_fit_gn_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch(name);
 }
 
 extern "C" int kpf_mano_assoc_f32(const float* points, const float* point_weight, const float* verts, float max_dist2, int* idx, float* vert_target,

@@ -13,7 +13,10 @@ mm, so 1.0 is small against any gradient that matters) they agree to 1e-4 mm, an
 Joints put the mesh where 21 points on the skeleton can: the shape is barely observable and nothing ties the skin to the sensor.  fit_mesh adds a vertex term
 (kpf_mano_fit_mesh_f32: 778 weighted vertex targets, a ground-truth mesh or the output of associate), associate gives every depth point its nearest vertex and
 every vertex the weighted centroid of its points (kpf_mano_assoc_f32; sum_n w_n |V - p_n|^2 and W |V - c|^2 have the same gradient, so the fit needs no
-atomics), and fit_cloud alternates the two on the depth points the preprocessing already sampled (cloud_mm).  DESIGN.md 4.12."""
+atomics), and fit_cloud alternates the two on the depth points the preprocessing already sampled (cloud_mm).  DESIGN.md 4.12.
+
+fit_gn is the joint fit by damped Gauss-Newton (kpf_mano_fit_gn_f32): the same objective and state, 8 iterations where Adam takes 50, one
+launch; fit_cloud(joint_solver="gn") uses it for its first stage."""
 import torch
 
 from . import lib as L
@@ -40,7 +43,8 @@ class ManoFitter:
         self.cfg = L.ManoFitCfg(int(iters), float(lr[0]), float(lr[1]), float(lr[2]), float(betas[0]), float(betas[1]), float(eps), float(lambda_shape),
                                 float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
         self.mesh_cfg = L.ManoFitMeshCfg(*[getattr(self.cfg, n) for n, _ in L.ManoFitCfg._fields_], 1.0)
-        self._bufs, self._mesh_bufs, self._assoc_bufs = {}, {}, {}
+        self.gn_cfg = L.ManoFitGnCfg(8, 0.1, 1e-2, float(lambda_shape), float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
+        self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs = {}, {}, {}, {}
 
     def new_state(self, B):
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
@@ -86,6 +90,53 @@ class ManoFitter:
                                               torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_f32")
         return {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
                 "residual": o["residual"], "status": o["status"]}
+
+    def fit_gn(self, joints_mm, weight=None, state=None, init_trans=True, iters=None, mu=0.1, nu=1e-2, jacobian=False):
+        """fit by damped Gauss-Newton (kpf_mano_fit_gn_f32): the same objective, state, targets, weights, joint_map and status convention,
+        an order of magnitude fewer iterations.  Per iteration, with r_i = sqrt(w_i / sum w) (J_map[i] + t - y_i) and J = d r / d (pose, betas, trans):
+        solve (J^T J + Lambda + mu diag(J^T J) + nu I) delta = J^T r + Lambda p by Cholesky and step p <- p - delta; the damping is fixed, nothing is
+        accepted or rejected.  iters=None: 8 (the fitter's `iters` is Adam's); 0 <= iters <= 64.  mu = 0 diverges on real starts: keep the damping.
+
+        Returns what fit returns plus history [B, iters + 1] (the mean weighted joint distance in mm before iteration 1 and after each iteration; its
+        first and last entries are residual's) and, with jacobian=True, jacobian [B, 63, 61]: the unweighted d (J_map[i] + t) / d p of the state on entry,
+        rows in target order.  status bit 4: the matrix was not positive definite -- the state holds the last completed iteration.  Own output tensors per
+        batch size (and per iters, for history); one launch, no host wait."""
+        B = joints_mm.shape[0]
+        self._check(joints_mm, (B, 21, 3), "joints_mm")
+        if weight is not None:
+            self._check(weight, (B, 21), "weight")
+        n = 8 if iters is None else int(iters)
+        if not 0 <= n <= 64:
+            raise ValueError("fit_gn takes 0 <= iters <= 64, not %d" % n)
+        if B not in self._gn_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            self._gn_bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 2),
+                                "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B), "history": {}}
+        o = self._gn_bufs[B]
+        if n not in o["history"]:
+            o["history"][n] = torch.empty(B, n + 1, device=self.device, dtype=torch.float32)
+        if jacobian and "jacobian" not in o:
+            o["jacobian"] = torch.empty(B, 63, 61, device=self.device, dtype=torch.float32)
+        hist = o["history"][n]
+        if state is None:
+            state = o["state"]
+            for s in state:
+                s.zero_()
+        pose, betas, trans = state
+        self._check_state(state, B)
+        c = self.gn_cfg
+        c.iters, c.mu, c.nu, c.init_trans = n, float(mu), float(nu), 1 if init_trans else 0
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_fit_gn_f32(joints_mm.data_ptr(), None if weight is None else weight.data_ptr(), *[m.data_ptr() for m in self.model],
+                                                 L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
+                                                 o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(),
+                                                 hist.data_ptr(), o["jacobian"].data_ptr() if jacobian else None, B,
+                                                 torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_gn_f32")
+        out = {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
+               "residual": o["residual"], "status": o["status"], "history": hist}
+        if jacobian:
+            out["jacobian"] = o["jacobian"]
+        return out
 
     def _check_state(self, state, B):
         for s, n in zip(state, (48, 10, 3)):
@@ -166,12 +217,18 @@ class ManoFitter:
         return dict(o)
 
     def fit_cloud(self, joints_mm, points_mm, weight=None, point_weight=None, state=None, init_trans=True, rounds=3, iters_cloud=None, max_dist=20.0,
-                  lambda_verts=1.0):
+                  lambda_verts=1.0, joint_solver="adam"):
         """Joints, then the depth points: one fit on the joints, then `rounds` times associate followed by fit_mesh (warm start, init_trans=False, the joints
         kept in the objective, iters_cloud iterations each; None = the fitter's), and last one associate on the final vertices: 2 * rounds + 2 launches and no
         host wait.  Returns the last fit's outputs plus cloud_before and cloud_after (the stats of the first and the last association: matched points and
-        their mean distance to the mesh in mm) and the last association's idx, vert_target and vert_weight.  rounds=0 is fit plus one associate."""
-        out = self.fit(joints_mm, weight, state=state, init_trans=init_trans)
+        their mean distance to the mesh in mm) and the last association's idx, vert_target and vert_weight.  rounds=0 is fit plus one associate.
+        joint_solver: "adam" (fit) or "gn" (fit_gn with its defaults) for the first stage; the vertex rounds are Adam either way."""
+        if joint_solver not in ("adam", "gn"):
+            raise ValueError("joint_solver must be \"adam\" or \"gn\", not %r" % (joint_solver,))
+        if joint_solver == "gn":
+            out = self.fit_gn(joints_mm, weight, state=state, init_trans=init_trans)
+        else:
+            out = self.fit(joints_mm, weight, state=state, init_trans=init_trans)
         state = (out["mano_pose_aa"], out["mano_shape"], out["trans"])
         first = None
         for r in range(int(rounds)):

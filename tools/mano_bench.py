@@ -1,6 +1,7 @@
 """Timing of the MANO layer in HIP: the MANO head's train step (forward + backward to the features and the MLP's parameters) at B = 32 with the
 hand model as torch ops under autograd (layer="torch") against heads_train.ManoLayerHip (layer="hip"), and the joint fit mano_fit.ManoFitter at B = 1 and 32
-with iters = 10 and 50; and the fit with a vertex term, the association of 1024 points and the chain fit_cloud (3 rounds) at B = 1 and 32
+with iters = 10 and 50; the Gauss-Newton fit fit_gn at B = 1 and 32 -- ms per call at its default 8 iterations, at 1 and 0, ms per
+iteration = (8 - 1) / 7, the residual and history after, Adam's 10 / 50-iteration figures of the same run beside them (records fit_gn_B1, fit_gn_B32); and the fit with a vertex term, the association of 1024 points and the chain fit_cloud (3 rounds) at B = 1 and 32
 with iters = 50.  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
@@ -65,6 +66,18 @@ def main():
             rec["fit_ms_B%d_iters%d" % (B, iters)] = _timed(lambda: fitter.fit(y), args.reps, torch)
             out = fitter.fit(y)
             rec["fit_residual_mm_B%d_iters%d" % (B, iters)] = [float(v) for v in out["residual"].mean(0)]
+    # the Gauss-Newton fit on the same targets: its default 8 iterations, 1 and 0 iterations for the cost of one, and Adam's figures of this run
+    for B in (1, 32):
+        fitter = ManoFitter(m, dev)
+        y = target[:B].contiguous()
+        ms = {n: _timed(lambda: fitter.fit_gn(y, iters=n), args.reps, torch) for n in (0, 1, 8)}
+        out = fitter.fit_gn(y)
+        rec["fit_gn_B%d" % B] = {"ms_iters8": ms[8], "ms_iters1": ms[1], "ms_iters0": ms[0], "ms_per_iteration": (ms[8] - ms[1]) / 7,
+                                 "residual_mm": [float(v) for v in out["residual"].mean(0)], "history_mm": [float(v) for v in out["history"].mean(0)],
+                                 "status": sorted(set(int(v) for v in out["status"])),
+                                 "adam_ms_iters10": rec["fit_ms_B%d_iters10" % B], "adam_ms_iters50": rec["fit_ms_B%d_iters50" % B],
+                                 "adam_residual_mm_iters10": rec["fit_residual_mm_B%d_iters10" % B][1],
+                                 "adam_residual_mm_iters50": rec["fit_residual_mm_B%d_iters50" % B][1]}
     # the mesh fit: the vertex targets are the hand's own vertices; the cloud is 1024 of them with 0.5 mm of noise
     verts = (pose["verts3d"] + torch.tensor([30.0, -20.0, 600.0], device=dev)).contiguous()
     pick = torch.randint(0, 778, (1024,), generator=gen).to(dev)
