@@ -382,6 +382,35 @@ int kpf_mano_fit_gn_f32(const float* target /*[B][21][3] mm*/, const float* weig
     float* residual /*[B][2]*/, int* status /*[B]*/, float* history /*[B][iters + 1] or NULL*/, float* jacobian /*[B][63][61] or NULL*/,
     int B, void* stream);
 
+/* The Gauss-Newton fit with the vertex term (ABI 29): the iteration of kpf_mano_fit_gn_f32 over the 63 joint rows and 2334 vertex rows
+ *   sqrt(lambda_verts u_v / sv) (V_v + t - c_v),  sv = sum u
+ * with the targets, weights and nullability of kpf_mano_fit_mesh_f32 (vert_target and vert_weight both or neither; target == NULL with a vertex term is
+ * a vertex-only fit; a call without either kind of target is refused, and so is vert_jacobian without a vertex term).  A row under weight 0 is selected out, never multiplied; a term whose weights sum to 0
+ * contributes nothing.  N = J^T J over all rows, A = N + Lambda + mu diag(N) + nu I, g = J^T r + Lambda p, A delta = g by Cholesky, p <- p - delta; the
+ * damping is fixed.  init_trans is kpf_mano_fit_mesh_f32's rule (the joints when sw > 0, otherwise the vertices; summed in double, rounded once).
+ * status bits: 1 BOTH weight sums are 0; 2 a joint or vertex target under a positive weight is not finite (either: the state keeps its bits, the outputs
+ * evaluate it); 4 a pivot is not > 0 or not finite (the state holds the last completed iteration, the history repeats).  residual [B][4] as
+ * kpf_mano_fit_mesh_f32.  history [B][iters + 1][2] or NULL: the mean weighted joint and vertex distance before iteration 1 and after each iteration.
+ * jacobian [B][63][61] or NULL as kpf_mano_fit_gn_f32; vert_jacobian [B][2334][61] or NULL (vertex term only): the unweighted d (V_v + t) / d p of the
+ * state on entry, mm, row v * 3 + d.  Without a vertex term the launch is kpf_mano_fit_gn_f32's kernel: state, joints, verts, rotmat, status,
+ * residual[:, :2] and history[..., 0] are its bits, the vertex distances are 0.  With it: one 256-thread workgroup per hand, every iteration inside the
+ * launch, J^T J and J^T r accumulated on v_mfma_f32_16x16x4_f32 in a fixed order, no atomics: bits depend neither on B nor on position nor on a replay. */
+typedef struct kpf_mano_fit_mesh_gn_cfg {
+  int iters;                       /* as kpf_mano_fit_gn_cfg, field for field ... */
+  float mu, nu;
+  float lambda_shape, lambda_pose; int init_trans;
+  int joint_map[21];
+  float lambda_verts;              /* ... plus the vertex term's factor, >= 0 */
+} kpf_mano_fit_mesh_gn_cfg;        /* HOST struct */
+int kpf_mano_fit_mesh_gn_f32(const float* target /*[B][21][3] mm, or NULL*/, const float* weight /*[B][21] >= 0, or NULL = ones*/,
+    const float* vert_target /*[B][778][3] mm, or NULL*/, const float* vert_weight /*[B][778] >= 0, or NULL; both or neither*/,
+    const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+    const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_gn_cfg* cfg,
+    float* pose_aa /*[B][48] in/out*/, float* betas /*[B][10] in/out*/, float* trans /*[B][3] mm in/out*/,
+    float* verts /*[B][778][3] or NULL*/, float* joints /*[B][21][3], target order*/, float* rotmat /*[B][16][9] or NULL*/,
+    float* residual /*[B][4]*/, int* status /*[B]*/, float* history /*[B][iters + 1][2] or NULL*/, float* jacobian /*[B][63][61] or NULL*/,
+    float* vert_jacobian /*[B][2334][61] or NULL*/, int B, void* stream);
+
 /* Depth points -> per-vertex targets (ABI 27), one workgroup per hand.  points [B][N][3] in camera-space mm (the frame of the tracker's cam_mm),
  * 1 <= N <= 4096 (any other N is refused and nothing is written); point_weight [B][N] or NULL = ones; verts [B][778][3] (a fit's verts);
  * max_dist2: squared gate in mm^2.  idx [B][N]: the nearest vertex or -1; vert_target / vert_weight: per vertex the weighted centroid and the summed
@@ -1034,7 +1063,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 28
+#define KPF_ABI_VERSION 29
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -4,6 +4,7 @@
 //   kpf_mano_fit_f32       Adam on pose / shape / translation against 21 target joints, every iteration inside the one launch (mano_fit.ManoFitter)
 //   kpf_mano_fit_mesh_f32  the same fit with a vertex term (778 weighted vertex targets): the second instantiation of the fit kernel
 //   kpf_mano_fit_gn_f32    the joint fit by damped Gauss-Newton: forward-mode Jacobian, normal matrix and Cholesky solve in LDS (its own kernel, further down)
+//   kpf_mano_fit_mesh_gn_f32  the Gauss-Newton fit with the vertex term: 2334 more rows, J^T J on the fp32 MFMA (its own kernel, after the joint fit's)
 //   kpf_mano_assoc_f32     depth points -> nearest vertex, per-vertex centroid and weight: the vertex targets of the fit above (its own kernel, further down)
 // The fits share the stage functions below; the forward's arithmetic is the text it had in kpf_aux.hip (tests/test_heads_gpu.py pins its bits).
 // Every reduction has a fixed order (wave butterflies, then a fixed sum over the four waves) and there are no atomics: a replay is bit-identical and a
@@ -881,6 +882,8 @@ struct ManoGnArgs {
   float *pose, *betas, *trans, *verts, *joints, *rotmat, *residual;
   int* status;
   float *history, *jacobian;  // [B][iters + 1], [B][63][61]; each may be null
+  int res_ld, hist_ld;        // 2 and 1: the layouts above.  4 and 2 (the mesh entry without a vertex term): residual [B][4] and history [B][iters + 1][2],
+                              // the vertex distances (columns 2, 3 and entry 1 of each pair) written as 0
 };
 
 struct ManoGnLds {
@@ -962,11 +965,50 @@ __device__ __forceinline__ void mano_gn_vertex_tangent(const ManoModel& m, const
            (T[r * 4 + 0] * dp[0] + T[r * 4 + 1] * dp[1] + T[r * 4 + 2] * dp[2]);
 }
 
+// What the vertex rows of the Gauss-Newton mesh fit keep in LDS beside the joint fit's state.  The system is padded to 64 columns:
+// 0..60 the unknowns, 61 the residual r (so that g = J^T r falls out of the same product as J^T J), 62 zero, 63 spare (see dG2).
+constexpr int GN_C = 64, GN_VB = 4, GN_CV = 4 * GN_VB, GN_CR = 3 * GN_CV, GN_CLD = 80, GN_DPLD = GN_CR + 1;
+constexpr int GN_CHUNKS = (NV + GN_CV - 1) / GN_CV;
+
+struct ManoGnVertLds {
+  float dG2[NJ * 12][GN_C];  // entry i of d G2[j] along column c at [j * 12 + i][c]: the column lanes write and read it without a bank conflict.  Column 63 holds
+                             // G2[j] itself, so that the lane that sums the tangent transforms of columns 0..60 sums the vertex's own transform T_v in lane 63
+  float dR[48][9];           // d Rj[c / 3] along pose column c
+  float dp[GN_C][GN_DPLD];   // d (v_posed) along column c for the chunk's 16 vertices x 3 coordinates (pose columns 3..47, shape columns 48..57), metres
+  float chunk[GN_C * GN_C];  // 48 rows of [J | r | 0 0] at a stride of 80 floats (rows k .. k + 3 of a tile column fall into 64 different banks); after the
+                             // last chunk: the 64 x 64 product
+  float vm[NC];              // the skinned vertices of this state, mm, without the translation
+  float w[GN_CV][NJ];        // the chunk's skinning weights: one coalesced load per thread, then wave-uniform LDS reads
+  float c[NC], u[NV];        // the vertex targets (selected to 0 where the weight is not > 0) and weights, loaded once per launch: a row's scale and its
+                             // residual then cost no global-memory latency inside the chunk loop
+};
+
+__device__ __forceinline__ void mano_gn_keep_rotation(ManoGnVertLds* x, int c, const float* dR) {
+  if (c < 48)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) x->dR[c][i] = dR[i];
+}
+
+__device__ __forceinline__ void mano_gn_keep_transform(ManoGnVertLds* x, int c, int j, const float* d2) {
+#pragma unroll
+  for (int i = 0; i < 12; ++i) x->dG2[j * 12 + i][c] = d2[i];
+}
+
+__device__ __forceinline__ void mano_gn_keep_spare(ManoGnVertLds* x, const ManoLds& s, int c) {  // lanes 61..63
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int i = 0; i < 12; ++i) x->dG2[j * 12 + i][c] = c == GN_C - 1 ? s.G2[j][i] : 0.0f;
+}
+
 // J and r of the state in s / f (after mano_fit_eval).  Lanes 0..60 of wave 0 each build one column forward-mode: the tangent transform is carried down
 // the chain (a joint's parent is the root or the joint before it, so the root's and the previous joint's tangents in registers are enough) and the five
 // tips' blended tangent transforms are accumulated on the way.  gout: null, or [63][61] for the unweighted columns in target-row order.
 // All 256 threads; ends with a barrier.
-__device__ __forceinline__ void mano_gn_tangent(const ManoModel& m, const ManoLds& s, const ManoFitLds& f, ManoGnLds& n, int t, float* gout) {
+// VT (the fit with the vertex term): every column lane also leaves what the vertex rows need in x -- its joint's rotation tangent and, joint by joint as it
+// walks the chain, its tangent transforms d G2[j]; lanes 61..63 fill the three spare columns (zeros, and G2 itself in column 63).
+template <bool VT>
+__device__ __forceinline__ void mano_gn_tangent(const ManoModel& m, const ManoLds& s, const ManoFitLds& f, ManoGnLds& n, int t, float* gout,
+                                                ManoGnVertLds* x = nullptr) {
   if (t >= 64 && t < 64 + 60) {  // the tips' blended transforms of this state, j ascending as mano_skin_transform
     const int k = (t - 64) / 12, i = (t - 64) % 12;
     float sum = 0.f;
@@ -991,6 +1033,7 @@ __device__ __forceinline__ void mano_gn_tangent(const ManoModel& m, const ManoLd
         for (int i = 0; i < 3; ++i) aa[i] = m.hands_mean[(col.a - 1) * 3 + i] + aa[i];
       rodrigues_tangent(aa, t - col.a * 3, col.dR);
     }
+    if constexpr (VT) mano_gn_keep_rotation(x, t, col.dR);
     auto put = [&](int h, int r, float metres) {  // model joint h, coordinate r: the column's entry in mm
       const float v = metres * 1000.0f + (r == td ? 1.0f : 0.0f);
       n.J[h * 3 + r][t] = f.W[h] > 0.0f ? n.SQ[h] * v : 0.0f;
@@ -1051,6 +1094,7 @@ __device__ __forceinline__ void mano_gn_tangent(const ManoModel& m, const ManoLd
         d2[r * 4 + 3] = dG[r * 4 + 3] - (dG[r * 4 + 0] * s.Jr[j][0] + dG[r * 4 + 1] * s.Jr[j][1] + dG[r * 4 + 2] * s.Jr[j][2]) -
                         (s.G[j][r * 4 + 0] * dJ[0] + s.G[j][r * 4 + 1] * dJ[1] + s.G[j][r * 4 + 2] * dJ[2]);
       }
+      if constexpr (VT) mano_gn_keep_transform(x, t, j, d2);
 #pragma unroll
       for (int k = 0; k < 5; ++k) {
         const float w = n.tipW[k][j];
@@ -1070,8 +1114,64 @@ __device__ __forceinline__ void mano_gn_tangent(const ManoModel& m, const ManoLd
 #pragma unroll
       for (int r = 0; r < 3; ++r) put(kManoTipRow[k], r, o[r]);
     }
+  } else if constexpr (VT) {
+    if (t < 64) mano_gn_keep_spare(x, s, t);
   }
   __syncthreads();
+}
+
+// This thread's entries of the 62 x 61 system (rows 0..60: the lower triangle of A; row 61: g), the same for every iteration: i | j << 8, or -1.
+// Rows a and 60 - a of the triangle hold 62 entries together: 31 pairs (row 30 pairs with itself), then the 61 entries of g.
+__device__ __forceinline__ void mano_gn_slots(int t, int (&slot)[GN_SLOTS]) {
+#pragma unroll
+  for (int q = 0; q < GN_SLOTS; ++q) {
+    const int e = t + 256 * q, pr = e / 62, k = e - pr * 62;
+    int i = -1, j = 0;
+    if (e >= 31 * 62) {
+      if (e < 31 * 62 + GN_P) {
+        i = GN_P;
+        j = e - 31 * 62;
+      }
+    } else if (!(pr == 30 && k >= 31)) {
+      j = k < GN_P - pr ? pr : 60 - pr;                          // the column (the smaller index)
+      i = k < GN_P - pr ? pr + k : 60 - pr + (k - (GN_P - pr));  // the row (>= j)
+    }
+    slot[q] = i < 0 ? -1 : (i | (j << 8));
+  }
+}
+
+// The system in val (each thread's entries, column 0 already in n.A) -> p <- p - delta.  False, and the state untouched, if a pivot is not > 0 or not finite.
+// All 256 threads; begins with a barrier, and the caller ends the iteration with one.
+__device__ __forceinline__ bool mano_gn_solve(ManoGnLds& n, ManoFitLds& f, const int (&slot)[GN_SLOTS], float (&val)[GN_SLOTS], int t) {
+  __syncthreads();
+  // Cholesky in its square-root-free form, right-looking, one barrier per column: A = C D^-1 C^T with C's column k the column as elimination step k
+  // finds it (its head is the pivot d_k), so that L = C D^-1/2.  Step k subtracts c_ik c_jk / d_k from every entry right of column k; an entry is
+  // written to LDS once, when the step before its column has made it final.  Row 61 takes part like any other: it ends as C D^-1/2 z, z = L^-1 g.
+  for (int k = 0; k < GN_P; ++k) {
+    const float dk = n.A[k][k];
+    if (t == 0 && !(dk > 0.0f && isfinite(dk))) n.fail = 1;
+#pragma unroll
+    for (int q = 0; q < GN_SLOTS; ++q) {
+      const int i = slot[q] & 255, j = slot[q] >> 8;
+      if (j > k) {  // an empty slot has j < 0
+        val[q] = fmaf(-n.A[i][k], n.A[j][k] / dk, val[q]);
+        if (j == k + 1) n.A[i][j] = val[q];
+      }
+    }
+    __syncthreads();
+  }
+  if (n.fail) return false;
+  if ((t >> 6) == 0) {  // back substitution C^T delta = (row 61): lane i holds row 61's entry i and d_i, delta_k travels by a shuffle
+    float z = t < GN_P ? n.A[GN_P][t] : 0.0f, delta = 0.0f;
+    const float d = t < GN_P ? n.A[t][t] : 1.0f;
+    for (int k = GN_P - 1; k >= 0; --k) {
+      const float dk = __shfl(z, k, 64) / __shfl(d, k, 64);
+      if (t == k) delta = dk;
+      if (t < k) z = fmaf(-n.A[k][t], dk, z);
+    }
+    if (t < GN_P) f.P[t] = f.P[t] - delta;
+  }
+  return true;
 }
 
 __global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
@@ -1109,7 +1209,7 @@ __global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
   __syncthreads();
   const bool ok = f.status == 0;  // otherwise: no init, no iteration, the state keeps its bits and the outputs evaluate it
   const int iters = ok ? a.c.iters : 0;
-  float* hist = a.history ? a.history + (long)b * (a.c.iters + 1) : nullptr;
+  float* hist = a.history ? a.history + (long)b * (a.c.iters + 1) * a.hist_ld : nullptr;
   float* jac = a.jacobian ? a.jacobian + (long)b * GN_R * GN_P : nullptr;
   if (t < 21) n.SQ[t] = (ok && f.W[t] > 0.0f) ? sqrtf(f.W[t] / f.sw) : 0.0f;
   if (iters > 0 || jac) {  // d Jr / d beta: 48 dot products of length 778 per beta, a wave per beta
@@ -1147,31 +1247,15 @@ __global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
     }
     __syncthreads();
   }
-  if (t == 0) a.residual[(long)b * 2 + 0] = mano_fit_residual(f);
-  if (iters == 0 && jac) mano_gn_tangent(a.m, s, f, n, t, jac);  // only evaluates: the entry Jacobian is still reported
-  // This thread's entries of the 62 x 61 system (rows 0..60: the lower triangle of A; row 61: g), the same for every iteration: i | j << 8, or -1.
-  // Rows a and 60 - a of the triangle hold 62 entries together: 31 pairs (row 30 pairs with itself), then the 61 entries of g.
+  if (t == 0) a.residual[(long)b * a.res_ld + 0] = mano_fit_residual(f);
+  if (iters == 0 && jac) mano_gn_tangent<false>(a.m, s, f, n, t, jac);  // only evaluates: the entry Jacobian is still reported
   int slot[GN_SLOTS];
-#pragma unroll
-  for (int q = 0; q < GN_SLOTS; ++q) {
-    const int e = t + 256 * q, pr = e / 62, k = e - pr * 62;
-    int i = -1, j = 0;
-    if (e >= 31 * 62) {
-      if (e < 31 * 62 + GN_P) {
-        i = GN_P;
-        j = e - 31 * 62;
-      }
-    } else if (!(pr == 30 && k >= 31)) {
-      j = k < GN_P - pr ? pr : 60 - pr;                          // the column (the smaller index)
-      i = k < GN_P - pr ? pr + k : 60 - pr + (k - (GN_P - pr));  // the row (>= j)
-    }
-    slot[q] = i < 0 ? -1 : (i | (j << 8));
-  }
+  mano_gn_slots(t, slot);
   int done = 0, st4 = 0;
   for (int it = 1; it <= iters; ++it) {
     if (it > 1) mano_fit_eval<false>(a.m, s, f, nullptr, t);
-    if (t == 0 && hist) hist[it - 1] = mano_fit_residual(f);
-    mano_gn_tangent(a.m, s, f, n, t, it == 1 ? jac : nullptr);
+    if (t == 0 && hist) hist[(it - 1) * a.hist_ld] = mano_fit_residual(f);
+    mano_gn_tangent<false>(a.m, s, f, n, t, it == 1 ? jac : nullptr);
     // the normal matrix's lower triangle with the damped diagonal, and g as row 61: every thread forms its entries, each a sum over the 63 rows in
     // ascending order, and keeps them in registers through the factorisation
     float val[GN_SLOTS];
@@ -1191,36 +1275,9 @@ __global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
       val[q] = sum;
       if (j == 0) n.A[i][0] = sum;
     }
-    __syncthreads();
-    // Cholesky in its square-root-free form, right-looking, one barrier per column: A = C D^-1 C^T with C's column k the column as elimination step k
-    // finds it (its head is the pivot d_k), so that L = C D^-1/2.  Step k subtracts c_ik c_jk / d_k from every entry right of column k; an entry is
-    // written to LDS once, when the step before its column has made it final.  Row 61 takes part like any other: it ends as C D^-1/2 z, z = L^-1 g.
-    for (int k = 0; k < GN_P; ++k) {
-      const float dk = n.A[k][k];
-      if (t == 0 && !(dk > 0.0f && isfinite(dk))) n.fail = 1;
-#pragma unroll
-      for (int q = 0; q < GN_SLOTS; ++q) {
-        const int i = slot[q] & 255, j = slot[q] >> 8;
-        if (j > k) {  // an empty slot has j < 0
-          val[q] = fmaf(-n.A[i][k], n.A[j][k] / dk, val[q]);
-          if (j == k + 1) n.A[i][j] = val[q];
-        }
-      }
-      __syncthreads();
-    }
-    if (n.fail) {  // a pivot that is not > 0 or not finite: stop, the state holds the last completed iteration
+    if (!mano_gn_solve(n, f, slot, val, t)) {  // a pivot that is not > 0 or not finite: stop, the state holds the last completed iteration
       st4 = 4;
       break;
-    }
-    if (wave == 0) {  // back substitution C^T delta = (row 61): lane i holds row 61's entry i and d_i, delta_k travels by a shuffle
-      float z = t < GN_P ? n.A[GN_P][t] : 0.0f, delta = 0.0f;
-      const float d = t < GN_P ? n.A[t][t] : 1.0f;
-      for (int k = GN_P - 1; k >= 0; --k) {
-        const float dk = __shfl(z, k, 64) / __shfl(d, k, 64);
-        if (t == k) delta = dk;
-        if (t < k) z = fmaf(-n.A[k][t], dk, z);
-      }
-      if (t < GN_P) f.P[t] = f.P[t] - delta;
     }
     done = it;
     __syncthreads();
@@ -1228,10 +1285,13 @@ __global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
   if (done > 0) mano_fit_eval<false>(a.m, s, f, nullptr, t);
   if (t == 0) {
     const float res = mano_fit_residual(f);
-    a.residual[(long)b * 2 + 1] = res;
+    a.residual[(long)b * a.res_ld + 1] = res;
     a.status[b] = f.status | st4;
     if (hist)  // after a stop the state no longer moves: the remaining entries repeat the last one
-      for (int it = (st4 ? done : iters); it <= a.c.iters; ++it) hist[it] = res;
+      for (int it = (st4 ? done : iters); it <= a.c.iters; ++it) hist[it * a.hist_ld] = res;
+    if (a.res_ld == 4) a.residual[(long)b * 4 + 2] = a.residual[(long)b * 4 + 3] = 0.0f;
+    if (hist && a.hist_ld == 2)
+      for (int it = 0; it <= a.c.iters; ++it) hist[it * 2 + 1] = 0.0f;
   }
   if (ok) {
     if (t < 48) a.pose[(long)b * 48 + t] = f.P[t];
@@ -1254,6 +1314,316 @@ __global__ __launch_bounds__(256) void mano_fit_gn_kernel(ManoGnArgs a) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) a.verts[((long)b * NV + v) * 3 + r] = o[r] * 1000.0f + f.P[58 + r];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Gauss-Newton mesh fit: the iteration above with 2334 more rows, sqrt(lambda_verts u_v / sv) (V_v + t - c_v).  Per iteration, after
+// mano_fit_eval<true> (all 778 vertices) and mano_gn_tangent<true> (J and r of the joints; every column's d G2[j] left in LDS):
+//   the vertex rows in 49 chunks of 16 vertices -- a wave takes four vertices, a lane one of the 64 columns, and sums dT = sum_j w[v][j] d G2[j] for its
+//   four vertices from one read of d G2[j] (lane 63 sums T_v itself that way); d v_posed of the chunk is formed once by all 256 threads from coalesced
+//   reads of posedirs / shapedirs; row = scale (dT [p; 1] + T[:, :3] d p) in mm, column 61 = scale (V + t - c);
+//   the product [J | r]^T [J | r] on v_mfma_f32_16x16x4_f32: wave w holds tile row w (4 tiles of 16 x 16) in registers across the joint rows and all chunks,
+//   k ascending, so N = J^T J is its leading 61 x 61 block and g = J^T r its row 61;
+//   the spill to LDS, Lambda and the damping, and the joint fit's factorisation and back substitution (mano_gn_solve).
+// ---------------------------------------------------------------------------------------------------------------
+struct ManoMeshGnArgs {
+  const float *target, *weight, *vtarget, *vweight;  // target may be null (no joint carries weight); the vertex pair is never null here
+  ManoModel m;
+  kpf_mano_fit_gn_cfg c;
+  float lambda_verts;
+  float *pose, *betas, *trans, *verts, *joints, *rotmat, *residual;
+  int* status;
+  float *history, *jacobian, *vjacobian;  // [B][iters + 1][2], [B][63][61], [B][2334][61]; each may be null
+};
+
+// Chunk ch's 48 rows into x.chunk (vjac: null, or the unweighted rows of every vertex, [2334][61]).  All 256 threads; ends with a barrier, and its inner
+// barrier also separates the previous chunk's product from this chunk's rows.
+__device__ __forceinline__ void mano_gn_vertex_chunk(const ManoModel& m, const ManoLds& s, const ManoFitLds& f, ManoGnVertLds& x, float lambda, int ch, int t,
+                                                     float* vjac) {
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, base = ch * GN_CV;
+  int vq[GN_VB];  // this wave's vertices; past the last one: the last one's loads, and zero rows
+#pragma unroll
+  for (int q = 0; q < GN_VB; ++q) vq[q] = min(base + wave * GN_VB + q, NV - 1);
+  x.w[t >> 4][t & 15] = m.skin[(long)min(base + (t >> 4), NV - 1) * NJ + (t & 15)];
+#pragma unroll
+  for (int e = t; e < 15 * GN_CR; e += 256) {  // pmap = Rj[1:] - I: joint a's nine rows of posedirs serve its three columns
+    const int a = e / GN_CR + 1, vd = e % GN_CR, c = base * 3 + vd;
+    float p[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) p[i] = c < NC ? m.poseT[(long)((a - 1) * 9 + i) * NC + c] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      float sum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) sum = fmaf(p[i], x.dR[a * 3 + k][i], sum);
+      x.dp[a * 3 + k][vd] = sum;
+    }
+  }
+#pragma unroll
+  for (int e = t; e < 10 * GN_CR; e += 256) {
+    const int k = e / GN_CR, vd = e % GN_CR, c = base * 3 + vd;
+    x.dp[48 + k][vd] = c < NC ? m.shapeT[(long)k * NC + c] : 0.f;
+  }
+  __syncthreads();
+  float dT[GN_VB][12];
+#pragma unroll
+  for (int q = 0; q < GN_VB; ++q)
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dT[q][i] = 0.f;
+#pragma unroll 4
+  for (int j = 0; j < NJ; ++j) {
+    float d[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) d[i] = x.dG2[j * 12 + i][lane];
+#pragma unroll
+    for (int q = 0; q < GN_VB; ++q) {
+      const float w = x.w[wave * GN_VB + q][j];
+#pragma unroll
+      for (int i = 0; i < 12; ++i) dT[q][i] = fmaf(w, d[i], dT[q][i]);
+    }
+  }
+  const bool moves = lane >= 3 && lane < 58;  // v_posed does not move with the root's rotation or the translation
+#pragma unroll
+  for (int q = 0; q < GN_VB; ++q) {
+    const int v = vq[q], row0 = (wave * GN_VB + q) * 3;
+    const bool valid = base + wave * GN_VB + q < NV;
+    float T[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dT[q][i]), GN_C - 1));
+    const float u = x.u[v];
+    const bool on = valid && u > 0.0f;  // a row under weight 0 is selected out, never multiplied
+    const float scale = on ? sqrtf(lambda * u / f.sv) : 0.0f;
+    const float px = s.v[v * 3 + 0], py = s.v[v * 3 + 1], pz = s.v[v * 3 + 2];
+    const float d0 = moves ? x.dp[lane][row0 + 0] : 0.f, d1 = moves ? x.dp[lane][row0 + 1] : 0.f, d2 = moves ? x.dp[lane][row0 + 2] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const float o = (dT[q][r * 4 + 0] * px + dT[q][r * 4 + 1] * py + dT[q][r * 4 + 2] * pz + dT[q][r * 4 + 3]) +
+                      (T[r * 4 + 0] * d0 + T[r * 4 + 1] * d1 + T[r * 4 + 2] * d2);
+      const float val = o * 1000.0f + (lane - 58 == r ? 1.0f : 0.0f);
+      if (vjac && valid && lane < GN_P) vjac[(long)(v * 3 + r) * GN_P + lane] = val;
+      float e = 0.f;
+      if (on && lane < GN_P) e = scale * val;
+      else if (on && lane == GN_P) e = scale * (x.vm[v * 3 + r] + f.P[58 + r] - x.c[v * 3 + r]);
+      x.chunk[(row0 + r) * GN_CLD + lane] = e;
+    }
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ float mano_mesh_gn_vert_distance(ManoFitLds& f, const ManoGnVertLds& x, int t) {
+  float in = mano_vert_distance(x.c, x.u, x.vm, &f.P[58], t), sum;
+  mano_block_sum<1>(f, t, &in, &sum);
+  return f.sv > 0.0f ? sum / f.sv : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a) {
+  __shared__ ManoLds s;
+  __shared__ ManoFitLds f;
+  __shared__ ManoGnLds n;
+  __shared__ ManoGnVertLds x;
+  const int b = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const float* vc = a.vtarget + (long)b * NC;
+  const float* vu = a.vweight + (long)b * NV;
+  // the state, the targets and the status: the mesh fit's rules
+  if (t < 48) f.P[t] = a.pose[(long)b * 48 + t];
+  else if (t < 58) f.P[t] = a.betas[(long)b * 10 + (t - 48)];
+  else if (t < 61) f.P[t] = a.trans[(long)b * 3 + (t - 58)];
+  if (t >= 64 && t < 64 + 21) {
+    const int i = t - 64, h = a.c.joint_map[i];
+    const float w = a.target ? (a.weight ? a.weight[(long)b * 21 + i] : 1.0f) : 0.0f;
+    f.W[h] = w;
+    n.inv[h] = i;
+    for (int d = 0; d < 3; ++d) f.Y[h][d] = w > 0.0f ? a.target[((long)b * 21 + i) * 3 + d] : 0.0f;  // a target of weight 0 is selected out, not multiplied
+  }
+  if (t >= 128 && t < 128 + 5 * NJ) n.tipW[(t - 128) / NJ][(t - 128) % NJ] = a.m.skin[(long)kManoTip[(t - 128) / NJ] * NJ + (t - 128) % NJ];
+  if (t == 255) n.fail = 0;
+  for (int v = t; v < NV; v += 256) {
+    const float u = vu[v];
+    x.u[v] = u;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) x.c[v * 3 + d] = u > 0.0f ? vc[v * 3 + d] : 0.0f;  // a target of weight 0 is selected out, not multiplied
+  }
+  float vstat[2];  // sum of the vertex weights, non-finite vertex targets under a positive weight
+  {
+    float in[2];
+    mano_vert_weights(vc, vu, t, in);
+    mano_block_sum<2>(f, t, in, vstat);
+  }
+  __syncthreads();
+  if (t == 0) {
+    float sw = 0.f;
+    int st = 0;
+    for (int i = 0; i < 21; ++i) {
+      if (!(f.W[i] > 0.0f)) continue;
+      sw += f.W[i];
+      if (!(isfinite(f.Y[i][0]) && isfinite(f.Y[i][1]) && isfinite(f.Y[i][2]))) st |= 2;
+    }
+    if (vstat[1] > 0.0f) st |= 2;
+    if (!(sw > 0.0f) && !(vstat[0] > 0.0f)) st |= 1;
+    f.sw = sw;
+    f.sv = vstat[0];
+    f.status = st;
+  }
+  __syncthreads();
+  const bool ok = f.status == 0;  // otherwise: no init, no iteration, the state keeps its bits and the outputs evaluate it
+  const int iters = ok ? a.c.iters : 0;
+  float* hist = a.history ? a.history + (long)b * (a.c.iters + 1) * 2 : nullptr;
+  float* jac = a.jacobian ? a.jacobian + (long)b * GN_R * GN_P : nullptr;
+  float* vjac = a.vjacobian ? a.vjacobian + (long)b * NC * GN_P : nullptr;
+  if (t < 21) n.SQ[t] = (ok && f.W[t] > 0.0f) ? sqrtf(f.W[t] / f.sw) : 0.0f;
+  if (iters > 0 || jac || vjac) {  // d Jr / d beta, as the joint fit forms it
+    for (int k = wave; k < 10; k += 4) {
+      float acc[NJ * 3];
+#pragma unroll
+      for (int o = 0; o < NJ * 3; ++o) acc[o] = 0.f;
+      for (int v = lane; v < NV; v += 64) {
+        const float sx = a.m.shapeT[(long)k * NC + v * 3 + 0], sy = a.m.shapeT[(long)k * NC + v * 3 + 1], sz = a.m.shapeT[(long)k * NC + v * 3 + 2];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const float w = a.m.jreg[(long)j * NV + v];
+          acc[j * 3 + 0] = fmaf(w, sx, acc[j * 3 + 0]);
+          acc[j * 3 + 1] = fmaf(w, sy, acc[j * 3 + 1]);
+          acc[j * 3 + 2] = fmaf(w, sz, acc[j * 3 + 2]);
+        }
+      }
+#pragma unroll
+      for (int o = 0; o < NJ * 3; ++o) {
+        const float sum = wave_sum(acc[o]);
+        if (lane == 0) n.dJrS[k][o / 3][o % 3] = sum;
+      }
+    }
+  }
+  mano_fit_eval<true>(a.m, s, f, x.vm, t);
+  if (iters > 0 && a.c.init_trans) {  // the mesh fit's rule: from the joints when they carry weight, otherwise from the vertices; in double, rounded once
+    if (f.sw > 0.0f) {
+      if (t < 3) {
+        double sum = 0.0, den = 0.0;
+        for (int i = 0; i < 21; ++i)
+          if (f.W[i] > 0.0f) {
+            sum = fma((double)f.W[i], (double)f.Y[i][t] - (double)f.Jm[i][t], sum);
+            den += (double)f.W[i];
+          }
+        f.P[58 + t] = (float)(sum / den);
+      }
+    } else {
+      double in[3], off[3];
+      mano_vert_offset(x.c, x.u, x.vm, t, in);
+      mano_block_sum3d(f, t, in, off);
+      if (t < 3) f.P[58 + t] = (float)((t == 0 ? off[0] : (t == 1 ? off[1] : off[2])) / (double)f.sv);
+    }
+    __syncthreads();
+  }
+  {
+    const float dv = mano_mesh_gn_vert_distance(f, x, t);
+    if (t == 0) {
+      a.residual[(long)b * 4 + 0] = mano_fit_residual(f);
+      a.residual[(long)b * 4 + 2] = dv;
+    }
+  }
+  if (iters == 0 && (jac || vjac)) {  // only evaluates: the entry Jacobians are still reported
+    mano_gn_tangent<true>(a.m, s, f, n, t, jac, &x);
+    if (vjac)
+      for (int ch = 0; ch < GN_CHUNKS; ++ch) mano_gn_vertex_chunk(a.m, s, f, x, a.lambda_verts, ch, t, vjac);
+  }
+  int slot[GN_SLOTS];
+  mano_gn_slots(t, slot);
+  int done = 0, st4 = 0;
+  for (int it = 1; it <= iters; ++it) {
+    if (it > 1) mano_fit_eval<true>(a.m, s, f, x.vm, t);
+    if (hist) {
+      const float dv = mano_mesh_gn_vert_distance(f, x, t);
+      if (t == 0) {
+        hist[(it - 1) * 2 + 0] = mano_fit_residual(f);
+        hist[(it - 1) * 2 + 1] = dv;
+      }
+    }
+    mano_gn_tangent<true>(a.m, s, f, n, t, it == 1 ? jac : nullptr, &x);
+    // wave w's tile row of [J | r]^T [J | r]: lane l feeds element [k0 + l / 16][tile * 16 + l % 16] of the rows to both operands and holds
+    // rows w * 16 + 4 (l / 16) + 0..3 of column tile * 16 + l % 16 in acc[tile].  The sum has two levels, both in a fixed order: the joint rows and each
+    // chunk's 48 rows are summed from zero (part) and the 50 partial sums are added in turn -- one chain over all 2397 rows would round about five
+    // times as much, and that error of J^T J was the largest term of the state's distance from the float64 iteration
+    f32x4 acc[4], part[4];
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) acc[tj] = part[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < 64; k0 += 4) {  // the 63 joint rows, as mano_gn_tangent left them (a row under weight 0 is 0)
+      const int k = k0 + (lane >> 4);
+      auto el = [&](int c) { return k < GN_R ? (c < GN_P ? n.J[k][c] : (c == GN_P ? n.R[k] : 0.0f)) : 0.0f; };
+      const float av = el(wave * 16 + (lane & 15));
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj) part[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, el(tj * 16 + (lane & 15)), part[tj], 0, 0, 0);
+    }
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) acc[tj] = part[tj];
+    for (int ch = 0; ch < GN_CHUNKS; ++ch) {
+      mano_gn_vertex_chunk(a.m, s, f, x, a.lambda_verts, ch, t, it == 1 ? vjac : nullptr);
+      const float* rows = x.chunk + (lane >> 4) * GN_CLD + (lane & 15);
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj) part[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k0 = 0; k0 < GN_CR; k0 += 4) {
+        const float av = rows[k0 * GN_CLD + wave * 16];
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj) part[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, rows[k0 * GN_CLD + tj * 16], part[tj], 0, 0, 0);
+      }
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj) acc[tj] += part[tj];
+    }
+    __syncthreads();  // the last chunk's rows have been read: x.chunk becomes the 64 x 64 product
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) x.chunk[(wave * 16 + 4 * (lane >> 4) + r) * GN_C + tj * 16 + (lane & 15)] = acc[tj][r];
+    __syncthreads();
+    float val[GN_SLOTS];  // the lower triangle with Lambda and the damping, and g as row 61: the joint fit's layout
+#pragma unroll
+    for (int q = 0; q < GN_SLOTS; ++q) {
+      const int i = slot[q] & 255, j = slot[q] >> 8;
+      val[q] = 0.f;
+      if (slot[q] < 0) continue;
+      float sum = x.chunk[i * GN_C + j];
+      if (i == GN_P) sum = fmaf(gn_lambda(a.c, j), f.P[j], sum);
+      else if (i == j) sum = fmaf(a.c.mu, sum, sum + gn_lambda(a.c, j)) + a.c.nu;
+      val[q] = sum;
+      if (j == 0) n.A[i][0] = sum;
+    }
+    if (!mano_gn_solve(n, f, slot, val, t)) {  // a pivot that is not > 0 or not finite: stop, the state holds the last completed iteration
+      st4 = 4;
+      break;
+    }
+    done = it;
+    __syncthreads();
+  }
+  if (done > 0) mano_fit_eval<true>(a.m, s, f, x.vm, t);
+  {
+    const float dv = mano_mesh_gn_vert_distance(f, x, t);
+    if (t == 0) {
+      const float res = mano_fit_residual(f);
+      a.residual[(long)b * 4 + 1] = res;
+      a.residual[(long)b * 4 + 3] = dv;
+      a.status[b] = f.status | st4;
+      if (hist)  // after a stop the state no longer moves: the remaining entries repeat the last one
+        for (int it = (st4 ? done : iters); it <= a.c.iters; ++it) {
+          hist[it * 2 + 0] = res;
+          hist[it * 2 + 1] = dv;
+        }
+    }
+  }
+  if (ok) {
+    if (t < 48) a.pose[(long)b * 48 + t] = f.P[t];
+    else if (t < 58) a.betas[(long)b * 10 + (t - 48)] = f.P[t];
+    else if (t < 61) a.trans[(long)b * 3 + (t - 58)] = f.P[t];
+  }
+  if (t < 63) {
+    const int i = t / 3, d = t - i * 3;
+    a.joints[((long)b * 21 + i) * 3 + d] = f.Jm[a.c.joint_map[i]][d] + f.P[58 + d];
+  }
+  if (a.rotmat && t >= 64 && t < 64 + NJ) {  // rodrigues(pose_aa[j]): without hands_mean
+    float R[9];
+    rodrigues(&f.P[(t - 64) * 3], R);
+    for (int i = 0; i < 9; ++i) a.rotmat[((long)b * NJ + (t - 64)) * 9 + i] = R[i];
+  }
+  if (a.verts)
+    for (int c = t; c < NC; c += 256) a.verts[(long)b * NC + c] = x.vm[c] + f.P[58 + c % 3];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1460,7 +1830,59 @@ extern "C" int kpf_mano_fit_gn_f32(const float* target, const float* weight, con
   a.c = *cfg;
   a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
   a.status = status; a.history = history; a.jacobian = jacobian;
+  a.res_ld = 2; a.hist_ld = 1;
   hipLaunchKernelGGL(mano_fit_gn_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch(name);
+}
+
+extern "C" int kpf_mano_fit_mesh_gn_f32(const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+                                        const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+                                        const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_gn_cfg* cfg, float* pose_aa,
+                                        float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status,
+                                        float* history, float* jacobian, float* vert_jacobian, int B, void* stream) {
+  const char* name = "kpf_mano_fit_mesh_gn_f32";
+  KPF_REQUIRE(shapedirs_t && posedirs_t && v_template && j_regressor && skin_weights && hands_mean && cfg && pose_aa && betas && trans && joints &&
+                  residual && status,
+              "%s: null pointer", name);
+  KPF_REQUIRE((vert_target == nullptr) == (vert_weight == nullptr), "%s: vert_target and vert_weight go together", name);
+  KPF_REQUIRE(target || vert_target, "%s: neither joint nor vertex targets", name);
+  KPF_REQUIRE(vert_target || !vert_jacobian, "%s: vert_jacobian needs the vertex term", name);
+  KPF_REQUIRE(B > 0, "%s: bad shape B=%d", name, B);
+  KPF_REQUIRE(cfg->iters >= 0 && cfg->iters <= 64, "%s: iters=%d outside [0, 64]", name, cfg->iters);
+  KPF_REQUIRE(cfg->mu >= 0.f && cfg->nu >= 0.f && isfinite(cfg->mu) && isfinite(cfg->nu), "%s: bad damping mu=%g nu=%g", name, cfg->mu, cfg->nu);
+  KPF_REQUIRE(cfg->lambda_verts >= 0.f && isfinite(cfg->lambda_verts), "%s: lambda_verts=%g is negative or not finite", name, cfg->lambda_verts);
+  unsigned seen = 0;
+  for (int i = 0; i < 21; ++i) {
+    KPF_REQUIRE(cfg->joint_map[i] >= 0 && cfg->joint_map[i] < 21, "%s: joint_map[%d]=%d outside [0, 21)", name, i, cfg->joint_map[i]);
+    seen |= 1u << cfg->joint_map[i];
+  }
+  KPF_REQUIRE(seen == (1u << 21) - 1, "%s: joint_map is not a permutation", name);
+  kpf_mano_fit_gn_cfg c;
+  c.iters = cfg->iters;
+  c.mu = cfg->mu; c.nu = cfg->nu;
+  c.lambda_shape = cfg->lambda_shape; c.lambda_pose = cfg->lambda_pose;
+  c.init_trans = cfg->init_trans;
+  for (int i = 0; i < 21; ++i) c.joint_map[i] = cfg->joint_map[i];
+  const ManoModel m{shapedirs_t, posedirs_t, v_template, j_regressor, skin_weights, hands_mean};
+  if (!vert_target) {  // no vertex term: the joint fit's kernel, its bits
+    ManoGnArgs a;
+    a.target = target; a.weight = weight;
+    a.m = m;
+    a.c = c;
+    a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
+    a.status = status; a.history = history; a.jacobian = jacobian;
+    a.res_ld = 4; a.hist_ld = 2;
+    hipLaunchKernelGGL(mano_fit_gn_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return kpf_check_launch(name);
+  }
+  ManoMeshGnArgs a;
+  a.target = target; a.weight = weight; a.vtarget = vert_target; a.vweight = vert_weight;
+  a.m = m;
+  a.c = c;
+  a.lambda_verts = cfg->lambda_verts;
+  a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
+  a.status = status; a.history = history; a.jacobian = jacobian; a.vjacobian = vert_jacobian;
+  hipLaunchKernelGGL(mano_fit_mesh_gn_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   return kpf_check_launch(name);
 }
 

@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 28  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 29  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -67,6 +67,10 @@ class ManoFitMeshCfg(C.Structure):  # kpf_mano_fit_mesh_cfg (include/kpf.h): kpf
 
 class ManoFitGnCfg(C.Structure):  # kpf_mano_fit_gn_cfg (include/kpf.h)
     _fields_ = [("iters", C.c_int)] + [(n, C.c_float) for n in "mu nu lambda_shape lambda_pose".split()] + [("init_trans", C.c_int), ("joint_map", C.c_int * 21)]
+
+
+class ManoFitMeshGnCfg(C.Structure):  # kpf_mano_fit_mesh_gn_cfg (include/kpf.h): kpf_mano_fit_gn_cfg's fields, then lambda_verts
+    _fields_ = ManoFitGnCfg._fields_ + [("lambda_verts", C.c_float)]
 
 
 class WgradPlan(C.Structure):  # kpf_wgrad_plan (include/kpf.h)
@@ -141,6 +145,7 @@ _SIGS = {
     "kpf_mano_fit_f32": [_P] * 8 + [C.POINTER(ManoFitCfg)] + [_P] * 8 + [C.c_int, _P],
     "kpf_mano_fit_mesh_f32": [_P] * 10 + [C.POINTER(ManoFitMeshCfg)] + [_P] * 8 + [C.c_int, _P],
     "kpf_mano_fit_gn_f32": [_P] * 8 + [C.POINTER(ManoFitGnCfg)] + [_P] * 10 + [C.c_int, _P],
+    "kpf_mano_fit_mesh_gn_f32": [_P] * 10 + [C.POINTER(ManoFitMeshGnCfg)] + [_P] * 11 + [C.c_int, _P],
     "kpf_mano_assoc_f32": [_P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, _P],
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],

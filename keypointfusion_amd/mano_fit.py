@@ -16,7 +16,8 @@ every vertex the weighted centroid of its points (kpf_mano_assoc_f32; sum_n w_n 
 atomics), and fit_cloud alternates the two on the depth points the preprocessing already sampled (cloud_mm).  DESIGN.md 4.12.
 
 fit_gn is the joint fit by damped Gauss-Newton (kpf_mano_fit_gn_f32): the same objective and state, 8 iterations where Adam takes 50, one
-launch; fit_cloud(joint_solver="gn") uses it for its first stage."""
+launch; fit_cloud(joint_solver="gn") uses it for its first stage.  fit_mesh_gn is the same for the fit with the vertex term (kpf_mano_fit_mesh_gn_f32,
+DESIGN.md 4.14); fit_cloud(cloud_solver="gn") uses it for its vertex rounds."""
 import torch
 
 from . import lib as L
@@ -44,7 +45,8 @@ class ManoFitter:
                                 float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
         self.mesh_cfg = L.ManoFitMeshCfg(*[getattr(self.cfg, n) for n, _ in L.ManoFitCfg._fields_], 1.0)
         self.gn_cfg = L.ManoFitGnCfg(8, 0.1, 1e-2, float(lambda_shape), float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
-        self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs = {}, {}, {}, {}
+        self.mesh_gn_cfg = L.ManoFitMeshGnCfg(*[getattr(self.gn_cfg, n) for n, _ in L.ManoFitGnCfg._fields_], 1.0)
+        self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs, self._mesh_gn_bufs = {}, {}, {}, {}, {}
 
     def new_state(self, B):
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
@@ -191,6 +193,65 @@ class ManoFitter:
         return {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
                 "residual": o["residual"], "status": o["status"]}
 
+    def fit_mesh_gn(self, joints_mm=None, weight=None, vert_target=None, vert_weight=None, state=None, init_trans=True, lambda_verts=1.0, iters=None,
+                    mu=0.1, nu=1e-2, jacobian=False):
+        """fit_mesh by damped Gauss-Newton (kpf_mano_fit_mesh_gn_f32): fit_gn's iteration over the 63 joint rows and the 2334 vertex rows
+        sqrt(lambda_verts u_v / sum u) (V_v + t - c_v), with fit_mesh's arguments, init_trans rule and status bits 1 and 2, and fit_gn's bit 4.  iters=None: 8;
+        0 <= iters <= 64.  Without vert_target the launch is fit_gn's kernel and its bits.
+
+        Returns what fit_mesh returns plus history [B, iters + 1, 2] (the mean weighted joint and vertex distance in mm before iteration 1 and after each
+        iteration) and, with jacobian=True, jacobian [B, 63, 61] (as fit_gn) and vert_jacobian [B, 2334, 61]: the unweighted d (V_v + t) / d p of the state
+        on entry, row v * 3 + d (zeros without a vertex term).  Own output tensors per batch size (and per iters, for history); one launch, no host wait."""
+        if (vert_target is None) != (vert_weight is None):
+            raise ValueError("vert_target and vert_weight go together")
+        if joints_mm is None and vert_target is None:
+            raise ValueError("fit_mesh_gn needs joints_mm or vert_target")
+        B = (joints_mm if joints_mm is not None else vert_target).shape[0]
+        if joints_mm is not None:
+            self._check(joints_mm, (B, 21, 3), "joints_mm")
+        if weight is not None:
+            self._check(weight, (B, 21), "weight")
+        if vert_target is not None:
+            self._check(vert_target, (B, 778, 3), "vert_target")
+            self._check(vert_weight, (B, 778), "vert_weight")
+        n = 8 if iters is None else int(iters)
+        if not 0 <= n <= 64:
+            raise ValueError("fit_mesh_gn takes 0 <= iters <= 64, not %d" % n)
+        if B not in self._mesh_gn_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            self._mesh_gn_bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 4),
+                                     "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B), "history": {}}
+        o = self._mesh_gn_bufs[B]
+        if n not in o["history"]:
+            o["history"][n] = torch.empty(B, n + 1, 2, device=self.device, dtype=torch.float32)
+        if jacobian and "jacobian" not in o:
+            o["jacobian"] = torch.empty(B, 63, 61, device=self.device, dtype=torch.float32)
+            o["vert_jacobian"] = torch.zeros(B, 2334, 61, device=self.device, dtype=torch.float32)
+        hist = o["history"][n]
+        if state is None:
+            state = o["state"]
+            for s in state:
+                s.zero_()
+        pose, betas, trans = state
+        self._check_state(state, B)
+        c = self.mesh_gn_cfg
+        c.iters, c.mu, c.nu, c.init_trans, c.lambda_verts = n, float(mu), float(nu), 1 if init_trans else 0, float(lambda_verts)
+        if jacobian and vert_target is None:
+            o["vert_jacobian"].zero_()
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_fit_mesh_gn_f32(ptr(joints_mm), ptr(weight), ptr(vert_target), ptr(vert_weight), *[m.data_ptr() for m in self.model],
+                                                      L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
+                                                      o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(),
+                                                      hist.data_ptr(), o["jacobian"].data_ptr() if jacobian else None,
+                                                      o["vert_jacobian"].data_ptr() if jacobian and vert_target is not None else None, B,
+                                                      torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_mesh_gn_f32")
+        out = {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
+               "residual": o["residual"], "status": o["status"], "history": hist}
+        if jacobian:
+            out["jacobian"], out["vert_jacobian"] = o["jacobian"], o["vert_jacobian"]
+        return out
+
     def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0):
         """points_mm [B, N, 3] (camera-space mm, 1 <= N <= 4096), verts3d [B, 778, 3] (a fit's), point_weight [B, N] >= 0 or None (= ones), max_dist: the gate
         in mm (float("inf"): none) -> idx [B, N] int32 (each point's nearest vertex, -1 if its weight is 0, a coordinate is not finite or the vertex is
@@ -217,14 +278,18 @@ class ManoFitter:
         return dict(o)
 
     def fit_cloud(self, joints_mm, points_mm, weight=None, point_weight=None, state=None, init_trans=True, rounds=3, iters_cloud=None, max_dist=20.0,
-                  lambda_verts=1.0, joint_solver="adam"):
+                  lambda_verts=1.0, joint_solver="adam", cloud_solver="adam"):
         """Joints, then the depth points: one fit on the joints, then `rounds` times associate followed by fit_mesh (warm start, init_trans=False, the joints
         kept in the objective, iters_cloud iterations each; None = the fitter's), and last one associate on the final vertices: 2 * rounds + 2 launches and no
         host wait.  Returns the last fit's outputs plus cloud_before and cloud_after (the stats of the first and the last association: matched points and
         their mean distance to the mesh in mm) and the last association's idx, vert_target and vert_weight.  rounds=0 is fit plus one associate.
-        joint_solver: "adam" (fit) or "gn" (fit_gn with its defaults) for the first stage; the vertex rounds are Adam either way."""
+        joint_solver: "adam" (fit) or "gn" (fit_gn with its defaults) for the first stage.  cloud_solver: "adam" (fit_mesh) or "gn" (fit_mesh_gn; iters_cloud=None
+        is then 2 -- the alternation limits the chain, not the solver, so the rounds should be many and short: rounds=6) for the vertex rounds.  The two are
+        independent; on the synthetic hand the Adam joint stage is the better start for the cloud."""
         if joint_solver not in ("adam", "gn"):
             raise ValueError("joint_solver must be \"adam\" or \"gn\", not %r" % (joint_solver,))
+        if cloud_solver not in ("adam", "gn"):
+            raise ValueError("cloud_solver must be \"adam\" or \"gn\", not %r" % (cloud_solver,))
         if joint_solver == "gn":
             out = self.fit_gn(joints_mm, weight, state=state, init_trans=init_trans)
         else:
@@ -234,8 +299,12 @@ class ManoFitter:
         for r in range(int(rounds)):
             a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0)
             first = a if first is None else first
-            out = self.fit_mesh(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
-                                iters=iters_cloud)
+            if cloud_solver == "gn":
+                out = self.fit_mesh_gn(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
+                                       iters=2 if iters_cloud is None else iters_cloud)
+            else:
+                out = self.fit_mesh(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
+                                    iters=iters_cloud)
         last = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=2)
         out = dict(out)
         out.update(cloud_before=(last if first is None else first)["stats"], cloud_after=last["stats"], idx=last["idx"], vert_target=last["vert_target"],

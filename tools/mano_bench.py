@@ -2,7 +2,8 @@
 hand model as torch ops under autograd (layer="torch") against heads_train.ManoLayerHip (layer="hip"), and the joint fit mano_fit.ManoFitter at B = 1 and 32
 with iters = 10 and 50; the Gauss-Newton fit fit_gn at B = 1 and 32 -- ms per call at its default 8 iterations, at 1 and 0, ms per
 iteration = (8 - 1) / 7, the residual and history after, Adam's 10 / 50-iteration figures of the same run beside them (records fit_gn_B1, fit_gn_B32); and the fit with a vertex term, the association of 1024 points and the chain fit_cloud (3 rounds) at B = 1 and 32
-with iters = 50.  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
+with iters = 50; the Gauss-Newton mesh fit fit_mesh_gn at 0, 1, 2 and 8 iterations and the chain with six Gauss-Newton rounds of two
+iterations, Adam's figures of the same run beside them (records fit_mesh_gn_B1 / _B32, fit_cloud_gn_B1 / _B32).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
     python tools/mano_bench.py --reps 50
@@ -92,6 +93,22 @@ def main():
         rec["fit_cloud_ms_B%d_iters50_rounds3" % B] = _timed(lambda: fitter.fit_cloud(y, pts), args.reps, torch)
         out = fitter.fit_cloud(y, pts)
         rec["fit_cloud_mm_B%d_iters50_rounds3" % B] = [float(out["cloud_before"][:, 1].mean()), float(out["cloud_after"][:, 1].mean())]
+        # the Gauss-Newton mesh fit on the same targets, and the chain with Gauss-Newton rounds (6 rounds of 2 iterations) beside Adam's
+        ms = {n: _timed(lambda: fitter.fit_mesh_gn(y, None, vt, u, iters=n), args.reps, torch) for n in (0, 1, 2, 8)}
+        out = fitter.fit_mesh_gn(y, None, vt, u)
+        rec["fit_mesh_gn_B%d" % B] = {"ms_iters0": ms[0], "ms_iters1": ms[1], "ms_iters2": ms[2], "ms_iters8": ms[8], "ms_per_iteration": (ms[8] - ms[1]) / 7,
+                                      "residual_mm": [float(v) for v in out["residual"].mean(0)],
+                                      "history_mm": [[float(v) for v in row] for row in out["history"].mean(0)],
+                                      "status": sorted(set(int(v) for v in out["status"])),
+                                      "adam_ms_iters50": rec["fit_mesh_ms_B%d_iters50" % B],
+                                      "adam_residual_mm_iters50": rec["fit_mesh_residual_mm_B%d_iters50" % B]}
+        gn = dict(rounds=6, iters_cloud=2, cloud_solver="gn")
+        cloud_ms = _timed(lambda: fitter.fit_cloud(y, pts, **gn), args.reps, torch)
+        out = fitter.fit_cloud(y, pts, **gn)
+        rec["fit_cloud_gn_B%d" % B] = {"ms_rounds6_iters2": cloud_ms, "cloud_mm": [float(out["cloud_before"][:, 1].mean()), float(out["cloud_after"][:, 1].mean())],
+                                       "status": sorted(set(int(v) for v in out["status"])),
+                                       "adam_ms_rounds3_iters50": rec["fit_cloud_ms_B%d_iters50_rounds3" % B],
+                                       "adam_cloud_mm_rounds3_iters50": rec["fit_cloud_mm_B%d_iters50_rounds3" % B]}
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:
