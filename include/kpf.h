@@ -422,6 +422,37 @@ int kpf_mano_fit_mesh_gn_f32(const float* target /*[B][21][3] mm, or NULL*/, con
 int kpf_mano_assoc_f32(const float* points, const float* point_weight, const float* verts, float max_dist2,
     int* idx, float* vert_target, float* vert_weight, float* stats, int B, int N, void* stream);
 
+/* Area-weighted vertex normals (ABI 30), one workgroup per hand, no atomics.  verts [B][778][3]; faces [F][3] int (the model's th_faces), 1 <= F <= 2048;
+ * sign +1 or -1 (-1: a mirrored hand or the other winding).  Anything else is refused and nothing is written.  A face with an index outside 0..777 is
+ * skipped.  Per face e1 = v1 - v0, e2 = v2 - v0, fn = e1 x e2 (fn.x = e1.y*e2.z - e1.z*e2.y, ...; unnormalised); per vertex S = the sum of fn over the
+ * faces in ascending order, once for each corner of the face that is the vertex; len = sqrt((S.x*S.x + S.y*S.y) + S.z*S.z); normals [B][778][3] =
+ * sign * (S / len) if len > 0 and finite, else (0, 0, 0) -- a vertex in no face, a cancelling fan, a NaN vertex's neighbourhood.  Every operation is
+ * individually rounded (no fma): a numpy-fp32 restatement gives the same bits. */
+int kpf_mano_normals_f32(const float* verts /*[B][778][3] mm*/, const int* faces /*[F][3]*/, int F, float sign /*+1 or -1*/,
+    float* normals /*[B][778][3]*/, int B, void* stream);
+
+/* kpf_mano_assoc_f32 over the vertices that face the camera (ABI 30): its N limits, weights, gate, argmin rule, centroid rule and rounding.  The camera is
+ * the origin of the frame.  normals [B][778][3] (kpf_mano_normals_f32's); 0 <= facing_min < 1.  visible [B][778]: 1 iff n_v is finite and not all-zero and
+ * (n.x*V.x + n.y*V.y) + n.z*V.z < -(facing_min * sqrt((V.x*V.x + V.y*V.y) + V.z*V.z)).  The argmin runs over the visible vertices only (ascending,
+ * strict <); with no visible vertex every idx is -1.  stats [B][4]: the matched points, their mean distance to their vertex, the mean of
+ * |(n_i.x*d.x + n_i.y*d.y) + n_i.z*d.z| with d = p - V_i over the matched points in ascending order, the number of visible vertices. */
+int kpf_mano_assoc_vis_f32(const float* points, const float* point_weight, const float* verts, const float* normals /*[B][778][3]*/,
+    float max_dist2, float facing_min /*0 <= . < 1*/, int* idx, float* vert_target, float* vert_weight,
+    int* visible /*[B][778]*/, float* stats /*[B][4]*/, int B, int N, void* stream);
+
+/* kpf_mano_fit_mesh_gn_f32 with a point-to-plane vertex term (ABI 30).  vert_normal [B][778][3], fixed for the launch, or NULL: then this is
+ * kpf_mano_fit_mesh_gn_f32, the same kernel and bits.  With normals a vertex term is required, and each vertex contributes ONE row
+ *   sqrt(lambda_verts u_v / sv) n_v^T (V_v + t - c_v),  Jacobian n_v^T d (V_v + t) / d p
+ * (against the association's centroid: sum w_n (n.(V - p_n))^2 and W (n.(V - c))^2 have the same gradient).  Joint rows, Lambda, damping, solve,
+ * init_trans and status bits 1, 2, 4 are kpf_mano_fit_mesh_gn_f32's; bit 2 is also set by a non-finite normal under a positive weight; a zero normal
+ * under a positive weight gives a zero row and still counts in sv.  Column 1 of history and columns 2, 3 of residual report the mean weighted
+ * |n_v . (V_v + t - c_v)|.  jacobian / vert_jacobian are unchanged (unweighted, unprojected). */
+int kpf_mano_fit_mesh_gn_plane_f32(const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+    const float* vert_normal /*[B][778][3] or NULL*/, const float* shapedirs_t, const float* posedirs_t, const float* v_template,
+    const float* j_regressor, const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_gn_cfg* cfg,
+    float* pose_aa, float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual /*[B][4]*/, int* status,
+    float* history, float* jacobian, float* vert_jacobian, int B, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Reduced-precision path (BASELINE configs[2] bf16, configs[4] fp16): same operators on 16-bit NHWC activations.  `dtype` is
  * KPF_DT_BF16 or KPF_DT_F16; LayerNorm / bias / layer-scale parameters and the depthwise taps stay fp32.
@@ -1063,7 +1094,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 29
+#define KPF_ABI_VERSION 30
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

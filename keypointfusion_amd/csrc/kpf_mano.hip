@@ -6,6 +6,9 @@
 //   kpf_mano_fit_gn_f32    the joint fit by damped Gauss-Newton: forward-mode Jacobian, normal matrix and Cholesky solve in LDS (its own kernel, further down)
 //   kpf_mano_fit_mesh_gn_f32  the Gauss-Newton fit with the vertex term: 2334 more rows, J^T J on the fp32 MFMA (its own kernel, after the joint fit's)
 //   kpf_mano_assoc_f32     depth points -> nearest vertex, per-vertex centroid and weight: the vertex targets of the fit above (its own kernel, further down)
+//   kpf_mano_normals_f32   area-weighted vertex normals of the fitted mesh from the model's faces (its own kernel, after the association's)
+//   kpf_mano_assoc_vis_f32 the association over the vertices that face the camera, with the point-to-plane distance among its stats
+//   kpf_mano_fit_mesh_gn_plane_f32  the Gauss-Newton mesh fit with one point-to-plane row per vertex: the second instantiation of that kernel
 // The fits share the stage functions below; the forward's arithmetic is the text it had in kpf_aux.hip (tests/test_heads_gpu.py pins its bits).
 // Every reduction has a fixed order (wave butterflies, then a fixed sum over the four waves) and there are no atomics: a replay is bit-identical and a
 // sample's bits do not depend on B or on its position in the batch.
@@ -1338,8 +1341,11 @@ struct ManoMeshGnArgs {
 
 // Chunk ch's 48 rows into x.chunk (vjac: null, or the unweighted rows of every vertex, [2334][61]).  All 256 threads; ends with a barrier, and its inner
 // barrier also separates the previous chunk's product from this chunk's rows.
+// PLANE: a vertex contributes one row, its three contracted with the normal n_v (nrm: this sample's [778][3] in global memory, 48 components per chunk);
+// the other two of its rows are zeros, so that the chunk, the product and the two-level sum keep their shape and order.  vjac stays unprojected.
+template <bool PLANE>
 __device__ __forceinline__ void mano_gn_vertex_chunk(const ManoModel& m, const ManoLds& s, const ManoFitLds& f, ManoGnVertLds& x, float lambda, int ch, int t,
-                                                     float* vjac) {
+                                                     float* vjac, const float* nrm = nullptr) {
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, base = ch * GN_CV;
   int vq[GN_VB];  // this wave's vertices; past the last one: the last one's loads, and zero rows
 #pragma unroll
@@ -1395,28 +1401,56 @@ __device__ __forceinline__ void mano_gn_vertex_chunk(const ManoModel& m, const M
     const float scale = on ? sqrtf(lambda * u / f.sv) : 0.0f;
     const float px = s.v[v * 3 + 0], py = s.v[v * 3 + 1], pz = s.v[v * 3 + 2];
     const float d0 = moves ? x.dp[lane][row0 + 0] : 0.f, d1 = moves ? x.dp[lane][row0 + 1] : 0.f, d2 = moves ? x.dp[lane][row0 + 2] : 0.f;
+    float pl = 0.f;  // PLANE: n_v . (this lane's three entries)
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       const float o = (dT[q][r * 4 + 0] * px + dT[q][r * 4 + 1] * py + dT[q][r * 4 + 2] * pz + dT[q][r * 4 + 3]) +
                       (T[r * 4 + 0] * d0 + T[r * 4 + 1] * d1 + T[r * 4 + 2] * d2);
       const float val = o * 1000.0f + (lane - 58 == r ? 1.0f : 0.0f);
       if (vjac && valid && lane < GN_P) vjac[(long)(v * 3 + r) * GN_P + lane] = val;
-      float e = 0.f;
-      if (on && lane < GN_P) e = scale * val;
-      else if (on && lane == GN_P) e = scale * (x.vm[v * 3 + r] + f.P[58 + r] - x.c[v * 3 + r]);
-      x.chunk[(row0 + r) * GN_CLD + lane] = e;
+      if constexpr (PLANE) {
+        float e = 0.f;
+        if (on && lane < GN_P) e = val;
+        else if (on && lane == GN_P) e = x.vm[v * 3 + r] + f.P[58 + r] - x.c[v * 3 + r];
+        pl = fmaf(on ? nrm[v * 3 + r] : 0.0f, e, pl);  // a normal under weight 0 is selected out, never multiplied
+        if (r > 0) x.chunk[(row0 + r) * GN_CLD + lane] = 0.0f;
+      } else {
+        float e = 0.f;
+        if (on && lane < GN_P) e = scale * val;
+        else if (on && lane == GN_P) e = scale * (x.vm[v * 3 + r] + f.P[58 + r] - x.c[v * 3 + r]);
+        x.chunk[(row0 + r) * GN_CLD + lane] = e;
+      }
     }
+    if constexpr (PLANE) x.chunk[row0 * GN_CLD + lane] = on ? scale * pl : 0.0f;
   }
   __syncthreads();
 }
 
-__device__ __forceinline__ float mano_mesh_gn_vert_distance(ManoFitLds& f, const ManoGnVertLds& x, int t) {
-  float in = mano_vert_distance(x.c, x.u, x.vm, &f.P[58], t), sum;
+// mano_vert_distance along the normal: sum u_v |n_v . (V_v + t - c_v)|
+__device__ __forceinline__ float mano_vert_plane_distance(const float* c, const float* u, const float* vm, const float* nrm, const float* tr, int t) {
+  float sum = 0.f;
+  for (int v = t; v < NV; v += 256) {
+    const float w = u[v];
+    if (!(w > 0.0f)) continue;
+    const float r0 = vm[v * 3 + 0] + tr[0] - c[v * 3 + 0], r1 = vm[v * 3 + 1] + tr[1] - c[v * 3 + 1], r2 = vm[v * 3 + 2] + tr[2] - c[v * 3 + 2];
+    sum = fmaf(w, fabsf(nrm[v * 3 + 0] * r0 + nrm[v * 3 + 1] * r1 + nrm[v * 3 + 2] * r2), sum);
+  }
+  return sum;
+}
+
+template <bool PLANE>
+__device__ __forceinline__ float mano_mesh_gn_vert_distance(ManoFitLds& f, const ManoGnVertLds& x, const float* nrm, int t) {
+  float in, sum;
+  if constexpr (PLANE) in = mano_vert_plane_distance(x.c, x.u, x.vm, nrm, &f.P[58], t);
+  else in = mano_vert_distance(x.c, x.u, x.vm, &f.P[58], t);
   mano_block_sum<1>(f, t, &in, &sum);
   return f.sv > 0.0f ? sum / f.sv : 0.0f;
 }
 
-__global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a) {
+// PLANE: the vertex term is point-to-plane (one row per vertex, see mano_gn_vertex_chunk).  Without it the kernel is the mesh fit as it was, statement by
+// statement.  vnormal [B][778][3], fixed for the launch, is an argument of its own so that the arguments of the instantiation without it stay what they were.
+template <bool PLANE>
+__global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a, const float* vnormal) {
   __shared__ ManoLds s;
   __shared__ ManoFitLds f;
   __shared__ ManoGnLds n;
@@ -1424,6 +1458,7 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
   const int b = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const float* vc = a.vtarget + (long)b * NC;
   const float* vu = a.vweight + (long)b * NV;
+  const float* vn = PLANE ? vnormal + (long)b * NC : nullptr;
   // the state, the targets and the status: the mesh fit's rules
   if (t < 48) f.P[t] = a.pose[(long)b * 48 + t];
   else if (t < 58) f.P[t] = a.betas[(long)b * 10 + (t - 48)];
@@ -1447,6 +1482,10 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
   {
     float in[2];
     mano_vert_weights(vc, vu, t, in);
+    if constexpr (PLANE) {  // a normal under a positive weight that is not finite counts as such a target does
+      for (int v = t; v < NV; v += 256)
+        if (vu[v] > 0.0f && !(isfinite(vn[v * 3 + 0]) && isfinite(vn[v * 3 + 1]) && isfinite(vn[v * 3 + 2]))) in[1] += 1.0f;
+    }
     mano_block_sum<2>(f, t, in, vstat);
   }
   __syncthreads();
@@ -1514,7 +1553,7 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
     __syncthreads();
   }
   {
-    const float dv = mano_mesh_gn_vert_distance(f, x, t);
+    const float dv = mano_mesh_gn_vert_distance<PLANE>(f, x, vn, t);
     if (t == 0) {
       a.residual[(long)b * 4 + 0] = mano_fit_residual(f);
       a.residual[(long)b * 4 + 2] = dv;
@@ -1523,7 +1562,7 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
   if (iters == 0 && (jac || vjac)) {  // only evaluates: the entry Jacobians are still reported
     mano_gn_tangent<true>(a.m, s, f, n, t, jac, &x);
     if (vjac)
-      for (int ch = 0; ch < GN_CHUNKS; ++ch) mano_gn_vertex_chunk(a.m, s, f, x, a.lambda_verts, ch, t, vjac);
+      for (int ch = 0; ch < GN_CHUNKS; ++ch) mano_gn_vertex_chunk<PLANE>(a.m, s, f, x, a.lambda_verts, ch, t, vjac, vn);
   }
   int slot[GN_SLOTS];
   mano_gn_slots(t, slot);
@@ -1531,7 +1570,7 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
   for (int it = 1; it <= iters; ++it) {
     if (it > 1) mano_fit_eval<true>(a.m, s, f, x.vm, t);
     if (hist) {
-      const float dv = mano_mesh_gn_vert_distance(f, x, t);
+      const float dv = mano_mesh_gn_vert_distance<PLANE>(f, x, vn, t);
       if (t == 0) {
         hist[(it - 1) * 2 + 0] = mano_fit_residual(f);
         hist[(it - 1) * 2 + 1] = dv;
@@ -1555,7 +1594,7 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) acc[tj] = part[tj];
     for (int ch = 0; ch < GN_CHUNKS; ++ch) {
-      mano_gn_vertex_chunk(a.m, s, f, x, a.lambda_verts, ch, t, it == 1 ? vjac : nullptr);
+      mano_gn_vertex_chunk<PLANE>(a.m, s, f, x, a.lambda_verts, ch, t, it == 1 ? vjac : nullptr, vn);
       const float* rows = x.chunk + (lane >> 4) * GN_CLD + (lane & 15);
 #pragma unroll
       for (int tj = 0; tj < 4; ++tj) part[tj] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1595,7 +1634,7 @@ __global__ __launch_bounds__(256) void mano_fit_mesh_gn_kernel(ManoMeshGnArgs a)
   }
   if (done > 0) mano_fit_eval<true>(a.m, s, f, x.vm, t);
   {
-    const float dv = mano_mesh_gn_vert_distance(f, x, t);
+    const float dv = mano_mesh_gn_vert_distance<PLANE>(f, x, vn, t);
     if (t == 0) {
       const float res = mano_fit_residual(f);
       a.residual[(long)b * 4 + 1] = res;
@@ -1712,6 +1751,224 @@ __global__ __launch_bounds__(256) void mano_assoc_kernel(ManoAssocArgs a) {
       }
     a.stats[(long)b * 2 + 0] = (float)cnt;
     a.stats[(long)b * 2 + 1] = cnt > 0 ? __fdiv_rn(sum, (float)cnt) : 0.0f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Vertex normals: n_v = sign * normalize(sum over the corners of the faces at v of (v1 - v0) x (v2 - v0)) -- unnormalised face normals, so
+// area-weighted.  One workgroup per hand; vertices, faces and face normals in LDS.  A thread owns vertices t, t + 256, ... and scans the faces in ascending
+// order: no atomics, and the sum's order is the face order.  Every operation individually rounded, as the association: tests/mano_surface_cases.py::
+// normals_host gives the same bits.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int NORMALS_MAXF = 2048;
+
+struct ManoNormalsArgs {
+  const float* verts;  // [B][778][3]
+  const int* faces;    // [F][3]
+  int F;
+  float sign;
+  float* normals;      // [B][778][3]
+};
+
+struct ManoNormalsLds {
+  float v[NC];
+  int f[NORMALS_MAXF * 3];     // a face with an index outside 0..777: its first index is -1
+  float fn[NORMALS_MAXF * 3];
+};
+
+__global__ __launch_bounds__(256) void mano_normals_kernel(ManoNormalsArgs a) {
+#pragma clang fp contract(off)
+  __shared__ ManoNormalsLds s;
+  const int b = blockIdx.x, t = threadIdx.x, F = a.F;
+  for (int c = t; c < NC; c += 256) s.v[c] = a.verts[(long)b * NC + c];
+  for (int c = t; c < F * 3; c += 256) s.f[c] = a.faces[c];
+  __syncthreads();
+  for (int k = t; k < F; k += 256) {
+    const int i0 = s.f[k * 3 + 0], i1 = s.f[k * 3 + 1], i2 = s.f[k * 3 + 2];
+    const bool in = i0 >= 0 && i0 < NV && i1 >= 0 && i1 < NV && i2 >= 0 && i2 < NV;
+    float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+    if (in) {
+      const float ax = __fsub_rn(s.v[i1 * 3 + 0], s.v[i0 * 3 + 0]), ay = __fsub_rn(s.v[i1 * 3 + 1], s.v[i0 * 3 + 1]), az = __fsub_rn(s.v[i1 * 3 + 2], s.v[i0 * 3 + 2]);
+      const float bx = __fsub_rn(s.v[i2 * 3 + 0], s.v[i0 * 3 + 0]), by = __fsub_rn(s.v[i2 * 3 + 1], s.v[i0 * 3 + 1]), bz = __fsub_rn(s.v[i2 * 3 + 2], s.v[i0 * 3 + 2]);
+      n0 = __fsub_rn(__fmul_rn(ay, bz), __fmul_rn(az, by));
+      n1 = __fsub_rn(__fmul_rn(az, bx), __fmul_rn(ax, bz));
+      n2 = __fsub_rn(__fmul_rn(ax, by), __fmul_rn(ay, bx));
+    }
+    s.fn[k * 3 + 0] = n0;
+    s.fn[k * 3 + 1] = n1;
+    s.fn[k * 3 + 2] = n2;
+    if (!in) s.f[k * 3 + 0] = -1;  // skipped below (only this thread has read face k so far)
+  }
+  __syncthreads();
+  float S[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // vertices t, t + 256, t + 512, (t + 768)
+  // eight faces' indices are read before any is looked at (k0 + u < 2048 stays inside s.f; a slot past F holds nothing and is masked), so the 24 LDS reads
+  // of a step are in flight together; a hit -- six or so per vertex in the whole scan -- is the only branch
+  for (int k0 = 0; k0 < F; k0 += 8) {
+    int ix[8][3];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) ix[u][c] = s.f[(k0 + u) * 3 + c];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int k = k0 + u;
+      const bool live = k < F && ix[u][0] >= 0;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int i = ix[u][c];
+        if (!(live && (i & 255) == t)) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if ((i >> 8) == q) {
+            S[q][0] = __fadd_rn(S[q][0], s.fn[k * 3 + 0]);
+            S[q][1] = __fadd_rn(S[q][1], s.fn[k * 3 + 1]);
+            S[q][2] = __fadd_rn(S[q][2], s.fn[k * 3 + 2]);
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int v = t + q * 256;
+    if (v >= NV) continue;
+    const float len2 = __fadd_rn(__fadd_rn(__fmul_rn(S[q][0], S[q][0]), __fmul_rn(S[q][1], S[q][1])), __fmul_rn(S[q][2], S[q][2]));
+    const float len = sqrtf(len2);  // the correctly rounded root (see mano_assoc_kernel)
+    const bool ok = len > 0.0f && isfinite(len);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a.normals[((long)b * NV + v) * 3 + d] = ok ? __fmul_rn(a.sign, __fdiv_rn(S[q][d], len)) : 0.0f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Association over the vertices that face the camera: mano_assoc_kernel with a visibility flag per vertex.  The camera is the origin of
+// the frame, so vertex v is visible iff its normal is finite, not all-zero and n_v . V_v < -facing_min |V_v|.  The argmin runs over the visible vertices
+// only (compacted first, in ascending order); everything else -- gate, weights, centroids, rounding, orders -- is the association's.  stats [B][4]: matched points, their mean distance to their
+// vertex, their mean |n_i . (p - V_i)|, the visible vertices.  tests/mano_surface_cases.py::associate_vis_host gives the same bits.
+// ---------------------------------------------------------------------------------------------------------------
+struct ManoAssocVisArgs {
+  const float *points, *pweight, *verts, *normals;  // [B][N][3], [B][N] or null, [B][778][3], [B][778][3]
+  float max_dist2, facing_min;
+  int N;
+  int *idx, *visible;                               // [B][N], [B][778]
+  float *vtarget, *vweight, *stats;                 // [B][778][3], [B][778], [B][4]
+};
+
+struct ManoAssocVisLds {
+  float v[NC], n[NC];
+  int vis[NV];
+  float cv[NC];             // the visible vertices, compacted in ascending order: the argmin's loop is as long as their number
+  int cidx[NV], nvis;       // their indices
+  int idx[ASSOC_MAXN];
+  float dist[ASSOC_MAXN];   // a matched point's distance to its vertex, mm
+  float plane[ASSOC_MAXN];  // and to that vertex's tangent plane
+};
+
+__global__ __launch_bounds__(256) void mano_assoc_vis_kernel(ManoAssocVisArgs a) {
+#pragma clang fp contract(off)
+  __shared__ ManoAssocVisLds s;
+  const int b = blockIdx.x, t = threadIdx.x, N = a.N;
+  const float* P = a.points + (long)b * N * 3;
+  const float* PW = a.pweight ? a.pweight + (long)b * N : nullptr;
+  for (int c = t; c < NC; c += 256) {
+    s.v[c] = a.verts[(long)b * NC + c];
+    s.n[c] = a.normals[(long)b * NC + c];
+  }
+  __syncthreads();
+  for (int v = t; v < NV; v += 256) {
+    const float nx = s.n[v * 3 + 0], ny = s.n[v * 3 + 1], nz = s.n[v * 3 + 2];
+    const float vx = s.v[v * 3 + 0], vy = s.v[v * 3 + 1], vz = s.v[v * 3 + 2];
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(nx, vx), __fmul_rn(ny, vy)), __fmul_rn(nz, vz));
+    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)), __fmul_rn(vz, vz)));
+    const bool some = isfinite(nx) && isfinite(ny) && isfinite(nz) && !(nx == 0.0f && ny == 0.0f && nz == 0.0f);
+    const int vis = (some && dot < -__fmul_rn(a.facing_min, len)) ? 1 : 0;
+    s.vis[v] = vis;
+    a.visible[(long)b * NV + v] = vis;
+  }
+  __syncthreads();
+  if (t < 64) {  // wave 0 compacts the visible vertices, 64 at a time, by a ballot: the order stays ascending
+    int count = 0;
+    for (int base = 0; base < NV; base += 64) {
+      const int v = base + t;
+      const bool on = v < NV && s.vis[v] != 0;
+      const unsigned long long mask = __ballot(on);
+      if (on) {
+        const int pos = count + __popcll(mask & ((1ull << t) - 1ull));
+        s.cidx[pos] = v;
+        s.cv[pos * 3 + 0] = s.v[v * 3 + 0];
+        s.cv[pos * 3 + 1] = s.v[v * 3 + 1];
+        s.cv[pos * 3 + 2] = s.v[v * 3 + 2];
+      }
+      count += __popcll(mask);
+    }
+    if (t == 0) s.nvis = count;
+  }
+  __syncthreads();
+  const int nvis = s.nvis;
+  for (int n = t; n < N; n += 256) {  // the nearest visible vertex: ascending v, strict <
+    const float px = P[n * 3 + 0], py = P[n * 3 + 1], pz = P[n * 3 + 2];
+    const float w = PW ? PW[n] : 1.0f;
+    float best = INFINITY;
+    int bi = -1;
+    for (int i = 0; i < nvis; ++i) {
+      const float dx = __fsub_rn(px, s.cv[i * 3 + 0]), dy = __fsub_rn(py, s.cv[i * 3 + 1]), dz = __fsub_rn(pz, s.cv[i * 3 + 2]);
+      const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+      if (d2 < best) {
+        best = d2;
+        bi = i;
+      }
+    }
+    if (bi >= 0) bi = s.cidx[bi];
+    const bool matched = bi >= 0 && w > 0.0f && isfinite(px) && isfinite(py) && isfinite(pz) && best <= a.max_dist2;
+    float pl = 0.0f;
+    if (matched) {
+      const float dx = __fsub_rn(px, s.v[bi * 3 + 0]), dy = __fsub_rn(py, s.v[bi * 3 + 1]), dz = __fsub_rn(pz, s.v[bi * 3 + 2]);
+      pl = fabsf(__fadd_rn(__fadd_rn(__fmul_rn(s.n[bi * 3 + 0], dx), __fmul_rn(s.n[bi * 3 + 1], dy)), __fmul_rn(s.n[bi * 3 + 2], dz)));
+    }
+    s.idx[n] = matched ? bi : -1;
+    s.dist[n] = matched ? sqrtf(best) : 0.0f;
+    s.plane[n] = pl;
+    a.idx[(long)b * N + n] = matched ? bi : -1;
+  }
+  __syncthreads();
+  {  // this thread's vertices t, t + 256, t + 512, (t + 768): one pass over the points in ascending order serves all of them
+    float W[4] = {0.f, 0.f, 0.f, 0.f}, S[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+    for (int n = 0; n < N; ++n) {
+      const int i = s.idx[n];
+      if (i < 0 || (i & 255) != t) continue;
+      const float w = PW ? PW[n] : 1.0f;
+      const float px = P[n * 3 + 0], py = P[n * 3 + 1], pz = P[n * 3 + 2];
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if ((i >> 8) == k) {
+          W[k] = __fadd_rn(W[k], w);
+          S[k][0] = __fadd_rn(S[k][0], __fmul_rn(w, px));
+          S[k][1] = __fadd_rn(S[k][1], __fmul_rn(w, py));
+          S[k][2] = __fadd_rn(S[k][2], __fmul_rn(w, pz));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int v = t + k * 256;
+      if (v >= NV) continue;
+      const bool any = W[k] > 0.0f;
+      a.vweight[(long)b * NV + v] = any ? W[k] : 0.0f;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) a.vtarget[((long)b * NV + v) * 3 + d] = any ? __fdiv_rn(S[k][d], W[k]) : 0.0f;
+    }
+  }
+  if (t == 255) {  // the matched points' count and mean distances, summed in ascending point order; the visible vertices
+    float sum = 0.f, psum = 0.f;
+    int cnt = 0;
+    for (int n = 0; n < N; ++n)
+      if (s.idx[n] >= 0) {
+        sum = __fadd_rn(sum, s.dist[n]);
+        psum = __fadd_rn(psum, s.plane[n]);
+        ++cnt;
+      }
+    a.stats[(long)b * 4 + 0] = (float)cnt;
+    a.stats[(long)b * 4 + 1] = cnt > 0 ? __fdiv_rn(sum, (float)cnt) : 0.0f;
+    a.stats[(long)b * 4 + 2] = cnt > 0 ? __fdiv_rn(psum, (float)cnt) : 0.0f;
+    a.stats[(long)b * 4 + 3] = (float)nvis;
   }
 }
 
@@ -1835,18 +2092,19 @@ extern "C" int kpf_mano_fit_gn_f32(const float* target, const float* weight, con
   return kpf_check_launch(name);
 }
 
-extern "C" int kpf_mano_fit_mesh_gn_f32(const float* target, const float* weight, const float* vert_target, const float* vert_weight,
-                                        const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
-                                        const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_gn_cfg* cfg, float* pose_aa,
-                                        float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status,
-                                        float* history, float* jacobian, float* vert_jacobian, int B, void* stream) {
-  const char* name = "kpf_mano_fit_mesh_gn_f32";
+// The two Gauss-Newton mesh entries: `name` prefixes every refusal; vert_normal selects the instantiation with the point-to-plane vertex term
+static int mano_mesh_gn_launch(const char* name, const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+                               const float* vert_normal, const float* shapedirs_t, const float* posedirs_t, const float* v_template,
+                               const float* j_regressor, const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_gn_cfg* cfg,
+                               float* pose_aa, float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status,
+                               float* history, float* jacobian, float* vert_jacobian, int B, void* stream) {
   KPF_REQUIRE(shapedirs_t && posedirs_t && v_template && j_regressor && skin_weights && hands_mean && cfg && pose_aa && betas && trans && joints &&
                   residual && status,
               "%s: null pointer", name);
   KPF_REQUIRE((vert_target == nullptr) == (vert_weight == nullptr), "%s: vert_target and vert_weight go together", name);
   KPF_REQUIRE(target || vert_target, "%s: neither joint nor vertex targets", name);
   KPF_REQUIRE(vert_target || !vert_jacobian, "%s: vert_jacobian needs the vertex term", name);
+  KPF_REQUIRE(vert_target || !vert_normal, "%s: vert_normal needs the vertex term", name);
   KPF_REQUIRE(B > 0, "%s: bad shape B=%d", name, B);
   KPF_REQUIRE(cfg->iters >= 0 && cfg->iters <= 64, "%s: iters=%d outside [0, 64]", name, cfg->iters);
   KPF_REQUIRE(cfg->mu >= 0.f && cfg->nu >= 0.f && isfinite(cfg->mu) && isfinite(cfg->nu), "%s: bad damping mu=%g nu=%g", name, cfg->mu, cfg->nu);
@@ -1882,8 +2140,30 @@ extern "C" int kpf_mano_fit_mesh_gn_f32(const float* target, const float* weight
   a.lambda_verts = cfg->lambda_verts;
   a.pose = pose_aa; a.betas = betas; a.trans = trans; a.verts = verts; a.joints = joints; a.rotmat = rotmat; a.residual = residual;
   a.status = status; a.history = history; a.jacobian = jacobian; a.vjacobian = vert_jacobian;
-  hipLaunchKernelGGL(mano_fit_mesh_gn_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  if (vert_normal) hipLaunchKernelGGL(mano_fit_mesh_gn_kernel<true>, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, vert_normal);
+  else hipLaunchKernelGGL(mano_fit_mesh_gn_kernel<false>, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, vert_normal);
   return kpf_check_launch(name);
+}
+
+extern "C" int kpf_mano_fit_mesh_gn_f32(const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+                                        const float* shapedirs_t, const float* posedirs_t, const float* v_template, const float* j_regressor,
+                                        const float* skin_weights, const float* hands_mean, const kpf_mano_fit_mesh_gn_cfg* cfg, float* pose_aa,
+                                        float* betas, float* trans, float* verts, float* joints, float* rotmat, float* residual, int* status,
+                                        float* history, float* jacobian, float* vert_jacobian, int B, void* stream) {
+  return mano_mesh_gn_launch("kpf_mano_fit_mesh_gn_f32", target, weight, vert_target, vert_weight, nullptr, shapedirs_t, posedirs_t, v_template, j_regressor,
+                             skin_weights, hands_mean, cfg, pose_aa, betas, trans, verts, joints, rotmat, residual, status, history, jacobian, vert_jacobian,
+                             B, stream);
+}
+
+extern "C" int kpf_mano_fit_mesh_gn_plane_f32(const float* target, const float* weight, const float* vert_target, const float* vert_weight,
+                                              const float* vert_normal, const float* shapedirs_t, const float* posedirs_t, const float* v_template,
+                                              const float* j_regressor, const float* skin_weights, const float* hands_mean,
+                                              const kpf_mano_fit_mesh_gn_cfg* cfg, float* pose_aa, float* betas, float* trans, float* verts, float* joints,
+                                              float* rotmat, float* residual, int* status, float* history, float* jacobian, float* vert_jacobian, int B,
+                                              void* stream) {
+  return mano_mesh_gn_launch("kpf_mano_fit_mesh_gn_plane_f32", target, weight, vert_target, vert_weight, vert_normal, shapedirs_t, posedirs_t, v_template,
+                             j_regressor, skin_weights, hands_mean, cfg, pose_aa, betas, trans, verts, joints, rotmat, residual, status, history, jacobian,
+                             vert_jacobian, B, stream);
 }
 
 extern "C" int kpf_mano_assoc_f32(const float* points, const float* point_weight, const float* verts, float max_dist2, int* idx, float* vert_target,
@@ -1896,4 +2176,28 @@ extern "C" int kpf_mano_assoc_f32(const float* points, const float* point_weight
   a.idx = idx; a.vtarget = vert_target; a.vweight = vert_weight; a.stats = stats;
   hipLaunchKernelGGL(mano_assoc_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
   return kpf_check_launch("kpf_mano_assoc_f32");
+}
+
+extern "C" int kpf_mano_normals_f32(const float* verts, const int* faces, int F, float sign, float* normals, int B, void* stream) {
+  KPF_REQUIRE(verts && faces && normals, "kpf_mano_normals_f32: null pointer");
+  KPF_REQUIRE(B > 0 && F >= 1 && F <= NORMALS_MAXF, "kpf_mano_normals_f32: bad shape B=%d F=%d (1 <= F <= %d)", B, F, NORMALS_MAXF);
+  KPF_REQUIRE(sign == 1.0f || sign == -1.0f, "kpf_mano_normals_f32: sign=%g is neither +1 nor -1", sign);
+  ManoNormalsArgs a;
+  a.verts = verts; a.faces = faces; a.F = F; a.sign = sign; a.normals = normals;
+  hipLaunchKernelGGL(mano_normals_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch("kpf_mano_normals_f32");
+}
+
+extern "C" int kpf_mano_assoc_vis_f32(const float* points, const float* point_weight, const float* verts, const float* normals, float max_dist2,
+                                      float facing_min, int* idx, float* vert_target, float* vert_weight, int* visible, float* stats, int B, int N,
+                                      void* stream) {
+  KPF_REQUIRE(points && verts && normals && idx && vert_target && vert_weight && visible && stats, "kpf_mano_assoc_vis_f32: null pointer");
+  KPF_REQUIRE(B > 0 && N >= 1 && N <= ASSOC_MAXN, "kpf_mano_assoc_vis_f32: bad shape B=%d N=%d (1 <= N <= %d)", B, N, ASSOC_MAXN);
+  KPF_REQUIRE(!(max_dist2 < 0.f) && max_dist2 == max_dist2, "kpf_mano_assoc_vis_f32: max_dist2=%g", max_dist2);
+  KPF_REQUIRE(facing_min >= 0.f && facing_min < 1.f, "kpf_mano_assoc_vis_f32: facing_min=%g outside [0, 1)", facing_min);
+  ManoAssocVisArgs a;
+  a.points = points; a.pweight = point_weight; a.verts = verts; a.normals = normals; a.max_dist2 = max_dist2; a.facing_min = facing_min; a.N = N;
+  a.idx = idx; a.visible = visible; a.vtarget = vert_target; a.vweight = vert_weight; a.stats = stats;
+  hipLaunchKernelGGL(mano_assoc_vis_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch("kpf_mano_assoc_vis_f32");
 }

@@ -155,6 +155,18 @@ def mano_model_arrays(sd, device, p="mano_layer."):
             f("th_hands_mean").reshape(45).contiguous())
 
 
+def mano_faces(sd, device, p="mano_layer."):
+    """The ManoLayer's triangles (th_faces, [F][3], any integer type) as a contiguous int32 tensor on `device` -- the `faces` of kpf_mano_normals_f32
+    (include/kpf.h; F <= 2048) -- or None when the tensors carry none."""
+    f = sd.get(p + "th_faces")
+    if f is None:
+        return None
+    f = torch.as_tensor(f).detach().reshape(-1, 3)
+    if not 1 <= f.shape[0] <= 2048:
+        raise ValueError("th_faces has %d faces; the normals take 1 <= F <= 2048" % f.shape[0])
+    return f.to(torch.int32).to(device).contiguous()
+
+
 class ManoHeadPlan:
     def __init__(self, sd, device):
         self.base = []

@@ -17,11 +17,16 @@ atomics), and fit_cloud alternates the two on the depth points the preprocessing
 
 fit_gn is the joint fit by damped Gauss-Newton (kpf_mano_fit_gn_f32): the same objective and state, 8 iterations where Adam takes 50, one
 launch; fit_cloud(joint_solver="gn") uses it for its first stage.  fit_mesh_gn is the same for the fit with the vertex term (kpf_mano_fit_mesh_gn_f32,
-DESIGN.md 4.14); fit_cloud(cloud_solver="gn") uses it for its vertex rounds."""
+DESIGN.md 4.14); fit_cloud(cloud_solver="gn") uses it for its vertex rounds.
+
+The surface: normals gives the mesh's area-weighted vertex normals from the model's faces (kpf_mano_normals_f32), associate(normals=...)
+matches the depth points to the vertices that face the camera only (kpf_mano_assoc_vis_f32), fit_mesh_gn(vert_normal=...) measures the vertex term along the
+normals (kpf_mano_fit_mesh_gn_plane_f32: one point-to-plane row per vertex, which does not punish sliding along the surface), and
+fit_cloud(metric="plane") chains the three."""
 import torch
 
 from . import lib as L
-from .heads import mano_model_arrays
+from .heads import mano_faces, mano_model_arrays
 
 
 class ManoFitter:
@@ -38,6 +43,7 @@ class ManoFitter:
             raise KeyError("no mano_layer.th_shapedirs among the given tensors")
         self.device = torch.device(device)
         self.model = mano_model_arrays(sd, self.device, key[:-len("th_shapedirs")])
+        self.faces = mano_faces(sd, self.device, key[:-len("th_shapedirs")])  # [F, 3] int32 on the device, or None when the tensors carry no th_faces
         jm = list(range(21)) if joint_map is None else [int(j) for j in joint_map]
         if sorted(jm) != list(range(21)):
             raise ValueError("joint_map must be a permutation of 0..20")
@@ -46,7 +52,7 @@ class ManoFitter:
         self.mesh_cfg = L.ManoFitMeshCfg(*[getattr(self.cfg, n) for n, _ in L.ManoFitCfg._fields_], 1.0)
         self.gn_cfg = L.ManoFitGnCfg(8, 0.1, 1e-2, float(lambda_shape), float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
         self.mesh_gn_cfg = L.ManoFitMeshGnCfg(*[getattr(self.gn_cfg, n) for n, _ in L.ManoFitGnCfg._fields_], 1.0)
-        self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs, self._mesh_gn_bufs = {}, {}, {}, {}, {}
+        self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs, self._mesh_gn_bufs, self._normal_bufs = {}, {}, {}, {}, {}, {}
 
     def new_state(self, B):
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
@@ -194,18 +200,25 @@ class ManoFitter:
                 "residual": o["residual"], "status": o["status"]}
 
     def fit_mesh_gn(self, joints_mm=None, weight=None, vert_target=None, vert_weight=None, state=None, init_trans=True, lambda_verts=1.0, iters=None,
-                    mu=0.1, nu=1e-2, jacobian=False):
+                    mu=0.1, nu=1e-2, jacobian=False, vert_normal=None):
         """fit_mesh by damped Gauss-Newton (kpf_mano_fit_mesh_gn_f32): fit_gn's iteration over the 63 joint rows and the 2334 vertex rows
         sqrt(lambda_verts u_v / sum u) (V_v + t - c_v), with fit_mesh's arguments, init_trans rule and status bits 1 and 2, and fit_gn's bit 4.  iters=None: 8;
         0 <= iters <= 64.  Without vert_target the launch is fit_gn's kernel and its bits.
 
         Returns what fit_mesh returns plus history [B, iters + 1, 2] (the mean weighted joint and vertex distance in mm before iteration 1 and after each
         iteration) and, with jacobian=True, jacobian [B, 63, 61] (as fit_gn) and vert_jacobian [B, 2334, 61]: the unweighted d (V_v + t) / d p of the state
-        on entry, row v * 3 + d (zeros without a vertex term).  Own output tensors per batch size (and per iters, for history); one launch, no host wait."""
+        on entry, row v * 3 + d (zeros without a vertex term).  Own output tensors per batch size (and per iters, for history); one launch, no host wait.
+
+        vert_normal [B, 778, 3] (normals' output, fixed for the call): the vertex term becomes point-to-plane (kpf_mano_fit_mesh_gn_plane_f32),
+        one row sqrt(lambda_verts u_v / sum u) n_v . (V_v + t - c_v) per vertex; the vertex columns of history and residual are then the mean weighted
+        |n_v . (V_v + t - c_v)|, status bit 2 is also set by a non-finite normal under a positive weight, and a vertex term is required.  None: today's
+        call and bits."""
         if (vert_target is None) != (vert_weight is None):
             raise ValueError("vert_target and vert_weight go together")
         if joints_mm is None and vert_target is None:
             raise ValueError("fit_mesh_gn needs joints_mm or vert_target")
+        if vert_normal is not None and vert_target is None:
+            raise ValueError("vert_normal needs vert_target and vert_weight")
         B = (joints_mm if joints_mm is not None else vert_target).shape[0]
         if joints_mm is not None:
             self._check(joints_mm, (B, 21, 3), "joints_mm")
@@ -214,6 +227,8 @@ class ManoFitter:
         if vert_target is not None:
             self._check(vert_target, (B, 778, 3), "vert_target")
             self._check(vert_weight, (B, 778), "vert_weight")
+        if vert_normal is not None:
+            self._check(vert_normal, (B, 778, 3), "vert_normal")
         n = 8 if iters is None else int(iters)
         if not 0 <= n <= 64:
             raise ValueError("fit_mesh_gn takes 0 <= iters <= 64, not %d" % n)
@@ -239,24 +254,49 @@ class ManoFitter:
         if jacobian and vert_target is None:
             o["vert_jacobian"].zero_()
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        name = "kpf_mano_fit_mesh_gn_f32" if vert_normal is None else "kpf_mano_fit_mesh_gn_plane_f32"
+        extra = [] if vert_normal is None else [vert_normal.data_ptr()]
         with torch.cuda.device(self.device):
-            L.check(L.load().kpf_mano_fit_mesh_gn_f32(ptr(joints_mm), ptr(weight), ptr(vert_target), ptr(vert_weight), *[m.data_ptr() for m in self.model],
-                                                      L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
-                                                      o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(),
-                                                      hist.data_ptr(), o["jacobian"].data_ptr() if jacobian else None,
-                                                      o["vert_jacobian"].data_ptr() if jacobian and vert_target is not None else None, B,
-                                                      torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_mesh_gn_f32")
+            L.check(getattr(L.load(), name)(ptr(joints_mm), ptr(weight), ptr(vert_target), ptr(vert_weight), *extra, *[m.data_ptr() for m in self.model],
+                                            L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
+                                            o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(),
+                                            hist.data_ptr(), o["jacobian"].data_ptr() if jacobian else None,
+                                            o["vert_jacobian"].data_ptr() if jacobian and vert_target is not None else None, B,
+                                            torch.cuda.current_stream().cuda_stream), name)
         out = {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
                "residual": o["residual"], "status": o["status"], "history": hist}
         if jacobian:
             out["jacobian"], out["vert_jacobian"] = o["jacobian"], o["vert_jacobian"]
         return out
 
-    def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0):
+    def normals(self, verts3d, sign=1.0, _slot=0):
+        """verts3d [B, 778, 3] -> the area-weighted unit vertex normals [B, 778, 3] by the model's faces (th_faces, F <= 2048): sign * normalize(the sum of
+        (v1 - v0) x (v2 - v0) over the corners of the faces at the vertex), (0, 0, 0) for a vertex in no face or a sum that is 0 or not finite.  sign = -1
+        for a mirrored (left) hand or the other winding.  The fitter's own tensor per batch size; one launch, no host wait (kpf_mano_normals_f32)."""
+        B = int(verts3d.shape[0])
+        self._check(verts3d, (B, 778, 3), "verts3d")
+        if self.faces is None:
+            raise KeyError("no mano_layer.th_faces among the given tensors")
+        if float(sign) not in (1.0, -1.0):
+            raise ValueError("sign must be +1 or -1, not %r" % (sign,))
+        key = (B, _slot)
+        if key not in self._normal_bufs:
+            self._normal_bufs[key] = torch.empty(B, 778, 3, device=self.device, dtype=torch.float32)
+        out = self._normal_bufs[key]
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_normals_f32(verts3d.data_ptr(), self.faces.data_ptr(), int(self.faces.shape[0]), float(sign), out.data_ptr(), B,
+                                                  torch.cuda.current_stream().cuda_stream), "kpf_mano_normals_f32")
+        return out
+
+    def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0, normals=None, facing_min=0.0):
         """points_mm [B, N, 3] (camera-space mm, 1 <= N <= 4096), verts3d [B, 778, 3] (a fit's), point_weight [B, N] >= 0 or None (= ones), max_dist: the gate
         in mm (float("inf"): none) -> idx [B, N] int32 (each point's nearest vertex, -1 if its weight is 0, a coordinate is not finite or the vertex is
         farther than max_dist), vert_target [B, 778, 3] and vert_weight [B, 778] (per vertex the weighted centroid and the summed weight of its points; 0
-        and 0 without any), stats [B, 2] (matched points, their mean distance in mm).  The fitter's own tensors per (B, N); one launch, no host wait."""
+        and 0 without any), stats [B, 2] (matched points, their mean distance in mm).  The fitter's own tensors per (B, N); one launch, no host wait.
+
+        normals [B, 778, 3] (normals' output): only the vertices that face the camera -- the origin of the frame -- are candidates
+        (kpf_mano_assoc_vis_f32): n_v . V_v < -facing_min |V_v|, 0 <= facing_min < 1.  Also returned then: visible [B, 778] int32, and stats is [B, 4]: the
+        matched points, their mean distance to their vertex, their mean distance to that vertex's tangent plane, the visible vertices."""
         B, N = int(points_mm.shape[0]), int(points_mm.shape[1]) if points_mm.dim() == 3 else -1
         self._check(points_mm, (B, N, 3), "points_mm")
         self._check(verts3d, (B, 778, 3), "verts3d")
@@ -264,6 +304,8 @@ class ManoFitter:
             self._check(point_weight, (B, N), "point_weight")
         if not 1 <= N <= 4096:
             raise ValueError("associate takes 1 <= N <= 4096 points per hand, not %d" % N)
+        if normals is not None:
+            return self._associate_vis(points_mm, verts3d, point_weight, max_dist, _slot, normals, facing_min, B, N)
         key = (B, N, _slot)
         if key not in self._assoc_bufs:
             e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
@@ -277,15 +319,40 @@ class ManoFitter:
                     "kpf_mano_assoc_f32")
         return dict(o)
 
+    def _associate_vis(self, points_mm, verts3d, point_weight, max_dist, _slot, normals, facing_min, B, N):
+        self._check(normals, (B, 778, 3), "normals")
+        if not 0.0 <= float(facing_min) < 1.0:
+            raise ValueError("facing_min must be in [0, 1), not %r" % (facing_min,))
+        key = (B, N, _slot, "vis")
+        if key not in self._assoc_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            self._assoc_bufs[key] = {"idx": torch.empty(B, N, device=self.device, dtype=torch.int32), "vert_target": e(B, 778, 3), "vert_weight": e(B, 778),
+                                     "visible": torch.empty(B, 778, device=self.device, dtype=torch.int32), "stats": e(B, 4)}
+        o = self._assoc_bufs[key]
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_assoc_vis_f32(points_mm.data_ptr(), None if point_weight is None else point_weight.data_ptr(), verts3d.data_ptr(),
+                                                    normals.data_ptr(), float(max_dist) * float(max_dist), float(facing_min), o["idx"].data_ptr(),
+                                                    o["vert_target"].data_ptr(), o["vert_weight"].data_ptr(), o["visible"].data_ptr(), o["stats"].data_ptr(),
+                                                    B, N, torch.cuda.current_stream().cuda_stream), "kpf_mano_assoc_vis_f32")
+        return dict(o)
+
     def fit_cloud(self, joints_mm, points_mm, weight=None, point_weight=None, state=None, init_trans=True, rounds=3, iters_cloud=None, max_dist=20.0,
-                  lambda_verts=1.0, joint_solver="adam", cloud_solver="adam"):
+                  lambda_verts=1.0, joint_solver="adam", cloud_solver="adam", metric="point", facing_min=0.0, normal_sign=1.0):
         """Joints, then the depth points: one fit on the joints, then `rounds` times associate followed by fit_mesh (warm start, init_trans=False, the joints
         kept in the objective, iters_cloud iterations each; None = the fitter's), and last one associate on the final vertices: 2 * rounds + 2 launches and no
         host wait.  Returns the last fit's outputs plus cloud_before and cloud_after (the stats of the first and the last association: matched points and
         their mean distance to the mesh in mm) and the last association's idx, vert_target and vert_weight.  rounds=0 is fit plus one associate.
         joint_solver: "adam" (fit) or "gn" (fit_gn with its defaults) for the first stage.  cloud_solver: "adam" (fit_mesh) or "gn" (fit_mesh_gn; iters_cloud=None
         is then 2 -- the alternation limits the chain, not the solver, so the rounds should be many and short: rounds=6) for the vertex rounds.  The two are
-        independent; on the synthetic hand the Adam joint stage is the better start for the cloud."""
+        independent; on the synthetic hand the Adam joint stage is the better start for the cloud.
+
+        metric: "point" (the above, its bits) or "plane" (needs cloud_solver="gn"): each round is normals -> associate(normals=, facing_min)
+        -> fit_mesh_gn(vert_normal=), and a last normals + associate: 3 * rounds + 3 launches, no host wait.  Also returned then: normals and visible of the
+        final mesh, and cloud_before / cloud_after are the 4-wide stats.  normal_sign: normals' sign."""
+        if metric not in ("point", "plane"):
+            raise ValueError("metric must be \"point\" or \"plane\", not %r" % (metric,))
+        if metric == "plane" and cloud_solver != "gn":
+            raise ValueError("metric=\"plane\" needs cloud_solver=\"gn\"")
         if joint_solver not in ("adam", "gn"):
             raise ValueError("joint_solver must be \"adam\" or \"gn\", not %r" % (joint_solver,))
         if cloud_solver not in ("adam", "gn"):
@@ -296,6 +363,19 @@ class ManoFitter:
             out = self.fit(joints_mm, weight, state=state, init_trans=init_trans)
         state = (out["mano_pose_aa"], out["mano_shape"], out["trans"])
         first = None
+        if metric == "plane":
+            for r in range(int(rounds)):
+                nrm = self.normals(out["verts3d"], normal_sign)
+                a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0, normals=nrm, facing_min=facing_min)
+                first = a if first is None else first
+                out = self.fit_mesh_gn(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
+                                       iters=2 if iters_cloud is None else iters_cloud, vert_normal=nrm)
+            nrm = self.normals(out["verts3d"], normal_sign, _slot=2)
+            last = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=2, normals=nrm, facing_min=facing_min)
+            out = dict(out)
+            out.update(cloud_before=(last if first is None else first)["stats"], cloud_after=last["stats"], idx=last["idx"], vert_target=last["vert_target"],
+                       vert_weight=last["vert_weight"], normals=nrm, visible=last["visible"])
+            return out
         for r in range(int(rounds)):
             a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0)
             first = a if first is None else first

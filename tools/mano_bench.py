@@ -3,7 +3,9 @@ hand model as torch ops under autograd (layer="torch") against heads_train.ManoL
 with iters = 10 and 50; the Gauss-Newton fit fit_gn at B = 1 and 32 -- ms per call at its default 8 iterations, at 1 and 0, ms per
 iteration = (8 - 1) / 7, the residual and history after, Adam's 10 / 50-iteration figures of the same run beside them (records fit_gn_B1, fit_gn_B32); and the fit with a vertex term, the association of 1024 points and the chain fit_cloud (3 rounds) at B = 1 and 32
 with iters = 50; the Gauss-Newton mesh fit fit_mesh_gn at 0, 1, 2 and 8 iterations and the chain with six Gauss-Newton rounds of two
-iterations, Adam's figures of the same run beside them (records fit_mesh_gn_B1 / _B32, fit_cloud_gn_B1 / _B32).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
+iterations, Adam's figures of the same run beside them (records fit_mesh_gn_B1 / _B32, fit_cloud_gn_B1 / _B32); the vertex normals, the
+association over the camera-facing vertices and the chain with point-to-plane rounds (records normals_B1 / _B32, assoc_vis_B1 / _B32,
+fit_cloud_plane_B1 / _B32, beside fit_cloud_gn_* of the same run).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
     python tools/mano_bench.py --reps 50
@@ -109,6 +111,23 @@ def main():
                                        "status": sorted(set(int(v) for v in out["status"])),
                                        "adam_ms_rounds3_iters50": rec["fit_cloud_ms_B%d_iters50_rounds3" % B],
                                        "adam_cloud_mm_rounds3_iters50": rec["fit_cloud_mm_B%d_iters50_rounds3" % B]}
+        # the surface entries: the normals, the association over the camera-facing vertices, and the chain with point-to-plane rounds beside
+        # the point-to-vertex chain of this run.  The synthetic hand's faces are random, so the figures that mean something here are the times.
+        nrm = fitter.normals(vt)
+        rec["normals_B%d" % B] = {"ms": _timed(lambda: fitter.normals(vt), args.reps, torch), "faces": int(fitter.faces.shape[0])}
+        vis = fitter.associate(pts, vt, normals=nrm)
+        rec["assoc_vis_B%d" % B] = {"ms_N1024": _timed(lambda: fitter.associate(pts, vt, normals=nrm), args.reps, torch),
+                                    "visible": float(vis["stats"][:, 3].mean()), "matched": float(vis["stats"][:, 0].mean()),
+                                    "associate_ms_N1024": rec["associate_ms_B%d_N1024" % B]}
+        pl_ms = {n: _timed(lambda: fitter.fit_mesh_gn(y, None, vt, u, iters=n, vert_normal=nrm), args.reps, torch) for n in (1, 8)}
+        plane = dict(gn, metric="plane")
+        plane_ms = _timed(lambda: fitter.fit_cloud(y, pts, **plane), args.reps, torch)
+        out = fitter.fit_cloud(y, pts, **plane)
+        rec["fit_cloud_plane_B%d" % B] = {"ms_rounds6_iters2": plane_ms, "cloud_mm": [[float(v) for v in out[k].mean(0)] for k in ("cloud_before", "cloud_after")],
+                                          "status": sorted(set(int(v) for v in out["status"])),
+                                          "fit_mesh_gn_plane_ms_iters1": pl_ms[1], "fit_mesh_gn_plane_ms_iters8": pl_ms[8],
+                                          "fit_mesh_gn_plane_ms_per_iteration": (pl_ms[8] - pl_ms[1]) / 7,
+                                          "point_ms_rounds6_iters2": cloud_ms, "point_ms_per_iteration": rec["fit_mesh_gn_B%d" % B]["ms_per_iteration"]}
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:
