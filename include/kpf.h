@@ -675,7 +675,7 @@ int kpf_bn2_add_relu_backward(const float* dy, const float* out, const float* xa
  *   kpf_row_gather_fwd_f32  out[b][r][:] = sum_{g<G} w[b][r*G+g] * src[b][idx[b][r*G+g]][:]   (src [B][P][C], idx int32 [B][R*G],
  *                           w [B][R*G] or NULL for unit weights, out [B][R][C]).
  *   kpf_row_gather_bwd_f32  dsrc[b][p][:] = sum over entries e ascending with idx[b][e] == p of w[b][e] * dout[b][e/G][:];
- *                           R*G <= 8192 entries and P <= 2048 source rows per image; ws >= kpf_row_gather_ws_ints(B, P, R, G) ints
+ *                           R*G <= 8192 entries and P <= 4096 source rows per image; ws >= kpf_row_gather_ws_ints(B, P, R, G) ints
  *                           (the per-image inverse lists: a stable counting sort of the entries by source row).
  */
 int kpf_upsample2x_bwd(const void* dy, void* dx, int dtype, int B, int H, int W, int C, void* stream);
@@ -924,7 +924,7 @@ int kpf_geom_gate_forward(const float* pix_xyz, const float* joint_xyz, float* g
 int kpf_geom_gate_backward(const float* pix_xyz, const float* joint_xyz, const float* dgam, float* djoint, int B, int J, int P, void* stream);
 
 /* The same map with the joints given in crop coordinates uvd in [-1, 1]^3 (ABI 13): the uvd -> camera -> cube-normalised xyz transform of
- * dataloader/loader.py:775-789 (half_size = img_size / 2, flip = +-1) runs inside the kernel and the backward returns d/d(uvd).
+ * dataloader/loader.py:775-789 (half_size = img_size / 2, flip = +-1) runs inside the kernel (in double: one joint per workgroup) and the backward returns d/d(uvd).
  * par16 [B][16] = [M^-1 rows 0 and 1 (6) | fx fy u0 v0 (4) | centre xyz (3) | cube xyz (3)] per sample.  Replaces model/model.py:318-326. */
 int kpf_geom_gate_uvd_forward(const float* pix_xyz, const float* joint_uvd, const float* par16, float* gam, int B, int J, int P, float half_size, float flip,
                               void* stream);

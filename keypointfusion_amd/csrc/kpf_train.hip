@@ -2108,17 +2108,19 @@ __global__ __launch_bounds__(256) void geom_gate_kernel(const float* __restrict_
   const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const long bj = (long)b * J + j;
   float x0 = jx[bj * 3 + 0], x1 = jx[bj * 3 + 1], x2 = jx[bj * 3 + 2];
-  float tx = 0.f, ty = 0.f, dep = 0.f;
+  // (the joint's transform and its Jacobian in double: M^-1 carries a translation of hundreds of pixels against offsets from the principal point of tens, so in
+  //  fp32 the normalised joint lands ~3e-7 off — and next to a pixel the gate's gradient moves by 30 times that.  One joint per workgroup: a few dozen operations)
+  double tx = 0., ty = 0., dep = 0.;
   const float* pp = par ? par + (long)b * 16 : nullptr;
   if (pp) {
-    const float u = (x0 + 1.f) * half_size, v = (x1 + 1.f) * half_size;
-    dep = x2 * (pp[15] * 0.5f) + pp[12];
+    const double u = ((double)x0 + 1.) * half_size, v = ((double)x1 + 1.) * half_size;
+    dep = (double)x2 * (pp[15] * 0.5) + pp[12];
     tx = pp[0] * u + pp[1] * v + pp[2];
     ty = pp[3] * u + pp[4] * v + pp[5];
-    const float cx = (tx - pp[8]) * dep / pp[6], cy = flip * (ty - pp[9]) * dep / pp[7];
-    x0 = (cx - pp[10]) / (pp[13] * 0.5f);
-    x1 = (cy - pp[11]) / (pp[14] * 0.5f);
-    x2 = (dep - pp[12]) / (pp[15] * 0.5f);
+    const double cx = (tx - pp[8]) * dep / pp[6], cy = flip * (ty - pp[9]) * dep / pp[7];
+    x0 = (float)((cx - pp[10]) / (pp[13] * 0.5));
+    x1 = (float)((cy - pp[11]) / (pp[14] * 0.5));
+    x2 = (float)((dep - pp[12]) / (pp[15] * 0.5));
   }
   const float* ib = ix + (long)b * P * 3;
   float g0 = 0.f, g1 = 0.f, g2 = 0.f;
@@ -2140,11 +2142,11 @@ __global__ __launch_bounds__(256) void geom_gate_kernel(const float* __restrict_
     g2 = block_sum256(g2, red);
     if (tid == 0) {
       if (pp) {  // d/d(uvd) = J^T d/d(xyz_normalised)
-        const float gx = g0 / (pp[13] * 0.5f), gy = g1 / (pp[14] * 0.5f), gz = g2 / (pp[15] * 0.5f);
-        const float ax = dep / pp[6] * half_size, ay = flip * dep / pp[7] * half_size, hz = pp[15] * 0.5f;
-        g0 = gx * pp[0] * ax + gy * pp[3] * ay;
-        g1 = gx * pp[1] * ax + gy * pp[4] * ay;
-        g2 = (gx * (tx - pp[8]) / pp[6] + gy * flip * (ty - pp[9]) / pp[7] + gz) * hz;
+        const double gx = g0 / (pp[13] * 0.5), gy = g1 / (pp[14] * 0.5), gz = g2 / (pp[15] * 0.5);
+        const double ax = dep / pp[6] * half_size, ay = flip * dep / pp[7] * half_size, hz = pp[15] * 0.5;
+        g0 = (float)(gx * pp[0] * ax + gy * pp[3] * ay);
+        g1 = (float)(gx * pp[1] * ax + gy * pp[4] * ay);
+        g2 = (float)((gx * (tx - pp[8]) / pp[6] + gy * flip * (ty - pp[9]) / pp[7] + gz) * hz);
       }
       out[bj * 3 + 0] = g0;
       out[bj * 3 + 1] = g1;
