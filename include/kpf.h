@@ -440,6 +440,34 @@ int kpf_mano_assoc_vis_f32(const float* points, const float* point_weight, const
     float max_dist2, float facing_min /*0 <= . < 1*/, int* idx, float* vert_target, float* vert_weight,
     int* visible /*[B][778]*/, float* stats /*[B][4]*/, int B, int N, void* stream);
 
+/* kpf_mano_assoc_vis_f32 with a vertex mask (ABI 31): vert_mask [B][778] int, or NULL = none.  A vertex is a candidate iff it passes the facing rule AND
+ * vert_mask[v] != 0; visible and stats[3] report the combination.  The same kernel: with NULL or a mask of ones every output is
+ * kpf_mano_assoc_vis_f32's bits.  The mask the fit uses is 1 - occluded of kpf_mano_raster_f32. */
+int kpf_mano_assoc_vis_mask_f32(const float* points, const float* point_weight, const float* verts, const float* normals,
+    const int* vert_mask /*[B][778] or NULL*/, float max_dist2, float facing_min, int* idx, float* vert_target, float* vert_weight,
+    int* visible, float* stats, int B, int N, void* stream);
+
+/* z-buffer render of the mesh into a crop's pixel grid (ABI 31), one workgroup per hand, the buffer in LDS.  verts [B][778][3] mm in the camera frame
+ * of the depth points; faces [F][3] int, 1 <= F <= 2048; cam [B][4] = fx, fy, u0, v0; M [B][2][3], the affine map from frame pixels to crop
+ * coordinates (the top two rows of the preprocessing's M), or NULL = the identity; 1 <= H, W and H * W <= 16384; margin in mm, finite and >= 0;
+ * depth_obs [B][H][W] mm or NULL.  Anything else is refused before the launch and nothing is written.
+ *   Per vertex U = (x*fx)/z + u0, V = (y*fy)/z + v0, sx = ((m00*U + m01*V) + m02) - 0.5, sy = ((m10*U + m11*V) + m12) - 0.5, iz = 1/z.  The -0.5: the
+ * preprocessing back-projects crop pixel (c, r) from (c + 0.5, r + 0.5), so pixel (c, r) is sampled at sx = c, sy = r.
+ *   Per face (i0, i1, i2): skipped if an index is outside 0..777, two indices are equal, or a vertex is not finite or has z <= 0 -- there is NO
+ * near-plane clipping, a face that crosses z = 0 is dropped whole.  The edge function of a directed edge a -> b at p is evaluated from the lower index,
+ * e = (sx[hi]-sx[lo])*(py-sy[lo]) - (sy[hi]-sy[lo])*(px-sx[lo]), and negated if a > b.  area = edge(i0 -> i1) at vertex i2; skipped if 0 or not finite.
+ * w0, w1, w2 = edge(i1 -> i2), edge(i2 -> i0), edge(i0 -> i1) at the pixel; inside iff all three sign(area)*w_i >= 0 (two-sided).  The pixels are
+ * ceil(min) .. floor(max) per axis, clamped to the window in float.
+ *   Per inside pixel sum = (w0 + w1) + w2, izp = ((w0/sum)*iz0 + (w1/sum)*iz1) + (w2/sum)*iz2, d = 1/izp; a candidate iff d is finite and > 0.  The
+ * smallest d wins the pixel, among equal d the lowest face index (an integer min on (bits(d) << 32) | face: no dependence on arrival order).
+ *   depth [B][H][W] mm, 0 where nothing covers the pixel; face [B][H][W], -1 there.  occluded [B][778] = 1 iff the vertex is finite with z > 0, its
+ * nearest pixel (floor(sx + 0.5), floor(sy + 0.5)) is inside the window, that pixel is covered and depth[pixel] < z - margin.  stats [B][4]: covered
+ * pixels; observed pixels (depth_obs finite and > 0); pixels that are both; the mean of |d - d_obs| over those, summed per row in ascending column
+ * order and then over the rows in ascending order (0 without any).  Without depth_obs entries 1..3 are 0.  Every operation is individually rounded
+ * (no fma): a numpy-fp32 restatement gives the same bits. */
+int kpf_mano_raster_f32(const float* verts, const int* faces, int F, const float* cam, const float* M /*or NULL*/, int H, int W, float margin,
+    const float* depth_obs /*or NULL*/, float* depth, int* face, int* occluded, float* stats, int B, void* stream);
+
 /* kpf_mano_fit_mesh_gn_f32 with a point-to-plane vertex term (ABI 30).  vert_normal [B][778][3], fixed for the launch, or NULL: then this is
  * kpf_mano_fit_mesh_gn_f32, the same kernel and bits.  With normals a vertex term is required, and each vertex contributes ONE row
  *   sqrt(lambda_verts u_v / sv) n_v^T (V_v + t - c_v),  Jacobian n_v^T d (V_v + t) / d p
@@ -1094,7 +1122,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 30
+#define KPF_ABI_VERSION 31
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -1844,9 +1844,11 @@ __global__ __launch_bounds__(256) void mano_normals_kernel(ManoNormalsArgs a) {
 // the frame, so vertex v is visible iff its normal is finite, not all-zero and n_v . V_v < -facing_min |V_v|.  The argmin runs over the visible vertices
 // only (compacted first, in ascending order); everything else -- gate, weights, centroids, rounding, orders -- is the association's.  stats [B][4]: matched points, their mean distance to their
 // vertex, their mean |n_i . (p - V_i)|, the visible vertices.  tests/mano_surface_cases.py::associate_vis_host gives the same bits.
+// vmask (kpf_mano_assoc_vis_mask_f32; null: none): a vertex whose entry is 0 is no candidate either -- the z-buffer's self-occlusion.
 // ---------------------------------------------------------------------------------------------------------------
 struct ManoAssocVisArgs {
   const float *points, *pweight, *verts, *normals;  // [B][N][3], [B][N] or null, [B][778][3], [B][778][3]
+  const int* vmask;                                 // [B][778] or null
   float max_dist2, facing_min;
   int N;
   int *idx, *visible;                               // [B][N], [B][778]
@@ -1880,7 +1882,7 @@ __global__ __launch_bounds__(256) void mano_assoc_vis_kernel(ManoAssocVisArgs a)
     const float dot = __fadd_rn(__fadd_rn(__fmul_rn(nx, vx), __fmul_rn(ny, vy)), __fmul_rn(nz, vz));
     const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)), __fmul_rn(vz, vz)));
     const bool some = isfinite(nx) && isfinite(ny) && isfinite(nz) && !(nx == 0.0f && ny == 0.0f && nz == 0.0f);
-    const int vis = (some && dot < -__fmul_rn(a.facing_min, len)) ? 1 : 0;
+    const int vis = (some && dot < -__fmul_rn(a.facing_min, len) && (!a.vmask || a.vmask[(long)b * NV + v] != 0)) ? 1 : 0;
     s.vis[v] = vis;
     a.visible[(long)b * NV + v] = vis;
   }
@@ -1969,6 +1971,195 @@ __global__ __launch_bounds__(256) void mano_assoc_vis_kernel(ManoAssocVisArgs a)
     a.stats[(long)b * 4 + 1] = cnt > 0 ? __fdiv_rn(sum, (float)cnt) : 0.0f;
     a.stats[(long)b * 4 + 2] = cnt > 0 ? __fdiv_rn(psum, (float)cnt) : 0.0f;
     a.stats[(long)b * 4 + 3] = (float)nvis;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// z-buffer render of the mesh into the crop's pixel grid: depth, the owning face, the vertices that lie behind another part of the mesh
+// along their pixel's ray, and the comparison with an observed depth crop.  One workgroup per hand; the z-buffer is H * W 64-bit words of LDS holding
+// (bits(d) << 32) | face, and a face's candidate enters by an integer min: a positive float's bits order as the float does, so the smallest depth wins, among
+// equal depths the lowest face, whatever the order the faces arrive in.  A thread owns faces t, t + 256, ...: it walks a pixel box of up to
+// RASTER_SMALL pixels itself and queues a larger face, which a whole wave then walks, 8 x 8 pixels at a step (the queue's order does not matter either).
+// The faces are read from global memory (at 128 x 128 the buffer alone is 131072 of the 163840 bytes).  There is no near-plane clipping: a face with a vertex at z <= 0 is
+// skipped whole.  Every operation individually rounded: tests/mano_raster_cases.py::raster_host gives the same bits.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int RASTER_MAXPIX = 16384;
+constexpr unsigned long long RASTER_EMPTY = ~0ull;
+constexpr int RASTER_SMALL = 64;
+
+struct ManoRasterArgs {
+  const float* verts;      // [B][778][3]
+  const int* faces;        // [F][3]
+  const float *cam, *M;    // [B][4]: fx, fy, u0, v0; [B][2][3] or null (the identity)
+  const float* depth_obs;  // [B][H][W] or null
+  int F, H, W;
+  float margin;
+  float* depth;            // [B][H][W]
+  int *face, *occluded;    // [B][H][W], [B][778]
+  float* stats;            // [B][4]
+};
+
+// the launch's dynamic LDS: zb [HW] 64-bit | sx, sy, iz, z [778] float each | ok [778] int | count [4] int | queue [2048] 16-bit
+constexpr size_t raster_lds_bytes(int HW) { return (size_t)HW * 8 + (size_t)NV * 5 * 4 + 16 + (size_t)NORMALS_MAXF * 2; }
+
+// One directed edge a -> b, always evaluated from the lower vertex index: e = (sx[hi] - sx[lo]) (py - sy[lo]) - (sy[hi] - sy[lo]) (px - sx[lo]), negated
+// if a > b.  The two faces at an edge get the same number with opposite signs, so with an inclusive test a pixel centre on the edge belongs to one of them.
+struct RasterEdge {
+  float dx, dy, ox, oy;
+  bool neg;
+  __device__ __forceinline__ void set(const float* sx, const float* sy, int a, int b) {
+#pragma clang fp contract(off)
+    const int lo = a < b ? a : b, hi = a < b ? b : a;
+    dx = __fsub_rn(sx[hi], sx[lo]);
+    dy = __fsub_rn(sy[hi], sy[lo]);
+    ox = sx[lo];
+    oy = sy[lo];
+    neg = a > b;
+  }
+  __device__ __forceinline__ float at(float px, float py) const {
+#pragma clang fp contract(off)
+    const float e = __fsub_rn(__fmul_rn(dx, __fsub_rn(py, oy)), __fmul_rn(dy, __fsub_rn(px, ox)));
+    return neg ? -e : e;
+  }
+};
+
+// One face ready to be walked: its three edges (w0, w1, w2 are the weights of v0, v1, v2), the vertices' 1 / z, the sign of its area and its pixel box
+struct RasterFace {
+  RasterEdge e0, e1, e2;
+  float iz0, iz1, iz2;
+  bool pos;
+  int x0, x1, y0, y1;
+  // false: the face is skipped (an index outside 0..777, a repeated one, a vertex that is not finite or has z <= 0, no area, no pixel)
+  __device__ __forceinline__ bool set(const int* faces, int k, const float* sx, const float* sy, const float* iz, const int* ok, int H, int W) {
+#pragma clang fp contract(off)
+    const int i0 = faces[k * 3 + 0], i1 = faces[k * 3 + 1], i2 = faces[k * 3 + 2];
+    if ((unsigned)i0 >= (unsigned)NV || (unsigned)i1 >= (unsigned)NV || (unsigned)i2 >= (unsigned)NV) return false;
+    if (i0 == i1 || i1 == i2 || i0 == i2) return false;
+    if (!(ok[i0] && ok[i1] && ok[i2])) return false;
+    e0.set(sx, sy, i1, i2);
+    e1.set(sx, sy, i2, i0);
+    e2.set(sx, sy, i0, i1);
+    const float area = e2.at(sx[i2], sy[i2]);
+    if (area == 0.0f || !isfinite(area)) return false;  // a finite area: every sx, sy of the face is finite
+    // the pixel box, clamped to the window in float: a vertex at z = 1e-3 mm projects to 1e9
+    const float x0f = fmaxf(ceilf(fminf(fminf(sx[i0], sx[i1]), sx[i2])), 0.0f), x1f = fminf(floorf(fmaxf(fmaxf(sx[i0], sx[i1]), sx[i2])), (float)(W - 1));
+    const float y0f = fmaxf(ceilf(fminf(fminf(sy[i0], sy[i1]), sy[i2])), 0.0f), y1f = fminf(floorf(fmaxf(fmaxf(sy[i0], sy[i1]), sy[i2])), (float)(H - 1));
+    if (!(x0f <= x1f && y0f <= y1f)) return false;
+    x0 = (int)x0f; x1 = (int)x1f; y0 = (int)y0f; y1 = (int)y1f;  // inside [0, W - 1] x [0, H - 1]
+    iz0 = iz[i0]; iz1 = iz[i1]; iz2 = iz[i2];
+    pos = area > 0.0f;
+    return true;
+  }
+  // pixel (c, r) of the box: the face's depth there enters the z-buffer if the pixel centre is inside
+  __device__ __forceinline__ void pixel(int c, int r, int k, unsigned long long* zb, int W) const {
+#pragma clang fp contract(off)
+    const float px = (float)c, py = (float)r;
+    const float w0 = e0.at(px, py), w1 = e1.at(px, py), w2 = e2.at(px, py);
+    const bool in = pos ? (w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f) : (w0 <= 0.0f && w1 <= 0.0f && w2 <= 0.0f);  // two-sided: MANO is open at the wrist
+    if (!in) return;
+    const float sum = __fadd_rn(__fadd_rn(w0, w1), w2);
+    const float izp = __fadd_rn(__fadd_rn(__fmul_rn(__fdiv_rn(w0, sum), iz0), __fmul_rn(__fdiv_rn(w1, sum), iz1)), __fmul_rn(__fdiv_rn(w2, sum), iz2));
+    const float d = __fdiv_rn(1.0f, izp);  // perspective-correct
+    if (isfinite(d) && d > 0.0f) atomicMin(&zb[r * W + c], ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)k);
+  }
+};
+
+__global__ __launch_bounds__(256) void mano_raster_kernel(ManoRasterArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned long long raster_zb[];
+  const int b = blockIdx.x, t = threadIdx.x, H = a.H, W = a.W, HW = H * W, F = a.F;
+  unsigned long long* zb = raster_zb;
+  float* sx = reinterpret_cast<float*>(zb + HW);
+  float *sy = sx + NV, *iz = sy + NV, *vz = iz + NV;
+  int* ok = reinterpret_cast<int*>(vz + NV);
+  int* count = ok + NV;  // covered, observed, both; the length of the queue
+  unsigned short* queue = reinterpret_cast<unsigned short*>(count + 4);
+  for (int p = t; p < HW; p += 256) zb[p] = RASTER_EMPTY;
+  if (t < 4) count[t] = 0;
+  {
+    const float fx = a.cam[b * 4 + 0], fy = a.cam[b * 4 + 1], u0 = a.cam[b * 4 + 2], v0 = a.cam[b * 4 + 3];
+    float m[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+    if (a.M)
+      for (int k = 0; k < 6; ++k) m[k] = a.M[b * 6 + k];
+    for (int v = t; v < NV; v += 256) {
+      const float x = a.verts[((long)b * NV + v) * 3 + 0], y = a.verts[((long)b * NV + v) * 3 + 1], z = a.verts[((long)b * NV + v) * 3 + 2];
+      const float U = __fadd_rn(__fdiv_rn(__fmul_rn(x, fx), z), u0), V = __fadd_rn(__fdiv_rn(__fmul_rn(y, fy), z), v0);
+      sx[v] = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], U), __fmul_rn(m[1], V)), m[2]), 0.5f);
+      sy[v] = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[3], U), __fmul_rn(m[4], V)), m[5]), 0.5f);
+      iz[v] = __fdiv_rn(1.0f, z);
+      vz[v] = z;
+      ok[v] = (isfinite(x) && isfinite(y) && isfinite(z) && z > 0.0f) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  for (int k = t; k < F; k += 256) {  // a small face is walked by its thread, a large one is queued (at most F <= 2048 entries)
+    RasterFace f;
+    if (!f.set(a.faces, k, sx, sy, iz, ok, H, W)) continue;
+    if ((f.x1 - f.x0 + 1) * (f.y1 - f.y0 + 1) > RASTER_SMALL) {
+      queue[atomicAdd(&count[3], 1)] = (unsigned short)k;
+      continue;
+    }
+    for (int r = f.y0; r <= f.y1; ++r)
+      for (int c = f.x0; c <= f.x1; ++c) f.pixel(c, r, k, zb, W);
+  }
+  __syncthreads();
+  for (int q = t >> 6; q < count[3]; q += 4) {  // a queued face is walked by one wave, 8 x 8 pixels at a step
+    const int k = queue[q];
+    RasterFace f;
+    f.set(a.faces, k, sx, sy, iz, ok, H, W);
+    for (int r = f.y0 + ((t & 63) >> 3); r <= f.y1; r += 8)
+      for (int c = f.x0 + (t & 7); c <= f.x1; c += 8) f.pixel(c, r, k, zb, W);
+  }
+  __syncthreads();
+  for (int v = t; v < NV; v += 256) {  // behind the surface that owns its nearest pixel, by more than the margin
+    int occ = 0;
+    if (ok[v]) {
+      const float c = floorf(__fadd_rn(sx[v], 0.5f)), r = floorf(__fadd_rn(sy[v], 0.5f));
+      if (c >= 0.0f && c <= (float)(W - 1) && r >= 0.0f && r <= (float)(H - 1)) {
+        const unsigned long long key = zb[(int)r * W + (int)c];
+        occ = (key != RASTER_EMPTY && __uint_as_float((unsigned)(key >> 32)) < __fsub_rn(vz[v], a.margin)) ? 1 : 0;
+      }
+    }
+    a.occluded[(long)b * NV + v] = occ;
+  }
+  __syncthreads();  // the keys are replaced below
+  const float* obs = a.depth_obs ? a.depth_obs + (long)b * HW : nullptr;
+  int n_cov = 0, n_obs = 0, n_both = 0;
+  for (int p = t; p < HW; p += 256) {
+    const unsigned long long key = zb[p];
+    const bool cov = key != RASTER_EMPTY;
+    const float d = cov ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
+    a.depth[(long)b * HW + p] = d;
+    a.face[(long)b * HW + p] = cov ? (int)(unsigned)key : -1;
+    n_cov += cov ? 1 : 0;
+    if (obs) {
+      const float o = obs[p];
+      const bool seen = isfinite(o) && o > 0.0f;
+      n_obs += seen ? 1 : 0;
+      n_both += (seen && cov) ? 1 : 0;
+      zb[p] = (unsigned long long)__float_as_uint((seen && cov) ? fabsf(__fsub_rn(d, o)) : 0.0f);  // + 0 leaves a sum's bits as they are
+    }
+  }
+  atomicAdd(&count[0], n_cov);
+  atomicAdd(&count[1], n_obs);
+  atomicAdd(&count[2], n_both);
+  __syncthreads();
+  if (obs) {  // |d - d_obs| summed per row in ascending column order, then over the rows in ascending order
+    for (int r = t; r < H; r += 256) {
+      float s = 0.0f;
+      for (int c = 0; c < W; ++c) s = __fadd_rn(s, __uint_as_float((unsigned)zb[r * W + c]));
+      zb[r * W] = (unsigned long long)__float_as_uint(s);  // only this thread reads row r
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    float total = 0.0f;
+    if (obs)
+      for (int r = 0; r < H; ++r) total = __fadd_rn(total, __uint_as_float((unsigned)zb[r * W]));
+    a.stats[(long)b * 4 + 0] = (float)count[0];
+    a.stats[(long)b * 4 + 1] = (float)count[1];
+    a.stats[(long)b * 4 + 2] = (float)count[2];
+    a.stats[(long)b * 4 + 3] = count[2] > 0 ? __fdiv_rn(total, (float)count[2]) : 0.0f;
   }
 }
 
@@ -2188,16 +2379,53 @@ extern "C" int kpf_mano_normals_f32(const float* verts, const int* faces, int F,
   return kpf_check_launch("kpf_mano_normals_f32");
 }
 
+// The two entries of the association over the visible vertices: `name` prefixes every refusal; vert_mask is the only difference
+static int mano_assoc_vis_launch(const char* name, const float* points, const float* point_weight, const float* verts, const float* normals,
+                                 const int* vert_mask, float max_dist2, float facing_min, int* idx, float* vert_target, float* vert_weight, int* visible,
+                                 float* stats, int B, int N, void* stream) {
+  KPF_REQUIRE(points && verts && normals && idx && vert_target && vert_weight && visible && stats, "%s: null pointer", name);
+  KPF_REQUIRE(B > 0 && N >= 1 && N <= ASSOC_MAXN, "%s: bad shape B=%d N=%d (1 <= N <= %d)", name, B, N, ASSOC_MAXN);
+  KPF_REQUIRE(!(max_dist2 < 0.f) && max_dist2 == max_dist2, "%s: max_dist2=%g", name, max_dist2);
+  KPF_REQUIRE(facing_min >= 0.f && facing_min < 1.f, "%s: facing_min=%g outside [0, 1)", name, facing_min);
+  ManoAssocVisArgs a;
+  a.points = points; a.pweight = point_weight; a.verts = verts; a.normals = normals; a.vmask = vert_mask; a.max_dist2 = max_dist2;
+  a.facing_min = facing_min; a.N = N;
+  a.idx = idx; a.visible = visible; a.vtarget = vert_target; a.vweight = vert_weight; a.stats = stats;
+  hipLaunchKernelGGL(mano_assoc_vis_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch(name);
+}
+
 extern "C" int kpf_mano_assoc_vis_f32(const float* points, const float* point_weight, const float* verts, const float* normals, float max_dist2,
                                       float facing_min, int* idx, float* vert_target, float* vert_weight, int* visible, float* stats, int B, int N,
                                       void* stream) {
-  KPF_REQUIRE(points && verts && normals && idx && vert_target && vert_weight && visible && stats, "kpf_mano_assoc_vis_f32: null pointer");
-  KPF_REQUIRE(B > 0 && N >= 1 && N <= ASSOC_MAXN, "kpf_mano_assoc_vis_f32: bad shape B=%d N=%d (1 <= N <= %d)", B, N, ASSOC_MAXN);
-  KPF_REQUIRE(!(max_dist2 < 0.f) && max_dist2 == max_dist2, "kpf_mano_assoc_vis_f32: max_dist2=%g", max_dist2);
-  KPF_REQUIRE(facing_min >= 0.f && facing_min < 1.f, "kpf_mano_assoc_vis_f32: facing_min=%g outside [0, 1)", facing_min);
-  ManoAssocVisArgs a;
-  a.points = points; a.pweight = point_weight; a.verts = verts; a.normals = normals; a.max_dist2 = max_dist2; a.facing_min = facing_min; a.N = N;
-  a.idx = idx; a.visible = visible; a.vtarget = vert_target; a.vweight = vert_weight; a.stats = stats;
-  hipLaunchKernelGGL(mano_assoc_vis_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-  return kpf_check_launch("kpf_mano_assoc_vis_f32");
+  return mano_assoc_vis_launch("kpf_mano_assoc_vis_f32", points, point_weight, verts, normals, nullptr, max_dist2, facing_min, idx, vert_target, vert_weight,
+                               visible, stats, B, N, stream);
+}
+
+extern "C" int kpf_mano_assoc_vis_mask_f32(const float* points, const float* point_weight, const float* verts, const float* normals, const int* vert_mask,
+                                           float max_dist2, float facing_min, int* idx, float* vert_target, float* vert_weight, int* visible, float* stats,
+                                           int B, int N, void* stream) {
+  return mano_assoc_vis_launch("kpf_mano_assoc_vis_mask_f32", points, point_weight, verts, normals, vert_mask, max_dist2, facing_min, idx, vert_target,
+                               vert_weight, visible, stats, B, N, stream);
+}
+
+extern "C" int kpf_mano_raster_f32(const float* verts, const int* faces, int F, const float* cam, const float* M, int H, int W, float margin,
+                                   const float* depth_obs, float* depth, int* face, int* occluded, float* stats, int B, void* stream) {
+  const char* name = "kpf_mano_raster_f32";
+  KPF_REQUIRE(verts && faces && cam && depth && face && occluded && stats, "%s: null pointer", name);
+  KPF_REQUIRE(B > 0 && F >= 1 && F <= NORMALS_MAXF, "%s: bad shape B=%d F=%d (1 <= F <= %d)", name, B, F, NORMALS_MAXF);
+  KPF_REQUIRE(H >= 1 && W >= 1 && H <= RASTER_MAXPIX && W <= RASTER_MAXPIX && (long)H * W <= RASTER_MAXPIX, "%s: bad window H=%d W=%d (1 <= H, W; H * W <= %d)",
+              name, H, W, RASTER_MAXPIX);
+  KPF_REQUIRE(margin >= 0.f && isfinite(margin), "%s: margin=%g is negative or not finite", name, margin);
+  ManoRasterArgs a;
+  a.verts = verts; a.faces = faces; a.cam = cam; a.M = M; a.depth_obs = depth_obs; a.F = F; a.H = H; a.W = W; a.margin = margin;
+  a.depth = depth; a.face = face; a.occluded = occluded; a.stats = stats;
+  const size_t lds = raster_lds_bytes(H * W);
+  static std::atomic<bool> lds_opt_in[KPF_MAX_DEVICES];
+  if (lds > 64 * 1024 && !kpf_raise_lds_limit(reinterpret_cast<const void*>(&mano_raster_kernel), lds_opt_in)) {
+    kpf_set_error("%s: cannot raise the dynamic LDS limit", name);
+    return KPF_ELAUNCH;
+  }
+  hipLaunchKernelGGL(mano_raster_kernel, dim3(B), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
+  return kpf_check_launch(name);
 }

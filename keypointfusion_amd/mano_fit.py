@@ -22,7 +22,12 @@ DESIGN.md 4.14); fit_cloud(cloud_solver="gn") uses it for its vertex rounds.
 The surface: normals gives the mesh's area-weighted vertex normals from the model's faces (kpf_mano_normals_f32), associate(normals=...)
 matches the depth points to the vertices that face the camera only (kpf_mano_assoc_vis_f32), fit_mesh_gn(vert_normal=...) measures the vertex term along the
 normals (kpf_mano_fit_mesh_gn_plane_f32: one point-to-plane row per vertex, which does not punish sliding along the surface), and
-fit_cloud(metric="plane") chains the three."""
+fit_cloud(metric="plane") chains the three.
+
+Self-occlusion: render_depth is a z-buffer render of the mesh into the crop's pixel grid (kpf_mano_raster_f32: depth, owning face, the
+vertices hidden behind another part of the mesh, and the comparison with the observed depth crop), associate(vert_mask=...) keeps hidden vertices out of the
+candidates (kpf_mano_assoc_vis_mask_f32), and fit_cloud(occlusion="zbuffer") chains them; crop_camera and crop_depth_mm take the camera, the crop map and
+the observed depth from the preprocessing's outputs."""
 import torch
 
 from . import lib as L
@@ -53,6 +58,7 @@ class ManoFitter:
         self.gn_cfg = L.ManoFitGnCfg(8, 0.1, 1e-2, float(lambda_shape), float(lambda_pose), 1, (L.C.c_int * 21)(*jm))
         self.mesh_gn_cfg = L.ManoFitMeshGnCfg(*[getattr(self.gn_cfg, n) for n, _ in L.ManoFitGnCfg._fields_], 1.0)
         self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs, self._mesh_gn_bufs, self._normal_bufs = {}, {}, {}, {}, {}, {}
+        self._raster_bufs = {}
 
     def new_state(self, B):
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
@@ -288,7 +294,50 @@ class ManoFitter:
                                                   torch.cuda.current_stream().cuda_stream), "kpf_mano_normals_f32")
         return out
 
-    def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0, normals=None, facing_min=0.0):
+    def render_depth(self, verts3d, cam, M=None, size=(128, 128), margin=10.0, depth_obs=None, _slot=0):
+        """z-buffer render of the mesh into a crop's pixel grid (kpf_mano_raster_f32).  verts3d [B, 778, 3] mm in the camera frame of
+        cloud_mm; cam [B, 4] = fx, fy, u0, v0 and M [B, 2, 3], the map from frame pixels to crop coordinates (crop_camera's; None: the identity -- a render
+        into the frame's own top-left window); size = (H, W), H * W <= 16384; depth_obs [B, H, W] mm or None (crop_depth_mm's).  Crop pixel (c, r) is sampled
+        where the preprocessing back-projects it from, (c + 0.5, r + 0.5).  Two-sided, no near-plane clipping: a face with a vertex at z <= 0 is dropped.
+
+        Returns depth [B, H, W] (mm, 0 = background), face [B, H, W] int32 (the owning face, -1 = background), occluded [B, 778] int32 (1: the vertex lies more
+        than `margin` mm behind the surface that owns its nearest pixel; a vertex outside the window or on background is not occluded), stats [B, 4]
+        (covered pixels, observed pixels -- depth_obs finite and > 0 --, pixels that are both, the mean |depth - depth_obs| over those; without depth_obs
+        entries 1..3 are 0) and, with depth_obs, iou [B] = both / (covered + observed - both) (NaN when neither has a pixel).  The fitter's own tensors per
+        (B, H, W, slot); one launch, no host wait."""
+        H, W = int(size[0]), int(size[1])
+        if not (H >= 1 and W >= 1 and H * W <= 16384):
+            raise ValueError("render_depth takes 1 <= H, W and H * W <= 16384, not %d x %d" % (H, W))
+        if not (0.0 <= float(margin) < float("inf")):
+            raise ValueError("margin must be finite and >= 0, not %r" % (margin,))
+        B = int(verts3d.shape[0])
+        self._check(verts3d, (B, 778, 3), "verts3d")
+        self._check(cam, (B, 4), "cam")
+        if M is not None:
+            self._check(M, (B, 2, 3), "M")
+        if self.faces is None:
+            raise KeyError("no mano_layer.th_faces among the given tensors")
+        if depth_obs is not None:
+            self._check(depth_obs, (B, H, W), "depth_obs")
+        key = (B, H, W, _slot)
+        if key not in self._raster_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            i = lambda *s: torch.empty(*s, device=self.device, dtype=torch.int32)  # noqa: E731
+            self._raster_bufs[key] = {"depth": e(B, H, W), "face": i(B, H, W), "occluded": i(B, 778), "stats": e(B, 4)}
+        o = self._raster_bufs[key]
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_raster_f32(verts3d.data_ptr(), self.faces.data_ptr(), int(self.faces.shape[0]), cam.data_ptr(),
+                                                 None if M is None else M.data_ptr(), H, W, float(margin),
+                                                 None if depth_obs is None else depth_obs.data_ptr(), o["depth"].data_ptr(), o["face"].data_ptr(),
+                                                 o["occluded"].data_ptr(), o["stats"].data_ptr(), B, torch.cuda.current_stream().cuda_stream),
+                    "kpf_mano_raster_f32")
+        out = dict(o)
+        if depth_obs is not None:
+            st = o["stats"]
+            out["iou"] = st[:, 2] / (st[:, 0] + st[:, 1] - st[:, 2])
+        return out
+
+    def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0, normals=None, facing_min=0.0, vert_mask=None):
         """points_mm [B, N, 3] (camera-space mm, 1 <= N <= 4096), verts3d [B, 778, 3] (a fit's), point_weight [B, N] >= 0 or None (= ones), max_dist: the gate
         in mm (float("inf"): none) -> idx [B, N] int32 (each point's nearest vertex, -1 if its weight is 0, a coordinate is not finite or the vertex is
         farther than max_dist), vert_target [B, 778, 3] and vert_weight [B, 778] (per vertex the weighted centroid and the summed weight of its points; 0
@@ -296,7 +345,12 @@ class ManoFitter:
 
         normals [B, 778, 3] (normals' output): only the vertices that face the camera -- the origin of the frame -- are candidates
         (kpf_mano_assoc_vis_f32): n_v . V_v < -facing_min |V_v|, 0 <= facing_min < 1.  Also returned then: visible [B, 778] int32, and stats is [B, 4]: the
-        matched points, their mean distance to their vertex, their mean distance to that vertex's tangent plane, the visible vertices."""
+        matched points, their mean distance to their vertex, their mean distance to that vertex's tangent plane, the visible vertices.
+
+        vert_mask [B, 778] int32 (needs normals): a vertex whose entry is 0 is no candidate either (kpf_mano_assoc_vis_mask_f32) --
+        1 - render_depth's occluded; visible and stats[:, 3] report the combination.  None or all ones: the bits without it."""
+        if vert_mask is not None and normals is None:
+            raise ValueError("vert_mask needs normals")
         B, N = int(points_mm.shape[0]), int(points_mm.shape[1]) if points_mm.dim() == 3 else -1
         self._check(points_mm, (B, N, 3), "points_mm")
         self._check(verts3d, (B, 778, 3), "verts3d")
@@ -305,7 +359,7 @@ class ManoFitter:
         if not 1 <= N <= 4096:
             raise ValueError("associate takes 1 <= N <= 4096 points per hand, not %d" % N)
         if normals is not None:
-            return self._associate_vis(points_mm, verts3d, point_weight, max_dist, _slot, normals, facing_min, B, N)
+            return self._associate_vis(points_mm, verts3d, point_weight, max_dist, _slot, normals, facing_min, B, N, vert_mask)
         key = (B, N, _slot)
         if key not in self._assoc_bufs:
             e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
@@ -319,8 +373,11 @@ class ManoFitter:
                     "kpf_mano_assoc_f32")
         return dict(o)
 
-    def _associate_vis(self, points_mm, verts3d, point_weight, max_dist, _slot, normals, facing_min, B, N):
+    def _associate_vis(self, points_mm, verts3d, point_weight, max_dist, _slot, normals, facing_min, B, N, vert_mask=None):
         self._check(normals, (B, 778, 3), "normals")
+        if vert_mask is not None and not (vert_mask.is_cuda and vert_mask.dtype == torch.int32 and vert_mask.is_contiguous()
+                                          and tuple(vert_mask.shape) == (B, 778)):
+            raise ValueError("vert_mask must be a contiguous int32 [%d, 778] tensor on the device" % B)
         if not 0.0 <= float(facing_min) < 1.0:
             raise ValueError("facing_min must be in [0, 1), not %r" % (facing_min,))
         key = (B, N, _slot, "vis")
@@ -329,15 +386,18 @@ class ManoFitter:
             self._assoc_bufs[key] = {"idx": torch.empty(B, N, device=self.device, dtype=torch.int32), "vert_target": e(B, 778, 3), "vert_weight": e(B, 778),
                                      "visible": torch.empty(B, 778, device=self.device, dtype=torch.int32), "stats": e(B, 4)}
         o = self._assoc_bufs[key]
+        name = "kpf_mano_assoc_vis_f32" if vert_mask is None else "kpf_mano_assoc_vis_mask_f32"
+        extra = [] if vert_mask is None else [vert_mask.data_ptr()]
         with torch.cuda.device(self.device):
-            L.check(L.load().kpf_mano_assoc_vis_f32(points_mm.data_ptr(), None if point_weight is None else point_weight.data_ptr(), verts3d.data_ptr(),
-                                                    normals.data_ptr(), float(max_dist) * float(max_dist), float(facing_min), o["idx"].data_ptr(),
-                                                    o["vert_target"].data_ptr(), o["vert_weight"].data_ptr(), o["visible"].data_ptr(), o["stats"].data_ptr(),
-                                                    B, N, torch.cuda.current_stream().cuda_stream), "kpf_mano_assoc_vis_f32")
+            L.check(getattr(L.load(), name)(points_mm.data_ptr(), None if point_weight is None else point_weight.data_ptr(), verts3d.data_ptr(),
+                                            normals.data_ptr(), *extra, float(max_dist) * float(max_dist), float(facing_min), o["idx"].data_ptr(),
+                                            o["vert_target"].data_ptr(), o["vert_weight"].data_ptr(), o["visible"].data_ptr(), o["stats"].data_ptr(), B, N,
+                                            torch.cuda.current_stream().cuda_stream), name)
         return dict(o)
 
     def fit_cloud(self, joints_mm, points_mm, weight=None, point_weight=None, state=None, init_trans=True, rounds=3, iters_cloud=None, max_dist=20.0,
-                  lambda_verts=1.0, joint_solver="adam", cloud_solver="adam", metric="point", facing_min=0.0, normal_sign=1.0):
+                  lambda_verts=1.0, joint_solver="adam", cloud_solver="adam", metric="point", facing_min=0.0, normal_sign=1.0, occlusion=None, camera=None,
+                  raster_size=(128, 128), occlusion_margin=10.0, depth_obs=None):
         """Joints, then the depth points: one fit on the joints, then `rounds` times associate followed by fit_mesh (warm start, init_trans=False, the joints
         kept in the objective, iters_cloud iterations each; None = the fitter's), and last one associate on the final vertices: 2 * rounds + 2 launches and no
         host wait.  Returns the last fit's outputs plus cloud_before and cloud_after (the stats of the first and the last association: matched points and
@@ -348,7 +408,18 @@ class ManoFitter:
 
         metric: "point" (the above, its bits) or "plane" (needs cloud_solver="gn"): each round is normals -> associate(normals=, facing_min)
         -> fit_mesh_gn(vert_normal=), and a last normals + associate: 3 * rounds + 3 launches, no host wait.  Also returned then: normals and visible of the
-        final mesh, and cloud_before / cloud_after are the 4-wide stats.  normal_sign: normals' sign."""
+        final mesh, and cloud_before / cloud_after are the 4-wide stats.  normal_sign: normals' sign.
+
+        occlusion: None (the above, its bits) or "zbuffer" (needs metric="plane" and camera=(cam, M) as crop_camera gives them): each round
+        is normals -> render_depth(raster_size, occlusion_margin) -> associate(normals=, vert_mask=1 - occluded) -> fit_mesh_gn(vert_normal=), and a last
+        normals + render_depth(depth_obs=) + associate: 4 * rounds + 4 launches and the mask's elementwise op, no host wait.  Also returned then: depth,
+        face, occluded and depth_stats of the final mesh's render (render_depth's stats) and, with depth_obs [B, H, W] (crop_depth_mm's), iou."""
+        if occlusion not in (None, "zbuffer"):
+            raise ValueError("occlusion must be None or \"zbuffer\", not %r" % (occlusion,))
+        if occlusion == "zbuffer" and metric != "plane":
+            raise ValueError("occlusion=\"zbuffer\" needs metric=\"plane\"")
+        if occlusion == "zbuffer" and (camera is None or len(camera) != 2):
+            raise ValueError("occlusion=\"zbuffer\" needs camera=(cam, M)")
         if metric not in ("point", "plane"):
             raise ValueError("metric must be \"point\" or \"plane\", not %r" % (metric,))
         if metric == "plane" and cloud_solver != "gn":
@@ -364,17 +435,32 @@ class ManoFitter:
         state = (out["mano_pose_aa"], out["mano_shape"], out["trans"])
         first = None
         if metric == "plane":
+            zbuf = occlusion == "zbuffer"
+
+            def mask_of(verts, slot, obs=None):  # (the render, 1 - occluded) of the z-buffer, or (None, None)
+                if not zbuf:
+                    return None, None
+                ren = self.render_depth(verts, camera[0], camera[1], raster_size, occlusion_margin, depth_obs=obs, _slot=slot)
+                return ren, 1 - ren["occluded"]
+
             for r in range(int(rounds)):
                 nrm = self.normals(out["verts3d"], normal_sign)
-                a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0, normals=nrm, facing_min=facing_min)
+                _, mask = mask_of(out["verts3d"], 0)
+                a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0, normals=nrm, facing_min=facing_min,
+                                   vert_mask=mask)
                 first = a if first is None else first
                 out = self.fit_mesh_gn(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
                                        iters=2 if iters_cloud is None else iters_cloud, vert_normal=nrm)
             nrm = self.normals(out["verts3d"], normal_sign, _slot=2)
-            last = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=2, normals=nrm, facing_min=facing_min)
+            ren, mask = mask_of(out["verts3d"], 2, depth_obs)
+            last = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=2, normals=nrm, facing_min=facing_min, vert_mask=mask)
             out = dict(out)
             out.update(cloud_before=(last if first is None else first)["stats"], cloud_after=last["stats"], idx=last["idx"], vert_target=last["vert_target"],
                        vert_weight=last["vert_weight"], normals=nrm, visible=last["visible"])
+            if zbuf:
+                out.update(depth=ren["depth"], face=ren["face"], occluded=ren["occluded"], depth_stats=ren["stats"])
+                if depth_obs is not None:
+                    out["iou"] = ren["iou"]
             return out
         for r in range(int(rounds)):
             a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0)
@@ -407,3 +493,25 @@ def cloud_mm(prep):
     pts = prep["pcl"] * prep["cube"][:, None] / 2 + prep["center"][:, None]
     w = (prep["pcl_count"] > 0).to(pts.dtype)[:, None].expand(pts.shape[0], pts.shape[1]).contiguous()
     return pts.contiguous(), w
+
+
+def crop_camera(prep):
+    """The camera and the crop map of the preprocessing's outputs, as ManoFitter.render_depth and fit_cloud(camera=) take them: (cam [B, 4] float32 = fx,
+    fy, u0, v0 from prep["cam_para"], M [B, 2, 3] float32 = the top two rows of prep["M"]), device tensors.
+
+    The frame and the pixel convention: prep["M"] maps FRAME pixels (u, v, 1) to CROP coordinates (its last row is 0 0 1 -- the crop is affine), and
+    preprocess.depth_to_pcl back-projects crop pixel (column c, row r) from the crop coordinates (c + 0.5, r + 0.5) through inv(M) and then
+    x = (u - u0) / fx * d, y = (v - v0) / fy * d, z = d: cloud_mm's frame.  render_depth projects with u = x fx / z + u0, v = y fy / z + v0, applies M and
+    samples pixel (c, r) at those same crop coordinates (c + 0.5, r + 0.5), so a rendered depth, back-projected the preprocessing's way, lies on the mesh,
+    and a render can be compared pixel by pixel with crop_depth_mm."""
+    return prep["cam_para"].to(torch.float32).contiguous(), prep["M"][:, :2, :].to(torch.float32).contiguous()
+
+
+def crop_depth_mm(prep):
+    """The observed depth crop in mm, [B, H, W] float32 on the device: what render_depth(depth_obs=) and fit_cloud(depth_obs=) compare a render with.
+    preprocess.depth_to_pcl's rule: prep["img"] [B, 1, H, W] * prep["cube"][:, 2] / 2 + prep["center"][:, 2], and 0 (background: not observed) where img is
+    close to 1 by that function's test, numpy.isclose(img, 1).  Pixel (row r, column c) of the result is the crop's pixel (c, r), z along the camera axis:
+    the convention of crop_camera."""
+    img = prep["img"][:, 0].to(torch.float32)
+    d = img * (prep["cube"][:, 2].to(torch.float32) / 2)[:, None, None] + prep["center"][:, 2].to(torch.float32)[:, None, None]
+    return torch.where(torch.isclose(img, torch.ones_like(img)), torch.zeros_like(d), d).contiguous()

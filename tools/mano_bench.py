@@ -5,7 +5,9 @@ iteration = (8 - 1) / 7, the residual and history after, Adam's 10 / 50-iteratio
 with iters = 50; the Gauss-Newton mesh fit fit_mesh_gn at 0, 1, 2 and 8 iterations and the chain with six Gauss-Newton rounds of two
 iterations, Adam's figures of the same run beside them (records fit_mesh_gn_B1 / _B32, fit_cloud_gn_B1 / _B32); the vertex normals, the
 association over the camera-facing vertices and the chain with point-to-plane rounds (records normals_B1 / _B32, assoc_vis_B1 / _B32,
-fit_cloud_plane_B1 / _B32, beside fit_cloud_gn_* of the same run).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
+fit_cloud_plane_B1 / _B32, beside fit_cloud_gn_* of the same run); the z-buffer render at 128 x 128 and 32 x 32, with and without an
+observed depth crop, and the chain with the render's mask on the association (records raster_B1 / _B32, fit_cloud_zbuf_B1 / _B32, beside
+fit_cloud_plane_* of the same run).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
     python tools/mano_bench.py --reps 50
@@ -128,6 +130,44 @@ def main():
                                           "fit_mesh_gn_plane_ms_iters1": pl_ms[1], "fit_mesh_gn_plane_ms_iters8": pl_ms[8],
                                           "fit_mesh_gn_plane_ms_per_iteration": (pl_ms[8] - pl_ms[1]) / 7,
                                           "point_ms_rounds6_iters2": cloud_ms, "point_ms_per_iteration": rec["fit_mesh_gn_B%d" % B]["ms_per_iteration"]}
+        # the z-buffer render: camera (475, 475, 320, 240) and the map that puts a 250 mm square around the mesh's mean onto the window; the
+        # observed crop is the render of the neighbouring hand.  Random faces span the whole hand, so every pixel is contested: an upper figure; ms_128_local_faces is the time with faces of a real mesh's size.
+        fx, u0, v0 = 475.0, 320.0, 240.0
+        mean = vt.mean(1)
+        cam = torch.tensor([fx, fx, u0, v0], device=dev).repeat(B, 1).contiguous()
+
+        def crop_map(size):
+            sc = size / (250.0 * fx / mean[:, 2])
+            Mx = torch.zeros(B, 2, 3, device=dev)
+            Mx[:, 0, 0], Mx[:, 1, 1] = sc, sc
+            Mx[:, 0, 2] = size / 2.0 - sc * (mean[:, 0] * fx / mean[:, 2] + u0)
+            Mx[:, 1, 2] = size / 2.0 - sc * (mean[:, 1] * fx / mean[:, 2] + v0)
+            return Mx.contiguous()
+
+        M128, M32 = crop_map(128), crop_map(32)
+        # mesh-like faces: each vertex of hand 0 with its two nearest neighbours, and with its second and third -- 1556 faces a few pixels wide.  The skin
+        # is random, so another hand's neighbours are others: the batch for this figure is hand 0, B times.
+        near = torch.cdist(vt[0], vt[0]).topk(4, largest=False).indices.to(torch.int32)
+        local = ManoFitter(m, dev)
+        local.faces = torch.cat([near[:, [0, 1, 2]], near[:, [0, 2, 3]]]).contiguous()
+        v0, M0 = vt[:1].repeat(B, 1, 1).contiguous(), M128[:1].repeat(B, 1, 1).contiguous()
+        ren_local = local.render_depth(v0, cam, M0)
+        ren = fitter.render_depth(vt, cam, M128)
+        obs = torch.roll(ren["depth"], 1, 0).clone()
+        rec["raster_B%d" % B] = {"ms_128": _timed(lambda: fitter.render_depth(vt, cam, M128), args.reps, torch),
+                                 "ms_128_obs": _timed(lambda: fitter.render_depth(vt, cam, M128, depth_obs=obs), args.reps, torch),
+                                 "ms_32": _timed(lambda: fitter.render_depth(vt, cam, M32, size=(32, 32)), args.reps, torch),
+                                 "ms_128_local_faces": _timed(lambda: local.render_depth(v0, cam, M0), args.reps, torch),
+                                 "covered_128_local_faces": float(ren_local["stats"][:, 0].mean()),
+                                 "covered_128": float(ren["stats"][:, 0].mean()), "occluded": float(ren["occluded"].sum(1).float().mean()),
+                                 "faces": int(fitter.faces.shape[0]), "normals_ms": rec["normals_B%d" % B]["ms"],
+                                 "assoc_vis_ms_N1024": rec["assoc_vis_B%d" % B]["ms_N1024"]}
+        zbuf = dict(plane, occlusion="zbuffer", camera=(cam, M128), depth_obs=obs)
+        zbuf_ms = _timed(lambda: fitter.fit_cloud(y, pts, **zbuf), args.reps, torch)
+        out = fitter.fit_cloud(y, pts, **zbuf)
+        rec["fit_cloud_zbuf_B%d" % B] = {"ms_rounds6_iters2": zbuf_ms, "cloud_mm": [[float(v) for v in out[k].mean(0)] for k in ("cloud_before", "cloud_after")],
+                                         "status": sorted(set(int(v) for v in out["status"])), "depth_stats": [float(v) for v in out["depth_stats"].mean(0)],
+                                         "iou": float(out["iou"].mean()), "plane_ms_rounds6_iters2": plane_ms}
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:
