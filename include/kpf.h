@@ -1117,12 +1117,50 @@ int kpf_prep_augment_u16(const unsigned char* rgb, const unsigned short* depth, 
 int kpf_prep_aug_draw(long long* seed, int B, double sigma_com, double sigma_sc, double rot_range, double color_factor, long long seed_stride, int* mode,
                       double* off, double* sc, double* rot, double* rot_cs, double* color, void* stream);
 
+/* Device-resident MESH evaluation (ABI 32; keypointfusion_amd/evaluation_mesh_gpu.py, yardstick keypointfusion_amd/evaluation_mesh.py): the figures the
+ * HO3D / FreiHAND servers report for a predicted mesh against a ground-truth mesh of the same V vertices.  Device buffers throughout, no entry synchronises or
+ * allocates, no floating-point atomics, and the arithmetic below is part of the interface: a sample's bits depend neither on B, nor on its position in the
+ * batch, nor on a graph replay.
+ *
+ * kpf_eval_mesh_f32: pred, gt [B][V][3] float (mm); pred_origin, gt_origin [B][3] float, given together or both NULL (the root-relative protocol: each set minus
+ * its origin); thresholds [T] double, f_thresholds [Tf] double (mm).  1 <= V <= 1024, 1 <= T <= 256, 1 <= Tf <= 8, else KPF_EINVAL before the launch and
+ * nothing is written.  One 256-thread workgroup per hand; LDS 60 V bytes (both sets as float64, the logged err and nn as float32) + 320.  Leading index 0
+ * is the plain pass, 1 the aligned pass over the same buffer; the second index of nn / nn_idx is the direction, 0 pred -> gt, 1 gt -> pred.
+ *   All arithmetic in double from the float inputs, every operation individually rounded (no contraction), each result rounded ONCE to float:
+ *   a_v = (double)pred_v - (double)pred_origin, g_v = (double)gt_v - (double)gt_origin (no subtraction without origins).
+ *   err [2][B][V] float = (float)sqrt(d0*d0 + d1*d1 + d2*d2), d = a_v - g_v, summed left to right.
+ *   Every sum over vertices is ONE tree: thread t adds its vertices t, t + 256, ... in ascending order onto +0.0; the 64-lane xor butterfly (offsets 32,
+ *   16, .. 1) of each wave; then ((w0 + w1) + w2) + w3 over the four waves.  mean_err [2][B] double = tree sum of (double)err_v, divided by V.
+ *   aligned pass: the Umeyama alignment of kpf_eval_errors_f32 over all V vertices: centroids = tree sum / V; H[i][k] = tree sum of a0_i * b0_k, / V;
+ *   var = tree sum of (a0_0*a0_0 + a0_1*a0_1 + a0_2*a0_2), / V; rotation R and trace tr of H as there (8 Jacobi sweeps, signed third singular value);
+ *   scale = tr / var; a_v <- scale * (R[k][0]*a0_0 + R[k][1]*a0_1 + R[k][2]*a0_2) + centroid(g)_k.  When every predicted vertex is the same point, var and
+ *   H are 0 and scale = 0 / 0: the aligned err and mean_err of that sample are NaN, its plain figures and every other sample are unaffected.
+ *   nn, nn_idx [2][2][B][V] float / int: for every vertex of one set the nearest vertex of the other: d2 = (dx*dx + dy*dy) + dz*dz over the candidates in
+ *   ascending index with a strict <, starting from +inf (the LOWEST index wins a tie; a NaN distance never wins); nn = (float)sqrt(d2min), nn_idx = the
+ *   winner, or -1 with nn = +inf when nothing won (the aligned pass of a sample whose alignment is NaN).
+ *   pck_cnt [2][B][T] int = number of v with (double)err_v <= thresholds[t]; f_cnt [2][B][Tf][2] int = number of v with (double)nn_v <= f_thresholds[k], last
+ *   index the direction: both on the LOGGED floats; NaN and +inf never count. */
+int kpf_eval_mesh_f32(const float* pred, const float* gt, const float* pred_origin, const float* gt_origin, const double* thresholds, int T,
+                      const double* f_thresholds, int Tf, int B, int V, float* err, float* nn, int* nn_idx, double* mean_err, int* pck_cnt, int* f_cnt,
+                      void* stream);
+
+/* kpf_eval_mesh_accumulate: err, mean_err, pck_cnt, f_cnt of the call above; valid NULL or [B] bytes (0 drops a sample).  One workgroup; every state element is
+ * owned by one thread that walks the samples b = 0 .. B-1 in ascending order and skips valid == 0; a batch without a valid sample changes nothing:
+ *   n_samples [1] += valid samples, n_batches [1] += 1                                                                       (64-bit integers)
+ *   sum_mean_err [2] double: x = x + mean_err[a][b];   sum_vert [2][V] double: x = x + (double)err[a][b][v]
+ *   pck [2][T] 64-bit integers += pck_cnt[a][b][t]
+ *   sum_f [2][Tf][3] double: x = x + (F, P, R) of sample b at f_thresholds[k]: P = f_cnt[..][0] / (double)V, R = f_cnt[..][1] / (double)V,
+ *       F = (P + R > 0) ? 2.0 * P * R / (P + R) : 0.0, evaluated left to right. */
+int kpf_eval_mesh_accumulate(const float* err, const double* mean_err, const int* pck_cnt, const int* f_cnt, const unsigned char* valid, int B, int V, int T,
+                             int Tf, long long* n_samples, long long* n_batches, double* sum_mean_err, double* sum_vert, long long* pck, double* sum_f,
+                             void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 31
+#define KPF_ABI_VERSION 32
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -238,6 +238,210 @@ __global__ __launch_bounds__(EVAL_ACC_NT) void eval_accumulate_kernel(const floa
     }
   }
 }
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Mesh evaluation (keypointfusion_amd/evaluation_mesh_gpu.py): kpf_eval_mesh_f32, one 256-thread workgroup per hand, and kpf_eval_mesh_accumulate.
+// LDS of one hand, V <= 1024: the ground truth and ONE prediction set as float64 coordinate planes (2 * 3 * V * 8 = 48 KiB), the logged float32 err [V]
+// and nn [2][V] (12 KiB) that the counts are taken on, and 4 x 10 doubles of reduction scratch: the plain pass runs, then the aligned set overwrites the
+// prediction planes and the same pass runs again.
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+constexpr int MESH_NT = 256, MESH_WAVES = MESH_NT / 64;
+constexpr int MESH_MAX_V = 1024, MESH_MAX_T = 256, MESH_MAX_TF = 8;  // a thread owns vertices t, t + 256, ...: at most 4
+
+// The fixed tree of every sum over vertices: part[k] = thread t's vertices t, t + 256, ... added in ascending order onto +0.0 (the caller's loop), then the
+// 64-lane butterfly, then the four waves' sums in wave order.  Every thread returns with the same bits in part[].
+template <int N>
+__device__ __forceinline__ void mesh_block_sum(double (&part)[N], double (*scratch)[10]) {
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double w = eval_wave_sum(part[k]);
+    if ((threadIdx.x & 63) == 0) scratch[wave][k] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) part[k] = ((scratch[0][k] + scratch[1][k]) + scratch[2][k]) + scratch[3][k];
+  __syncthreads();  // scratch is free again
+}
+
+// Nearest vertex of the set (sx, sy, sz) for this thread's vertices of the set (qx, qy, qz): candidates in ascending index, strict <, from +inf.  All lanes
+// read candidate j at one address (an LDS broadcast); the thread's NB vertices sit in registers.  A NaN distance never wins.
+template <int NB>
+__device__ __forceinline__ void mesh_nearest(const double* qx, const double* qy, const double* qz, const double* sx, const double* sy, const double* sz, int V,
+                                             float* __restrict__ nn_out, int* __restrict__ idx_out, float* nn_lds) {
+  const int tid = threadIdx.x;
+  double x[NB], y[NB], z[NB], best[NB];
+  int idx[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int v = tid + i * MESH_NT;
+    const bool on = v < V;
+    x[i] = on ? qx[v] : 0.0, y[i] = on ? qy[v] : 0.0, z[i] = on ? qz[v] : 0.0;
+    best[i] = __builtin_inf();
+    idx[i] = -1;
+  }
+  for (int j = 0; j < V; ++j) {
+    const double cx = sx[j], cy = sy[j], cz = sz[j];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const double dx = x[i] - cx, dy = y[i] - cy, dz = z[i] - cz;
+      const double d2 = (dx * dx + dy * dy) + dz * dz;
+      if (d2 < best[i]) best[i] = d2, idx[i] = j;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int v = tid + i * MESH_NT;
+    if (v < V) {
+      const float d = (float)sqrt(best[i]);
+      nn_out[v] = d, idx_out[v] = idx[i], nn_lds[v] = d;
+    }
+  }
+}
+
+__device__ __forceinline__ void mesh_nearest_n(int nb, const double* qx, const double* qy, const double* qz, const double* sx, const double* sy,
+                                               const double* sz, int V, float* nn_out, int* idx_out, float* nn_lds) {
+  switch (nb) {  // ceil(V / 256), the same for every thread
+    case 1: mesh_nearest<1>(qx, qy, qz, sx, sy, sz, V, nn_out, idx_out, nn_lds); break;
+    case 2: mesh_nearest<2>(qx, qy, qz, sx, sy, sz, V, nn_out, idx_out, nn_lds); break;
+    case 3: mesh_nearest<3>(qx, qy, qz, sx, sy, sz, V, nn_out, idx_out, nn_lds); break;
+    default: mesh_nearest<4>(qx, qy, qz, sx, sy, sz, V, nn_out, idx_out, nn_lds); break;
+  }
+}
+
+__global__ __launch_bounds__(MESH_NT) void eval_mesh_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ pred_origin,
+                                                            const float* __restrict__ gt_origin, const double* __restrict__ th, int T,
+                                                            const double* __restrict__ fth, int Tf, int B, int V, float* __restrict__ err,
+                                                            float* __restrict__ nn, int* __restrict__ nn_idx, double* __restrict__ mean_err,
+                                                            int* __restrict__ pck_cnt, int* __restrict__ f_cnt) {
+  extern __shared__ double mesh_lds[];  // g [3][V], p [3][V] double; then err [V], nn [2][V] float
+  __shared__ double scratch[MESH_WAVES][10];
+  const int b = blockIdx.x, tid = threadIdx.x, nb = (V + MESH_NT - 1) / MESH_NT;
+  double *gx = mesh_lds, *gy = gx + V, *gz = gy + V, *px = gz + V, *py = px + V, *pz = py + V;
+  float* e_lds = reinterpret_cast<float*>(pz + V);
+  float* n_lds = e_lds + V;
+  const float* P = pred + (size_t)b * V * 3;
+  const float* G = gt + (size_t)b * V * 3;
+  double po[3] = {0.0, 0.0, 0.0}, go[3] = {0.0, 0.0, 0.0};
+  if (pred_origin)  // both or neither (checked on the host)
+    for (int k = 0; k < 3; ++k) po[k] = (double)pred_origin[3 * b + k], go[k] = (double)gt_origin[3 * b + k];
+  for (int v = tid; v < V; v += MESH_NT) {
+    px[v] = (double)P[3 * v] - po[0], py[v] = (double)P[3 * v + 1] - po[1], pz[v] = (double)P[3 * v + 2] - po[2];
+    gx[v] = (double)G[3 * v] - go[0], gy[v] = (double)G[3 * v + 1] - go[1], gz[v] = (double)G[3 * v + 2] - go[2];
+  }
+  __syncthreads();
+  const size_t BV = (size_t)B * V;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) {  // the Umeyama alignment of eval_errors_kernel over the V vertices; the aligned set replaces p
+      const double n = (double)V;
+      double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int v = tid; v < V; v += MESH_NT) c[0] += px[v], c[1] += py[v], c[2] += pz[v], c[3] += gx[v], c[4] += gy[v], c[5] += gz[v];
+      mesh_block_sum(c, scratch);
+      for (int k = 0; k < 6; ++k) c[k] = c[k] / n;
+      double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int v = tid; v < V; v += MESH_NT) {
+        const double a0[3] = {px[v] - c[0], py[v] - c[1], pz[v] - c[2]}, b0[3] = {gx[v] - c[3], gy[v] - c[4], gz[v] - c[5]};
+        for (int i = 0; i < 3; ++i)
+          for (int k = 0; k < 3; ++k) s[3 * i + k] += a0[i] * b0[k];
+        s[9] += a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2];
+      }
+      mesh_block_sum(s, scratch);
+      double H[3][3], R[3][3], tr;
+      for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) H[i][k] = s[3 * i + k] / n;
+      const double var = s[9] / n;
+      eval_umeyama_rotation(H, R, &tr);  // every thread holds the same H
+      const double scale = tr / var;     // 0 / 0 = NaN when every predicted vertex is the same point
+      for (int v = tid; v < V; v += MESH_NT) {  // each thread rewrites its own vertices only
+        const double a0[3] = {px[v] - c[0], py[v] - c[1], pz[v] - c[2]};
+        px[v] = scale * (R[0][0] * a0[0] + R[0][1] * a0[1] + R[0][2] * a0[2]) + c[3];
+        py[v] = scale * (R[1][0] * a0[0] + R[1][1] * a0[1] + R[1][2] * a0[2]) + c[4];
+        pz[v] = scale * (R[2][0] * a0[0] + R[2][1] * a0[1] + R[2][2] * a0[2]) + c[5];
+      }
+      __syncthreads();
+    }
+    // per-vertex error and its mean
+    double m[1] = {0.0};
+    float* e_out = err + pass * BV + (size_t)b * V;
+    for (int v = tid; v < V; v += MESH_NT) {
+      const double d0 = px[v] - gx[v], d1 = py[v] - gy[v], d2 = pz[v] - gz[v];
+      const float e = (float)sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+      e_out[v] = e, e_lds[v] = e;
+      m[0] += (double)e;
+    }
+    mesh_block_sum(m, scratch);
+    if (tid == 0) mean_err[(size_t)pass * B + b] = m[0] / (double)V;
+    // nearest vertices, both directions
+    const size_t o0 = ((size_t)pass * 2 + 0) * BV + (size_t)b * V, o1 = ((size_t)pass * 2 + 1) * BV + (size_t)b * V;
+    mesh_nearest_n(nb, px, py, pz, gx, gy, gz, V, nn + o0, nn_idx + o0, n_lds);
+    mesh_nearest_n(nb, gx, gy, gz, px, py, pz, V, nn + o1, nn_idx + o1, n_lds + V);
+    __syncthreads();
+    // counts on the logged values: every count is owned by one thread that walks the vertices (all lanes read one address)
+    for (int it = tid; it < T + 2 * Tf; it += MESH_NT) {
+      int cnt = 0;
+      if (it < T) {
+        const double thr = th[it];
+        for (int v = 0; v < V; ++v) cnt += ((double)e_lds[v] <= thr) ? 1 : 0;
+        pck_cnt[((size_t)pass * B + b) * T + it] = cnt;
+      } else {
+        const int r = it - T, k = r >> 1, dir = r & 1;
+        const double thr = fth[k];
+        const float* d = n_lds + dir * V;
+        for (int v = 0; v < V; ++v) cnt += ((double)d[v] <= thr) ? 1 : 0;
+        f_cnt[(((size_t)pass * B + b) * Tf + k) * 2 + dir] = cnt;
+      }
+    }
+    __syncthreads();  // e_lds / n_lds are rewritten by the next pass
+  }
+}
+
+// One workgroup; every state element is owned by one thread that walks the samples in ascending order and skips valid == 0.
+__global__ __launch_bounds__(MESH_NT) void eval_mesh_accumulate_kernel(const float* __restrict__ err, const double* __restrict__ mean_err,
+                                                                       const int* __restrict__ pck_cnt, const int* __restrict__ f_cnt,
+                                                                       const unsigned char* __restrict__ valid, int B, int V, int T, int Tf,
+                                                                       long long* __restrict__ n_samples, long long* __restrict__ n_batches,
+                                                                       double* __restrict__ sum_mean_err, double* __restrict__ sum_vert,
+                                                                       long long* __restrict__ pck, double* __restrict__ sum_f) {
+  const int n_vert = 2 * V, n_pck = 2 * T, n_f = 2 * Tf * 3, n_items = n_vert + n_pck + n_f + 2 + 1;
+  for (int it = threadIdx.x; it < n_items; it += MESH_NT) {
+    if (it < n_vert) {  // sum_vert [2][V]
+      const int a = it / V, v = it - a * V;
+      double acc = sum_vert[it];
+      for (int b = 0; b < B; ++b)
+        if (!valid || valid[b]) acc += (double)err[((size_t)a * B + b) * V + v];
+      sum_vert[it] = acc;
+    } else if (it < n_vert + n_pck) {  // pck [2][T]
+      const int r = it - n_vert, a = r / T, t = r - a * T;
+      long long c = 0;
+      for (int b = 0; b < B; ++b)
+        if (!valid || valid[b]) c += pck_cnt[((size_t)a * B + b) * T + t];
+      pck[r] += c;
+    } else if (it < n_vert + n_pck + n_f) {  // sum_f [2][Tf][3]: F, P, R of every sample
+      const int r = it - n_vert - n_pck, a = r / (Tf * 3), q = r - a * Tf * 3, k = q / 3, which = q - 3 * k;
+      double acc = sum_f[r];
+      for (int b = 0; b < B; ++b)
+        if (!valid || valid[b]) {
+          const int* h = f_cnt + (((size_t)a * B + b) * Tf + k) * 2;
+          const double Pr = (double)h[0] / (double)V, Rc = (double)h[1] / (double)V;
+          const double F = (Pr + Rc > 0.0) ? 2.0 * Pr * Rc / (Pr + Rc) : 0.0;
+          acc += which == 0 ? F : which == 1 ? Pr : Rc;
+        }
+      sum_f[r] = acc;
+    } else if (it < n_vert + n_pck + n_f + 2) {  // sum_mean_err [2]
+      const int a = it - n_vert - n_pck - n_f;
+      double acc = sum_mean_err[a];
+      for (int b = 0; b < B; ++b)
+        if (!valid || valid[b]) acc += mean_err[(size_t)a * B + b];
+      sum_mean_err[a] = acc;
+    } else {  // the counters
+      long long nv = 0;
+      for (int b = 0; b < B; ++b) nv += (!valid || valid[b]) ? 1 : 0;
+      if (nv > 0) {
+        *n_samples += nv;
+        *n_batches += 1;
+      }
+    }
+  }
+}
 #endif  // __HIPCC__
 
 }  // namespace
@@ -273,4 +477,32 @@ extern "C" int kpf_eval_accumulate(const float* err, const unsigned char* valid,
   hipLaunchKernelGGL(eval_accumulate_kernel, dim3(S), dim3(EVAL_ACC_NT), lds, ST(stream), err, valid, thresholds, S, B, Jsel, T, n_samples, n_batches, sum_err,
                      sum_pa, sum_batch_mean, sum_batch_pa_mean, pck, pck_pa);
   return kpf_check_launch("kpf_eval_accumulate");
+}
+
+extern "C" int kpf_eval_mesh_f32(const float* pred, const float* gt, const float* pred_origin, const float* gt_origin, const double* thresholds, int T,
+                                 const double* f_thresholds, int Tf, int B, int V, float* err, float* nn, int* nn_idx, double* mean_err, int* pck_cnt,
+                                 int* f_cnt, void* stream) {
+  KPF_REQUIRE(pred && gt && thresholds && f_thresholds && err && nn && nn_idx && mean_err && pck_cnt && f_cnt, "kpf_eval_mesh_f32: null pointer argument");
+  KPF_REQUIRE((pred_origin != nullptr) == (gt_origin != nullptr), "kpf_eval_mesh_f32: pred_origin and gt_origin are given together or both NULL");
+  KPF_REQUIRE(V >= 1 && V <= MESH_MAX_V, "kpf_eval_mesh_f32: V = %d vertices (1 .. %d: two float64 sets in LDS)", V, MESH_MAX_V);
+  KPF_REQUIRE(T >= 1 && T <= MESH_MAX_T, "kpf_eval_mesh_f32: T = %d thresholds (1 .. %d)", T, MESH_MAX_T);
+  KPF_REQUIRE(Tf >= 1 && Tf <= MESH_MAX_TF, "kpf_eval_mesh_f32: Tf = %d F-score thresholds (1 .. %d)", Tf, MESH_MAX_TF);
+  KPF_REQUIRE(B >= 1 && (long)B * V < (1L << 28), "kpf_eval_mesh_f32: bad shape (B %d, V %d)", B, V);
+  const size_t lds = (size_t)V * (6 * sizeof(double) + 3 * sizeof(float));  // <= 60 KiB, + 320 bytes static
+  hipLaunchKernelGGL(eval_mesh_kernel, dim3(B), dim3(MESH_NT), lds, ST(stream), pred, gt, pred_origin, gt_origin, thresholds, T, f_thresholds, Tf, B, V, err, nn,
+                     nn_idx, mean_err, pck_cnt, f_cnt);
+  return kpf_check_launch("kpf_eval_mesh_f32");
+}
+
+extern "C" int kpf_eval_mesh_accumulate(const float* err, const double* mean_err, const int* pck_cnt, const int* f_cnt, const unsigned char* valid, int B, int V,
+                                        int T, int Tf, long long* n_samples, long long* n_batches, double* sum_mean_err, double* sum_vert, long long* pck,
+                                        double* sum_f, void* stream) {
+  KPF_REQUIRE(err && mean_err && pck_cnt && f_cnt && n_samples && n_batches && sum_mean_err && sum_vert && pck && sum_f,
+              "kpf_eval_mesh_accumulate: null pointer argument");
+  KPF_REQUIRE(V >= 1 && V <= MESH_MAX_V && T >= 1 && T <= MESH_MAX_T && Tf >= 1 && Tf <= MESH_MAX_TF,
+              "kpf_eval_mesh_accumulate: bad shape (V %d of 1 .. %d, T %d of 1 .. %d, Tf %d of 1 .. %d)", V, MESH_MAX_V, T, MESH_MAX_T, Tf, MESH_MAX_TF);
+  KPF_REQUIRE(B >= 1 && (long)B * V < (1L << 28), "kpf_eval_mesh_accumulate: bad shape (B %d, V %d)", B, V);
+  hipLaunchKernelGGL(eval_mesh_accumulate_kernel, dim3(1), dim3(MESH_NT), 0, ST(stream), err, mean_err, pck_cnt, f_cnt, valid, B, V, T, Tf, n_samples, n_batches,
+                     sum_mean_err, sum_vert, pck, sum_f);
+  return kpf_check_launch("kpf_eval_mesh_accumulate");
 }

@@ -19,7 +19,9 @@ A sample whose predicted joints all coincide has no similarity alignment: its al
 and so are the aligned sums from then on; the plain figures are unaffected.  Under stream capture, and on a host whose `torch.linalg.inv` follows neither known
 rounding order (`inv3x3.host_mode() < 0`), M^-1 is computed on the device in the separately rounded order: M never leaves the device here.
 
-Not reproduced: the STB translation-only alignment (train.py:349-352, which indexes the batch rather than the joint), `z2error`, and the MANO / mesh dump.
+Not reproduced: the STB translation-only alignment (train.py:349-352, which indexes the batch rather than the joint) and `z2error`.  The mesh is scored by
+`evaluation_mesh_gpu.DeviceMeshEvaluator` (vertex errors, Procrustes, F-scores, vertex PCK: what the challenge server derives from the reference's mesh
+dump); the json dump itself is not written.
 """
 import ctypes as C
 

@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 31  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 32  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -235,6 +235,8 @@ _SIGS = {
     "kpf_track_step_f32": [_P] * 6 + [C.c_int] * 4 + [C.c_float, C.c_longlong] + [_P] * 9,
     "kpf_eval_errors_f32": [C.POINTER(C.c_void_p), C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P],
     "kpf_eval_accumulate": [_P, _P, _P] + [C.c_int] * 4 + [_P] * 9,
+    "kpf_eval_mesh_f32": [_P] * 5 + [C.c_int, _P] + [C.c_int] * 3 + [_P] * 7,
+    "kpf_eval_mesh_accumulate": [_P] * 5 + [C.c_int] * 4 + [_P] * 7,
 }
 _LONG_SIGS = {  # entries returning a long
     "kpf_cbam_workspace_floats": [C.c_int, C.c_int, C.c_int],

@@ -7,7 +7,8 @@ iterations, Adam's figures of the same run beside them (records fit_mesh_gn_B1 /
 association over the camera-facing vertices and the chain with point-to-plane rounds (records normals_B1 / _B32, assoc_vis_B1 / _B32,
 fit_cloud_plane_B1 / _B32, beside fit_cloud_gn_* of the same run); the z-buffer render at 128 x 128 and 32 x 32, with and without an
 observed depth crop, and the chain with the render's mask on the association (records raster_B1 / _B32, fit_cloud_zbuf_B1 / _B32, beside
-fit_cloud_plane_* of the same run).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
+fit_cloud_plane_* of the same run); the mesh evaluation evaluation_mesh_gpu.DeviceMeshEvaluator.update at V = 778 and beside it the same
+figures as torch ops on the device with one .cpu() per batch (records mesh_eval_B1 / _B32).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
     python tools/mano_bench.py --reps 50
@@ -168,6 +169,33 @@ def main():
         rec["fit_cloud_zbuf_B%d" % B] = {"ms_rounds6_iters2": zbuf_ms, "cloud_mm": [[float(v) for v in out[k].mean(0)] for k in ("cloud_before", "cloud_after")],
                                          "status": sorted(set(int(v) for v in out["status"])), "depth_stats": [float(v) for v in out["depth_stats"].mean(0)],
                                          "iou": float(out["iou"].mean()), "plane_ms_rounds6_iters2": plane_ms}
+    # the mesh evaluation: the fitted hands scored against the hands 2 mm away; beside it the same figures as torch ops
+    from keypointfusion_amd.evaluation import similarity_align
+    from keypointfusion_amd.evaluation_mesh_gpu import DeviceMeshEvaluator
+    gt_all = (verts + 2.0 * torch.randn(32, 778, 3, generator=gen).to(dev)).contiguous()
+    for B in (1, 32):
+        ev = DeviceMeshEvaluator()
+        pv, gv = verts[:B].contiguous(), gt_all[:B].contiguous()
+        th, taus = torch.from_numpy(ev.thresholds).to(dev), ev.f_thresholds
+
+        def torch_figures():
+            out = []
+            for a in (pv.double(), similarity_align(pv.double(), gv.double())):
+                d = torch.cdist(a, gv.double())
+                e = (a - gv.double()).norm(dim=-1)
+                d_pg, d_gp = d.min(2).values, d.min(1).values
+                f = [((d_pg <= t).double().mean(1), (d_gp <= t).double().mean(1)) for t in taus]
+                out += [e.mean(1), (e[..., None] <= th).sum((0, 1)).double()] + [2 * p * r / (p + r).clamp_min(1e-300) for p, r in f]
+            return torch.cat([o.reshape(-1) for o in out]).cpu()
+
+        ms = _timed(lambda: ev.update(pv, gv), args.reps, torch)
+        ev.reset()
+        ev.update(pv, gv)
+        summ, ref = ev.summary(), torch_figures()
+        rec["mesh_eval_B%d" % B] = {"ms_update": ms, "ms_torch_ops": _timed(torch_figures, args.reps, torch), "verts": 778,
+                                    "mean_error_mm": summ["mean_error"], "pa_mean_error_mm": summ["pa_mean_error"],
+                                    "f_score": {str(t): summ["f_score"][t] for t in taus}, "pa_f_score": {str(t): summ["pa_f_score"][t] for t in taus},
+                                    "auc": summ["auc"], "torch_mean_error_mm": float(ref[:B].mean()), "fit_gn_ms_iters8": rec["fit_gn_B%d" % B]["ms_iters8"]}
     line = json.dumps(rec)
     print(line, flush=True)
     if args.out:
