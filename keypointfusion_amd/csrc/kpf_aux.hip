@@ -1,7 +1,7 @@
 // Stand-alone heads of the reference that KPFusion.forward does not call but the north star names:
 //   CBAM channel / spatial gates   (model/cbam.py:26-94)            -> pool, gate, compress, spatial-gate, apply kernels
 //   Hourglass glue                 (model/hourglass.py:122-149)     -> 2x2 max-pool, nearest-x2 upsample fused with the skip add
-//   (the MANO layer of a19 is csrc/kpf_mano.hip)
+//   (the MANO layer of a19 is csrc/kpf_mano.hip; its fits and surface entries are csrc/kpf_mano_fit.hip and csrc/kpf_mano_surface.hip)
 // All HBM-bound elementwise / reduction work on NHWC activations (channel quads contiguous -> 16-byte lanes, coalesced).
 #include <math.h>
 

@@ -1,4 +1,5 @@
-"""Joints to mesh: fit the MANO layer's pose, shape and a translation to 21 camera-space joints per hand — kpf_mano_fit_f32 (csrc/kpf_mano.hip).
+"""Joints to mesh: fit the MANO layer's pose, shape and a translation to 21 camera-space joints per hand — kpf_mano_fit_f32 (csrc/kpf_mano_fit.hip; the surface entries are in
+csrc/kpf_mano_surface.hip).
 The fit of one hand is independent of every other, so one workgroup runs all Adam iterations of one sample inside a single launch: state, moments and the
 recomputed hand model stay on chip, and a call is one launch with no host wait and no device -> host copy (it can be captured in torch.cuda.graph).
 
@@ -64,12 +65,34 @@ class ManoFitter:
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
         return tuple(torch.zeros(B, n, device=self.device, dtype=torch.float32) for n in (48, 10, 3))
 
-    def _buffers(self, B):
-        if B not in self._bufs:  # static per batch size: a captured graph keeps writing where it was captured
+    def _fit_buffers(self, cache, B, res_w, **more):
+        """A fit method's own outputs for batch size B, from its own cache (static per batch size: a captured graph keeps writing where it was captured).
+        more: further entries of a new record (the Gauss-Newton methods' history={})."""
+        if B not in cache:
             e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
-            self._bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 2),
-                             "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B)}
-        return self._bufs[B]
+            cache[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, res_w),
+                        "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B), **more}
+        return cache[B]
+
+    def _take_state(self, o, state, B):
+        """The caller's state, checked, or (None) the method's own, zeroed: the cold start."""
+        if state is None:
+            state = o["state"]
+            for s in state:
+                s.zero_()
+        self._check_state(state, B)
+        return state
+
+    @staticmethod
+    def _out_ptrs(o):
+        return [o[k].data_ptr() for k in ("verts3d", "joints3d", "mano_pose", "residual", "status")]
+
+    @staticmethod
+    def _fit_result(o, state, **extra):
+        out = {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": state[0], "mano_shape": state[1], "trans": state[2],
+               "mano_pose": o["mano_pose"], "residual": o["residual"], "status": o["status"]}
+        out.update(extra)
+        return out
 
     def fit(self, joints_mm, weight=None, state=None, init_trans=True):
         """joints_mm [B, 21, 3] float32 on the device (mm, camera space), weight [B, 21] >= 0 or None (= ones).  state: None (start from zeros, in the
@@ -83,27 +106,17 @@ class ManoFitter:
         it was and the outputs evaluate it).  The output tensors are the fitter's own, overwritten by the next call of the same batch size."""
         y = joints_mm
         B = y.shape[0]
-        if not (y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and tuple(y.shape) == (B, 21, 3)):
-            raise ValueError("joints_mm must be a contiguous float32 [B, 21, 3] tensor on the device")
-        if weight is not None and not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous() and tuple(weight.shape) == (B, 21)):
-            raise ValueError("weight must be a contiguous float32 [B, 21] tensor on the device")
-        o = self._buffers(B)
-        if state is None:
-            state = o["state"]
-            for s in state:
-                s.zero_()
-        pose, betas, trans = state
-        for s, n in zip(state, (48, 10, 3)):
-            if not (s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and tuple(s.shape) == (B, n)):
-                raise ValueError("state must be contiguous float32 tensors [B, 48], [B, 10], [B, 3] on the device")
+        self._check(y, (B, 21, 3), "joints_mm", "[B, 21, 3]")
+        if weight is not None:
+            self._check(weight, (B, 21), "weight", "[B, 21]")
+        o = self._fit_buffers(self._bufs, B, 2)
+        state = self._take_state(o, state, B)
         self.cfg.init_trans = 1 if init_trans else 0
         with torch.cuda.device(self.device):
             L.check(L.load().kpf_mano_fit_f32(y.data_ptr(), None if weight is None else weight.data_ptr(), *[m.data_ptr() for m in self.model],
-                                              L.C.byref(self.cfg), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
-                                              o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(), B,
+                                              L.C.byref(self.cfg), *[s.data_ptr() for s in state], *self._out_ptrs(o), B,
                                               torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_f32")
-        return {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
-                "residual": o["residual"], "status": o["status"]}
+        return self._fit_result(o, state)
 
     def fit_gn(self, joints_mm, weight=None, state=None, init_trans=True, iters=None, mu=0.1, nu=1e-2, jacobian=False):
         """fit by damped Gauss-Newton (kpf_mano_fit_gn_f32): the same objective, state, targets, weights, joint_map and status convention,
@@ -122,35 +135,21 @@ class ManoFitter:
         n = 8 if iters is None else int(iters)
         if not 0 <= n <= 64:
             raise ValueError("fit_gn takes 0 <= iters <= 64, not %d" % n)
-        if B not in self._gn_bufs:
-            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
-            self._gn_bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 2),
-                                "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B), "history": {}}
-        o = self._gn_bufs[B]
+        o = self._fit_buffers(self._gn_bufs, B, 2, history={})
         if n not in o["history"]:
             o["history"][n] = torch.empty(B, n + 1, device=self.device, dtype=torch.float32)
         if jacobian and "jacobian" not in o:
             o["jacobian"] = torch.empty(B, 63, 61, device=self.device, dtype=torch.float32)
         hist = o["history"][n]
-        if state is None:
-            state = o["state"]
-            for s in state:
-                s.zero_()
-        pose, betas, trans = state
-        self._check_state(state, B)
+        state = self._take_state(o, state, B)
         c = self.gn_cfg
         c.iters, c.mu, c.nu, c.init_trans = n, float(mu), float(nu), 1 if init_trans else 0
         with torch.cuda.device(self.device):
             L.check(L.load().kpf_mano_fit_gn_f32(joints_mm.data_ptr(), None if weight is None else weight.data_ptr(), *[m.data_ptr() for m in self.model],
-                                                 L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
-                                                 o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(),
-                                                 hist.data_ptr(), o["jacobian"].data_ptr() if jacobian else None, B,
-                                                 torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_gn_f32")
-        out = {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
-               "residual": o["residual"], "status": o["status"], "history": hist}
-        if jacobian:
-            out["jacobian"] = o["jacobian"]
-        return out
+                                                 L.C.byref(c), *[s.data_ptr() for s in state], *self._out_ptrs(o), hist.data_ptr(),
+                                                 o["jacobian"].data_ptr() if jacobian else None, B, torch.cuda.current_stream().cuda_stream),
+                    "kpf_mano_fit_gn_f32")
+        return self._fit_result(o, state, history=hist, **({"jacobian": o["jacobian"]} if jacobian else {}))
 
     def _check_state(self, state, B):
         for s, n in zip(state, (48, 10, 3)):
@@ -158,9 +157,9 @@ class ManoFitter:
                 raise ValueError("state must be contiguous float32 tensors [B, 48], [B, 10], [B, 3] on the device")
 
     @staticmethod
-    def _check(t, shape, name):
+    def _check(t, shape, name, said=None):  # said: how the refusal writes the shape (fit's says B), else the numbers
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
-            raise ValueError("%s must be a contiguous float32 %s tensor on the device" % (name, list(shape)))
+            raise ValueError("%s must be a contiguous float32 %s tensor on the device" % (name, said or list(shape)))
 
     def fit_mesh(self, joints_mm=None, weight=None, vert_target=None, vert_weight=None, state=None, init_trans=True, lambda_verts=1.0, iters=None):
         """fit with a vertex term: + lambda_verts (1 / sum u) sum_v u_v |V_v + t - c_v|^2, vert_target c [B, 778, 3] in mm and vert_weight u [B, 778] >= 0
@@ -181,17 +180,8 @@ class ManoFitter:
         if vert_target is not None:
             self._check(vert_target, (B, 778, 3), "vert_target")
             self._check(vert_weight, (B, 778), "vert_weight")
-        if B not in self._mesh_bufs:
-            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
-            self._mesh_bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 4),
-                                  "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B)}
-        o = self._mesh_bufs[B]
-        if state is None:
-            state = o["state"]
-            for s in state:
-                s.zero_()
-        pose, betas, trans = state
-        self._check_state(state, B)
+        o = self._fit_buffers(self._mesh_bufs, B, 4)
+        state = self._take_state(o, state, B)
         c = self.mesh_cfg
         c.iters = self.cfg.iters if iters is None else int(iters)
         c.init_trans = 1 if init_trans else 0
@@ -199,11 +189,9 @@ class ManoFitter:
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         with torch.cuda.device(self.device):
             L.check(L.load().kpf_mano_fit_mesh_f32(ptr(joints_mm), ptr(weight), ptr(vert_target), ptr(vert_weight), *[m.data_ptr() for m in self.model],
-                                                   L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
-                                                   o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(), B,
+                                                   L.C.byref(c), *[s.data_ptr() for s in state], *self._out_ptrs(o), B,
                                                    torch.cuda.current_stream().cuda_stream), "kpf_mano_fit_mesh_f32")
-        return {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
-                "residual": o["residual"], "status": o["status"]}
+        return self._fit_result(o, state)
 
     def fit_mesh_gn(self, joints_mm=None, weight=None, vert_target=None, vert_weight=None, state=None, init_trans=True, lambda_verts=1.0, iters=None,
                     mu=0.1, nu=1e-2, jacobian=False, vert_normal=None):
@@ -238,23 +226,14 @@ class ManoFitter:
         n = 8 if iters is None else int(iters)
         if not 0 <= n <= 64:
             raise ValueError("fit_mesh_gn takes 0 <= iters <= 64, not %d" % n)
-        if B not in self._mesh_gn_bufs:
-            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
-            self._mesh_gn_bufs[B] = {"verts3d": e(B, 778, 3), "joints3d": e(B, 21, 3), "mano_pose": e(B, 16, 3, 3), "residual": e(B, 4),
-                                     "status": torch.empty(B, device=self.device, dtype=torch.int32), "state": self.new_state(B), "history": {}}
-        o = self._mesh_gn_bufs[B]
+        o = self._fit_buffers(self._mesh_gn_bufs, B, 4, history={})
         if n not in o["history"]:
             o["history"][n] = torch.empty(B, n + 1, 2, device=self.device, dtype=torch.float32)
         if jacobian and "jacobian" not in o:
             o["jacobian"] = torch.empty(B, 63, 61, device=self.device, dtype=torch.float32)
             o["vert_jacobian"] = torch.zeros(B, 2334, 61, device=self.device, dtype=torch.float32)
         hist = o["history"][n]
-        if state is None:
-            state = o["state"]
-            for s in state:
-                s.zero_()
-        pose, betas, trans = state
-        self._check_state(state, B)
+        state = self._take_state(o, state, B)
         c = self.mesh_gn_cfg
         c.iters, c.mu, c.nu, c.init_trans, c.lambda_verts = n, float(mu), float(nu), 1 if init_trans else 0, float(lambda_verts)
         if jacobian and vert_target is None:
@@ -264,16 +243,11 @@ class ManoFitter:
         extra = [] if vert_normal is None else [vert_normal.data_ptr()]
         with torch.cuda.device(self.device):
             L.check(getattr(L.load(), name)(ptr(joints_mm), ptr(weight), ptr(vert_target), ptr(vert_weight), *extra, *[m.data_ptr() for m in self.model],
-                                            L.C.byref(c), pose.data_ptr(), betas.data_ptr(), trans.data_ptr(), o["verts3d"].data_ptr(),
-                                            o["joints3d"].data_ptr(), o["mano_pose"].data_ptr(), o["residual"].data_ptr(), o["status"].data_ptr(),
-                                            hist.data_ptr(), o["jacobian"].data_ptr() if jacobian else None,
+                                            L.C.byref(c), *[s.data_ptr() for s in state], *self._out_ptrs(o), hist.data_ptr(),
+                                            o["jacobian"].data_ptr() if jacobian else None,
                                             o["vert_jacobian"].data_ptr() if jacobian and vert_target is not None else None, B,
                                             torch.cuda.current_stream().cuda_stream), name)
-        out = {"verts3d": o["verts3d"], "joints3d": o["joints3d"], "mano_pose_aa": pose, "mano_shape": betas, "trans": trans, "mano_pose": o["mano_pose"],
-               "residual": o["residual"], "status": o["status"], "history": hist}
-        if jacobian:
-            out["jacobian"], out["vert_jacobian"] = o["jacobian"], o["vert_jacobian"]
-        return out
+        return self._fit_result(o, state, history=hist, **({"jacobian": o["jacobian"], "vert_jacobian": o["vert_jacobian"]} if jacobian else {}))
 
     def normals(self, verts3d, sign=1.0, _slot=0):
         """verts3d [B, 778, 3] -> the area-weighted unit vertex normals [B, 778, 3] by the model's faces (th_faces, F <= 2048): sign * normalize(the sum of
