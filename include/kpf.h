@@ -468,6 +468,44 @@ int kpf_mano_assoc_vis_mask_f32(const float* points, const float* point_weight, 
 int kpf_mano_raster_f32(const float* verts, const int* faces, int F, const float* cam, const float* M /*or NULL*/, int H, int W, float margin,
     const float* depth_obs /*or NULL*/, float* depth, int* face, int* occluded, float* stats, int B, void* stream);
 
+/* The silhouette of an observed depth crop (ABI 33), once per frame: for every pixel the nearest observed pixel, and the nearest observed depth around
+ * it.  One workgroup per hand, integers and exact minima only.  depth_obs [B][H][W] mm, 1 <= H, W and H * W <= 16384; a pixel is OBSERVED iff its depth
+ * is finite and > 0 (kpf_mano_raster_f32's rule).  Anything else is refused before the launch and nothing is written.
+ *   dist2 [B][H][W] = the smallest (r - r')^2 + (c - c')^2 over the observed pixels (r', c') of the hand; nearest [B][H][W] = r' * W + c' of the observed
+ * pixel with the smallest (dist2, r', c') in lexicographic order -- among equally near pixels the lowest linear index.  Both are -1 everywhere for a hand
+ * with no observed pixel.  front [B][H][W] = the minimum of the observed depths among the pixels (r + i, c + j), i, j in -1..1, that lie in the window; 0
+ * where none of them is observed.  count [B] = the number of observed pixels.  No output may overlap depth_obs. */
+int kpf_depth_silhouette_f32(const float* depth_obs /*[B][H][W] mm*/, int H, int W, int* nearest /*[B][H][W]*/, int* dist2 /*[B][H][W]*/,
+    float* front /*[B][H][W]*/, int* count /*[B]*/, int B, void* stream);
+
+/* The free-space term of the cloud fit (ABI 33), once per round: a vertex that projects outside the observed silhouette is pulled to it, a vertex in
+ * front of the observed surface is pushed back along its ray, and either replaces that vertex's entry in the vertex targets of the mesh fit.  One
+ * workgroup per hand.  verts, cam, M (or NULL = the identity), H, W as kpf_mano_raster_f32; nearest, dist2, front [B][H][W]: kpf_depth_silhouette_f32's;
+ * slack2 >= 0; margin in mm, > 0 or +inf (+inf: the in-front rule is off); step in mm, > 0 or +inf (+inf: no clamp); lambda_free finite and >= 0;
+ * vert_target_in [B][778][3] and vert_weight_in [B][778] (both or neither: kpf_mano_assoc_*'s outputs), vert_normal_in [B][778][3] or NULL
+ * (kpf_mano_normals_f32's).  Anything else is refused before the launch and nothing is written.
+ *   Per vertex (x, y, z): U, V, sx, sy are kpf_mano_raster_f32's expressions; ok iff x, y, z are finite, z > 0 and neither sx nor sy is NaN.  The pixel
+ * is (c, r) = (floor(sx + 0.5), floor(sy + 0.5)), each clamped to [0, W - 1], [0, H - 1] in float before the conversion: a vertex OUTSIDE the window is
+ * judged at the nearest window pixel.  d2 = dist2[r][c], f = front[r][c].  m = M or ((1, 0, 0), (0, 1, 0)); det = m00*m11 - m01*m10; a hand whose det
+ * is 0 or not finite has no vertex of kind 1 or 2.
+ *   kind 1 (outside the silhouette) iff ok and d2 > slack2 (so d2 >= 0): the target keeps z and sits at the centre of pixel n = nearest[r][c],
+ * c* = n % W, r* = n / W:  a = ((float)c* + 0.5) - m02, b = ((float)r* + 0.5) - m12, u = (m11*a - m01*b) / det, v = (m00*b - m10*a) / det,
+ * t = (((u - u0) / fx) * z, ((v - v0) / fy) * z, z).
+ *   kind 2 (in front of the observed surface) iff ok and d2 == 0 and f > 0 and z < f - margin: zt = f - margin, s = zt / z, t = (x*s, y*s, zt).
+ *   kind 0: everything else.
+ *   The clamp: d = t - (x, y, z), len = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z); kind becomes 0 if len is 0 or not finite; if len > step then
+ * q = step / len and t = (x + d.x*q, y + d.y*q, z + d.z*q).
+ *   kind 0 copies vert_target_in, vert_weight_in, vert_normal_in of the vertex bit for bit (zeros for an input that is NULL); kind 1 and 2 write t,
+ * lambda_free (on the scale where one depth point weighs 1) and d / len: the vertex's matches in the cloud are dropped for the round, and the
+ * point-to-plane row of kpf_mano_fit_mesh_gn_plane_f32 sees the whole pull.  kind [B][778].  stats [B][4]: the vertices of kind 1, the mean of
+ * sqrt((float)d2) over them, the vertices of kind 2, the mean of f - z over them (0 without any).  Each sum: thread t of 256 adds its vertices t,
+ * t + 256, ... in ascending order onto +0, a 64-lane butterfly (offsets 32, 16, ... 1) per wave, then ((w0 + w1) + w2) + w3.  Every operation is
+ * individually rounded (no fma): a numpy-fp32 restatement gives the same bits. */
+int kpf_mano_free_space_f32(const float* verts, const float* cam, const float* M /*or NULL*/, int H, int W, const int* nearest, const int* dist2,
+    const float* front, int slack2, float margin, float step, float lambda_free, const float* vert_target_in /*or NULL*/,
+    const float* vert_weight_in /*or NULL*/, const float* vert_normal_in /*or NULL*/, float* vert_target, float* vert_weight, float* vert_normal,
+    int* kind /*[B][778]*/, float* stats /*[B][4]*/, int B, void* stream);
+
 /* kpf_mano_fit_mesh_gn_f32 with a point-to-plane vertex term (ABI 30).  vert_normal [B][778][3], fixed for the launch, or NULL: then this is
  * kpf_mano_fit_mesh_gn_f32, the same kernel and bits.  With normals a vertex term is required, and each vertex contributes ONE row
  *   sqrt(lambda_verts u_v / sv) n_v^T (V_v + t - c_v),  Jacobian n_v^T d (V_v + t) / d p
@@ -1160,7 +1198,7 @@ int kpf_conv_num_tile_cfgs(void);
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 32
+#define KPF_ABI_VERSION 33
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -28,7 +28,12 @@ fit_cloud(metric="plane") chains the three.
 Self-occlusion: render_depth is a z-buffer render of the mesh into the crop's pixel grid (kpf_mano_raster_f32: depth, owning face, the
 vertices hidden behind another part of the mesh, and the comparison with the observed depth crop), associate(vert_mask=...) keeps hidden vertices out of the
 candidates (kpf_mano_assoc_vis_mask_f32), and fit_cloud(occlusion="zbuffer") chains them; crop_camera and crop_depth_mm take the camera, the crop map and
-the observed depth from the preprocessing's outputs."""
+the observed depth from the preprocessing's outputs.
+
+Free space: every row above starts from a depth point, so nothing tells the mesh where it must not be.  silhouette turns the observed
+crop into per-pixel maps once per frame (kpf_depth_silhouette_f32: the nearest observed pixel, its distance, the nearest observed depth around it),
+free_space gives every vertex that lies outside the observed silhouette, or in front of the observed surface, a target of its own in place of the cloud's
+(kpf_mano_free_space_f32; csrc/kpf_mano_free.hip), and fit_cloud(free_space="silhouette") puts it between associate and fit_mesh_gn.  Off by default."""
 import torch
 
 from . import lib as L
@@ -60,6 +65,7 @@ class ManoFitter:
         self.mesh_gn_cfg = L.ManoFitMeshGnCfg(*[getattr(self.gn_cfg, n) for n, _ in L.ManoFitGnCfg._fields_], 1.0)
         self._bufs, self._mesh_bufs, self._assoc_bufs, self._gn_bufs, self._mesh_gn_bufs, self._normal_bufs = {}, {}, {}, {}, {}, {}
         self._raster_bufs = {}
+        self._sil_bufs, self._free_bufs = {}, {}
 
     def new_state(self, B):
         """(pose_aa [B, 48], betas [B, 10], trans [B, 3]) zeros: the cold start."""
@@ -311,6 +317,93 @@ class ManoFitter:
             out["iou"] = st[:, 2] / (st[:, 0] + st[:, 1] - st[:, 2])
         return out
 
+    def silhouette(self, depth_obs, _slot=0):
+        """The silhouette of an observed depth crop, once per frame (kpf_depth_silhouette_f32).  depth_obs [B, H, W] mm (crop_depth_mm's),
+        H * W <= 16384; a pixel is observed iff its depth is finite and > 0, render_depth's rule.
+
+        Returns nearest [B, H, W] int32 (r' * W + c' of the nearest observed pixel, the lowest linear index among equally near ones) and dist2 [B, H, W]
+        int32 (its squared distance in pixels; 0 on an observed pixel), both -1 for a hand without an observed pixel; front [B, H, W] (the smallest observed
+        depth of the pixel's 3 x 3 neighbourhood, 0 where none is observed) and count [B] int32 (the observed pixels).  The fitter's own tensors per
+        (B, H, W, slot); one launch, no host wait."""
+        if not (hasattr(depth_obs, "dim") and depth_obs.dim() == 3):
+            raise ValueError("depth_obs must be a contiguous float32 [B, H, W] tensor on the device")
+        B, H, W = (int(s) for s in depth_obs.shape)
+        if not (H >= 1 and W >= 1 and H * W <= 16384):
+            raise ValueError("silhouette takes 1 <= H, W and H * W <= 16384, not %d x %d" % (H, W))
+        self._check(depth_obs, (B, H, W), "depth_obs")
+        key = (B, H, W, _slot)
+        if key not in self._sil_bufs:
+            i = lambda *s: torch.empty(*s, device=self.device, dtype=torch.int32)  # noqa: E731
+            self._sil_bufs[key] = {"nearest": i(B, H, W), "dist2": i(B, H, W), "front": torch.empty(B, H, W, device=self.device, dtype=torch.float32),
+                                   "count": i(B)}
+        o = self._sil_bufs[key]
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_depth_silhouette_f32(depth_obs.data_ptr(), H, W, o["nearest"].data_ptr(), o["dist2"].data_ptr(), o["front"].data_ptr(),
+                                                      o["count"].data_ptr(), B, torch.cuda.current_stream().cuda_stream), "kpf_depth_silhouette_f32")
+        return dict(o)
+
+    def free_space(self, verts3d, cam, M, sil, slack2=1, margin=5.0, step=20.0, lambda_free=1.0, vert_target=None, vert_weight=None, vert_normal=None,
+                   _slot=0):
+        """The free-space term, once per round (kpf_mano_free_space_f32): where the mesh must not be.  verts3d [B, 778, 3], cam [B, 4] and
+        M [B, 2, 3] or None as render_depth takes them; sil: silhouette's output for the crop.  A vertex is judged at its nearest pixel (one outside the
+        window at the nearest window pixel):
+          kind 1, outside the silhouette: dist2 there > slack2 (pixels^2).  Its target is the point of its own depth on the ray through the centre of the
+                  nearest observed pixel;
+          kind 2, in front of the observed surface: the pixel is observed and z < front - margin (mm; float("inf"): the rule is off).  Its target is the
+                  vertex moved along its own ray to depth front - margin;
+          kind 0, neither -- also a vertex that is not finite or has z <= 0, and every vertex of a hand with a singular M or without an observed pixel.
+        A target farther than `step` mm from its vertex is pulled in to that distance (float("inf"): no clamp).
+
+        vert_target [B, 778, 3] and vert_weight [B, 778] (both or neither) and vert_normal [B, 778, 3] are associate's and normals' outputs: a vertex of
+        kind 0 passes them through bit for bit (zeros without them), a vertex of kind 1 or 2 is overridden by its target, the weight lambda_free (one depth
+        point weighs 1) and the unit direction of the pull as its normal -- the cloud's matches on it are dropped for the round.
+
+        Returns vert_target, vert_weight, vert_normal (fit_mesh_gn's inputs), kind [B, 778] int32 and stats [B, 4] (the vertices of kind 1, their mean
+        distance to the silhouette in pixels, the vertices of kind 2, their mean front - z in mm).  The fitter's own tensors per (B, slot); one launch, no
+        host wait."""
+        if not (isinstance(slack2, int) and slack2 >= 0):
+            raise ValueError("slack2 must be an integer >= 0, not %r" % (slack2,))
+        if not float(margin) > 0.0:
+            raise ValueError("margin must be > 0 or float(\"inf\"), not %r" % (margin,))
+        if not float(step) > 0.0:
+            raise ValueError("step must be > 0 or float(\"inf\"), not %r" % (step,))
+        if not 0.0 <= float(lambda_free) < float("inf"):
+            raise ValueError("lambda_free must be finite and >= 0, not %r" % (lambda_free,))
+        if (vert_target is None) != (vert_weight is None):
+            raise ValueError("vert_target and vert_weight go together")
+        if not (isinstance(sil, dict) and all(k in sil for k in ("nearest", "dist2", "front"))):
+            raise ValueError("sil must be silhouette's output")
+        B = int(verts3d.shape[0])
+        self._check(verts3d, (B, 778, 3), "verts3d")
+        self._check(cam, (B, 4), "cam")
+        if M is not None:
+            self._check(M, (B, 2, 3), "M")
+        H, W = (int(s) for s in sil["front"].shape[1:])
+        self._check(sil["front"], (B, H, W), "sil[\"front\"]")
+        for k in ("nearest", "dist2"):
+            t = sil[k]
+            if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B, H, W)):
+                raise ValueError("sil[\"%s\"] must be a contiguous int32 %s tensor on the device" % (k, [B, H, W]))
+        if vert_target is not None:
+            self._check(vert_target, (B, 778, 3), "vert_target")
+            self._check(vert_weight, (B, 778), "vert_weight")
+        if vert_normal is not None:
+            self._check(vert_normal, (B, 778, 3), "vert_normal")
+        key = (B, _slot)
+        if key not in self._free_bufs:
+            e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)  # noqa: E731
+            self._free_bufs[key] = {"vert_target": e(B, 778, 3), "vert_weight": e(B, 778), "vert_normal": e(B, 778, 3),
+                                    "kind": torch.empty(B, 778, device=self.device, dtype=torch.int32), "stats": e(B, 4)}
+        o = self._free_bufs[key]
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(self.device):
+            L.check(L.load().kpf_mano_free_space_f32(verts3d.data_ptr(), cam.data_ptr(), ptr(M), H, W, sil["nearest"].data_ptr(), sil["dist2"].data_ptr(),
+                                                     sil["front"].data_ptr(), slack2, float(margin), float(step), float(lambda_free), ptr(vert_target),
+                                                     ptr(vert_weight), ptr(vert_normal), o["vert_target"].data_ptr(), o["vert_weight"].data_ptr(),
+                                                     o["vert_normal"].data_ptr(), o["kind"].data_ptr(), o["stats"].data_ptr(), B,
+                                                     torch.cuda.current_stream().cuda_stream), "kpf_mano_free_space_f32")
+        return dict(o)
+
     def associate(self, points_mm, verts3d, point_weight=None, max_dist=20.0, _slot=0, normals=None, facing_min=0.0, vert_mask=None):
         """points_mm [B, N, 3] (camera-space mm, 1 <= N <= 4096), verts3d [B, 778, 3] (a fit's), point_weight [B, N] >= 0 or None (= ones), max_dist: the gate
         in mm (float("inf"): none) -> idx [B, N] int32 (each point's nearest vertex, -1 if its weight is 0, a coordinate is not finite or the vertex is
@@ -371,7 +464,8 @@ class ManoFitter:
 
     def fit_cloud(self, joints_mm, points_mm, weight=None, point_weight=None, state=None, init_trans=True, rounds=3, iters_cloud=None, max_dist=20.0,
                   lambda_verts=1.0, joint_solver="adam", cloud_solver="adam", metric="point", facing_min=0.0, normal_sign=1.0, occlusion=None, camera=None,
-                  raster_size=(128, 128), occlusion_margin=10.0, depth_obs=None):
+                  raster_size=(128, 128), occlusion_margin=10.0, depth_obs=None, free_space=None, free_slack2=1, free_margin=5.0, free_step=20.0,
+                  lambda_free=1.0):
         """Joints, then the depth points: one fit on the joints, then `rounds` times associate followed by fit_mesh (warm start, init_trans=False, the joints
         kept in the objective, iters_cloud iterations each; None = the fitter's), and last one associate on the final vertices: 2 * rounds + 2 launches and no
         host wait.  Returns the last fit's outputs plus cloud_before and cloud_after (the stats of the first and the last association: matched points and
@@ -387,7 +481,23 @@ class ManoFitter:
         occlusion: None (the above, its bits) or "zbuffer" (needs metric="plane" and camera=(cam, M) as crop_camera gives them): each round
         is normals -> render_depth(raster_size, occlusion_margin) -> associate(normals=, vert_mask=1 - occluded) -> fit_mesh_gn(vert_normal=), and a last
         normals + render_depth(depth_obs=) + associate: 4 * rounds + 4 launches and the mask's elementwise op, no host wait.  Also returned then: depth,
-        face, occluded and depth_stats of the final mesh's render (render_depth's stats) and, with depth_obs [B, H, W] (crop_depth_mm's), iou."""
+        face, occluded and depth_stats of the final mesh's render (render_depth's stats) and, with depth_obs [B, H, W] (crop_depth_mm's), iou.
+
+        free_space: None (the above, its bits and launches) or "silhouette" (needs cloud_solver="gn", camera=(cam, M) and depth_obs; either
+        metric, with or without occlusion="zbuffer"): one silhouette(depth_obs) per call, and in each round free_space(free_slack2, free_margin, free_step,
+        lambda_free) between associate and fit_mesh_gn -- a vertex outside the observed silhouette, or more than free_margin mm in front of the observed
+        surface, gets its free-space target in place of the cloud's (metric="point" takes the target and the weight, "plane" the merged normal too) -- and
+        a last free_space on the final vertices for the report: rounds + 2 launches more.  Also returned then: free_before and free_after (free_space's
+        stats of the first and the last call), free_kind (the last call's kind) and silhouette (silhouette's output).  Off by default: with few joints
+        weighted and a far start the term can make the vertex error worse; free_margin=float("inf") switches the in-front rule off."""
+        if free_space not in (None, "silhouette"):
+            raise ValueError("free_space must be None or \"silhouette\", not %r" % (free_space,))
+        if free_space is not None and cloud_solver != "gn":
+            raise ValueError("free_space=\"silhouette\" needs cloud_solver=\"gn\"")
+        if free_space is not None and (camera is None or len(camera) != 2):
+            raise ValueError("free_space=\"silhouette\" needs camera=(cam, M)")
+        if free_space is not None and depth_obs is None:
+            raise ValueError("free_space=\"silhouette\" needs depth_obs")
         if occlusion not in (None, "zbuffer"):
             raise ValueError("occlusion must be None or \"zbuffer\", not %r" % (occlusion,))
         if occlusion == "zbuffer" and metric != "plane":
@@ -408,6 +518,18 @@ class ManoFitter:
             out = self.fit(joints_mm, weight, state=state, init_trans=init_trans)
         state = (out["mano_pose_aa"], out["mano_shape"], out["trans"])
         first = None
+        sil, free_first = None, None
+        if free_space is not None:
+            sil = self.silhouette(depth_obs)
+
+        def free(verts, slot, a=None, nrm=None):  # free_space on `verts`, over the association `a` (and the normals); the report's call has neither
+            return self.free_space(verts, camera[0], camera[1], sil, free_slack2, free_margin, free_step, lambda_free,
+                                   None if a is None else a["vert_target"], None if a is None else a["vert_weight"], nrm, _slot=slot)
+
+        def free_report(out, verts):  # the last call, on the final vertices
+            if sil is not None:
+                rep = free(verts, 2)
+                out.update(free_before=(rep if free_first is None else free_first)["stats"], free_after=rep["stats"], free_kind=rep["kind"], silhouette=sil)
         if metric == "plane":
             zbuf = occlusion == "zbuffer"
 
@@ -423,8 +545,12 @@ class ManoFitter:
                 a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0, normals=nrm, facing_min=facing_min,
                                    vert_mask=mask)
                 first = a if first is None else first
-                out = self.fit_mesh_gn(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
-                                       iters=2 if iters_cloud is None else iters_cloud, vert_normal=nrm)
+                tgt, pull = a, nrm
+                if sil is not None:
+                    tgt = free(out["verts3d"], 1 if r == 0 else 0, a, nrm)
+                    free_first, pull = tgt if free_first is None else free_first, tgt["vert_normal"]
+                out = self.fit_mesh_gn(joints_mm, weight, tgt["vert_target"], tgt["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
+                                       iters=2 if iters_cloud is None else iters_cloud, vert_normal=pull)
             nrm = self.normals(out["verts3d"], normal_sign, _slot=2)
             ren, mask = mask_of(out["verts3d"], 2, depth_obs)
             last = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=2, normals=nrm, facing_min=facing_min, vert_mask=mask)
@@ -435,10 +561,14 @@ class ManoFitter:
                 out.update(depth=ren["depth"], face=ren["face"], occluded=ren["occluded"], depth_stats=ren["stats"])
                 if depth_obs is not None:
                     out["iou"] = ren["iou"]
+            free_report(out, out["verts3d"])
             return out
         for r in range(int(rounds)):
             a = self.associate(points_mm, out["verts3d"], point_weight, max_dist, _slot=1 if r == 0 else 0)
             first = a if first is None else first
+            if sil is not None:
+                a = free(out["verts3d"], 1 if r == 0 else 0, a)
+                free_first = a if free_first is None else free_first
             if cloud_solver == "gn":
                 out = self.fit_mesh_gn(joints_mm, weight, a["vert_target"], a["vert_weight"], state=state, init_trans=False, lambda_verts=lambda_verts,
                                        iters=2 if iters_cloud is None else iters_cloud)
@@ -449,6 +579,7 @@ class ManoFitter:
         out = dict(out)
         out.update(cloud_before=(last if first is None else first)["stats"], cloud_after=last["stats"], idx=last["idx"], vert_target=last["vert_target"],
                    vert_weight=last["vert_weight"])
+        free_report(out, out["verts3d"])
         return out
 
 

@@ -7,7 +7,8 @@ iterations, Adam's figures of the same run beside them (records fit_mesh_gn_B1 /
 association over the camera-facing vertices and the chain with point-to-plane rounds (records normals_B1 / _B32, assoc_vis_B1 / _B32,
 fit_cloud_plane_B1 / _B32, beside fit_cloud_gn_* of the same run); the z-buffer render at 128 x 128 and 32 x 32, with and without an
 observed depth crop, and the chain with the render's mask on the association (records raster_B1 / _B32, fit_cloud_zbuf_B1 / _B32, beside
-fit_cloud_plane_* of the same run); the mesh evaluation evaluation_mesh_gpu.DeviceMeshEvaluator.update at V = 778 and beside it the same
+fit_cloud_plane_* of the same run); the silhouette of an observed crop, the free-space term and the plane chain with it (records
+silhouette_B1 / _B32, free_space_B1 / _B32, fit_cloud_free_B1 / _B32, beside fit_cloud_plane_* of the same run); the mesh evaluation evaluation_mesh_gpu.DeviceMeshEvaluator.update at V = 778 and beside it the same
 figures as torch ops on the device with one .cpu() per batch (records mesh_eval_B1 / _B32).  Prints one JSON line and writes it to profiles/mano_bench.json (--out).
 
     python tools/mano_bench.py
@@ -169,6 +170,25 @@ def main():
         rec["fit_cloud_zbuf_B%d" % B] = {"ms_rounds6_iters2": zbuf_ms, "cloud_mm": [[float(v) for v in out[k].mean(0)] for k in ("cloud_before", "cloud_after")],
                                          "status": sorted(set(int(v) for v in out["status"])), "depth_stats": [float(v) for v in out["depth_stats"].mean(0)],
                                          "iou": float(out["iou"].mean()), "plane_ms_rounds6_iters2": plane_ms}
+        # the free-space term: the silhouette of the observed crop (the neighbouring hand's render, so vertices of both kinds exist), the
+        # term on the mesh with and without the association's outputs, and the plane chain with it beside the plane chain of this run
+        obs32 = torch.roll(fitter.render_depth(vt, cam, M32, size=(32, 32))["depth"], 1, 0).clone()
+        sil = {k: t.clone() for k, t in fitter.silhouette(obs).items()}
+        rec["silhouette_B%d" % B] = {"ms_128": _timed(lambda: fitter.silhouette(obs), args.reps, torch),
+                                     "ms_32": _timed(lambda: fitter.silhouette(obs32), args.reps, torch),
+                                     "observed_128": float(sil["count"].float().mean())}
+        fs = fitter.free_space(vt, cam, M128, sil)
+        rec["free_space_B%d" % B] = {"ms": _timed(lambda: fitter.free_space(vt, cam, M128, sil), args.reps, torch),
+                                     "ms_with_inputs": _timed(lambda: fitter.free_space(vt, cam, M128, sil, vert_target=vis["vert_target"],
+                                                                                        vert_weight=vis["vert_weight"], vert_normal=nrm), args.reps, torch),
+                                     "stats": [float(v) for v in fs["stats"].mean(0)]}
+        free = dict(plane, camera=(cam, M128), depth_obs=obs, free_space="silhouette")
+        free_ms = _timed(lambda: fitter.fit_cloud(y, pts, **free), args.reps, torch)
+        out = fitter.fit_cloud(y, pts, **free)
+        rec["fit_cloud_free_B%d" % B] = {"ms_rounds6_iters2": free_ms, "cloud_mm": [[float(v) for v in out[k].mean(0)] for k in ("cloud_before", "cloud_after")],
+                                         "status": sorted(set(int(v) for v in out["status"])),
+                                         "free_stats": [[float(v) for v in out[k].mean(0)] for k in ("free_before", "free_after")],
+                                         "plane_ms_rounds6_iters2": plane_ms}
     # the mesh evaluation: the fitted hands scored against the hands 2 mm away; beside it the same figures as torch ops
     from keypointfusion_amd.evaluation import similarity_align
     from keypointfusion_amd.evaluation_mesh_gpu import DeviceMeshEvaluator
