@@ -1193,12 +1193,73 @@ int kpf_eval_mesh_accumulate(const float* err, const double* mean_err, const int
                              int Tf, long long* n_samples, long long* n_batches, double* sum_mean_err, double* sum_vert, long long* pck, double* sum_f,
                              void* stream);
 
+/* The result drawn over the frame (ABI 34; keypointfusion_amd/overlay.py, whose draw_host restates both launches in numpy fp32 and gives the same bits;
+ * DESIGN.md 4.19).  Device buffers unless marked HOST; no entry synchronises or allocates.  Every floating-point operation is individually rounded fp32
+ * (no fma) and every decision that depends on arrival order is an integer min.  Anything outside the stated ranges is refused before the launch with
+ * KPF_EINVAL and a kpf_last_error text, and nothing is written.
+ *
+ * kpf_overlay_project_f32, one workgroup per hand: verts [B][778][3] mm in the camera frame; normals [B][778][3] (kpf_mano_normals_f32's) or NULL;
+ * cam [B][4] = fx, fy, u0, v0; M [B][2][3], frame pixels -> target-grid coordinates, or NULL = the identity; sample_offset finite; 0 <= ambient <= 1;
+ * 1 <= H, W (the target grid); 1 <= B < 2^20.
+ *   U, V, sx, sy, iz are kpf_mano_raster_f32's expressions with sample_offset in place of the literal 0.5: grid pixel (c, r) is sampled at sx = c, sy = r.
+ *   sample_offset is 0.5 for a crop grid reached through M (the preprocessing back-projects crop pixel (c, r) from (c + 0.5, r + 0.5)) and 0 for the frame
+ *   itself, where the un-crop of a joint (kpf_prep_uncrop_f32's frame_px) is x*fx/z + u0 with no half-pixel shift.
+ *   shade = ambient + (1 - ambient) * |n.z|; ambient where the normal is all-zero or not finite; 1 when normals is NULL.
+ *   ok = 1 iff x, y, z are finite and z > 0.  rect [B][4] = c0, r0, c1, r1 over the ok vertices (fmin / fmax, a NaN coordinate is skipped):
+ *   c0 = min(max(ceil(min sx), 0), W), c1 = max(min(floor(max sx), W - 1), -1), r0 and r1 alike with H, clamped in float before the conversion; a hand
+ *   with no ok vertex, or off the grid, has c1 < c0 or r1 < r0. */
+int kpf_overlay_project_f32(const float* verts, const float* normals /*or NULL*/, const float* cam, const float* M /*or NULL*/, float sample_offset,
+    float ambient, int H, int W, float* sx /*[B][778]*/, float* sy, float* iz, float* shade, int* ok /*[B][778]*/, int* rect /*[B][4]*/, int B,
+    void* stream);
+
+/* kpf_overlay_draw_u8, one 256-thread workgroup per 64 x 64 tile of the target grid and stored frame, the tile's 64-bit z-keys in 32 KiB of LDS.
+ *   Mesh (sx != NULL; otherwise none is drawn and the mesh's other fields are ignored): every hand b with frame_index[b] (clamped to 0..F-1; NULL: F == B
+ * and hand b lies on frame b) equal to the frame, mesh_on NULL or mesh_on[b] != 0, and a rect that meets the tile.  Faces, edge functions, the inside rule
+ * and d are kpf_mano_raster_f32's; a face with a vertex that is not ok is dropped; a candidate is a d that is finite and > 0; the smallest
+ * (bits(d) << 32) | (hand << 11 | face) wins the pixel: the nearest surface whichever hand it belongs to, among equal d the lowest hand, then the lowest
+ * face.  At the winner s = ((w0/sum)*s0 + (w1/sum)*s1) + (w2/sum)*s2 over its vertices' shade.  The pixel is HIDDEN iff depth_frame != NULL, its value
+ * o != 0 and (float)o < d - occl_margin: it keeps rgb and gets label 4.  Otherwise channel k is floor(((1 - alpha)*(float)rgb_k + alpha*(mesh_color[hand][k]*s))
+ * + 0.5) clamped to 0..255 (NaN -> 0), 1 - alpha computed once in float, and the label is 1.  owner = hand, prim = face, depth = d, hidden or not.
+ *   Skeleton (joints_px != NULL), over the mesh, opaque, no depth test: pixel (c, r) is the point ((float)c, (float)r) of joints_px' coordinates, and the
+ * LAST covering primitive wins in the order: hands ascending (of this frame, skel_on NULL or skel_on[b] != 0); within a hand joints 0..J-1, then bones
+ * 0..NB-1.  A joint (u, v) covers iff u, v are finite, the pixel is inside its box [(u - R) - 1, (u + R) + 1] x [(v - R) - 1, (v + R) + 1] and
+ * dx*dx + dy*dy <= R*R with (dx, dy) = pixel - (u, v), R = joint_radius.  A bone a -> b covers iff both ends are finite, the pixel is inside its box
+ * [(min(a.x, b.x) - h) - 1, (max(a.x, b.x) + h) + 1] x (y alike), h = bone_half_width, and with e = b - a, p = pixel - a, L = e.x*e.x + e.y*e.y,
+ * t = L > 0 ? fmin(fmax((p.x*e.x + p.y*e.y) / L, 0), 1) : 0, q = p - t*e:  q.x*q.x + q.y*q.y <= h*h.  The boxes, one pixel beyond the primitive's
+ * extent, are what a tile culls by.  A skeleton pixel gets the primitive's colour, label 3 (joint) or 2 (bone), owner = hand, prim = the joint's or
+ * bone's index; depth stays the mesh's.
+ *   A pixel nothing covers: out = rgb, label 0, owner = prim = -1, depth 0.
+ *   Ranges: 1 <= B < 2^20, 1 <= F <= 65535, 1 <= H, W; 0 <= alpha <= 1; occl_margin finite; with a mesh 1 <= Fc <= 2048 and none of its pointers NULL;
+ * with a skeleton 1 <= J <= 64, 0 <= NB <= 64, every bone index in [0, J), joint_radius and bone_half_width finite and >= 0; out must not overlap rgb. */
+typedef struct {
+  const float *sx, *sy, *iz, *shade;      /* [B][778]: kpf_overlay_project_f32's; sx NULL = no mesh */
+  const int *ok, *rect;                   /* [B][778], [B][4]: the same launch's */
+  const int* faces;                       /* [Fc][3] */
+  const float* mesh_color;                /* [B][3], 0..255 */
+  const unsigned char* mesh_on;           /* [B] or NULL */
+  const int* frame_index;                 /* [B] or NULL */
+  const unsigned char* rgb;               /* [F][H][W][3] */
+  const unsigned short* depth_frame;      /* [F][H][W] mm or NULL */
+  const float* joints_px;                 /* [B][J][3] = u, v, d in target-grid pixels, or NULL = no skeleton */
+  const unsigned char* skel_on;           /* [B] or NULL */
+  const int* bones;                       /* HOST [NB][2]: read before the launch and passed with it */
+  const unsigned char* bone_color;        /* HOST [NB][3] */
+  const unsigned char* joint_color;       /* HOST [J][3] */
+  unsigned char* out;                     /* [F][H][W][3] */
+  unsigned char* label;                   /* [F][H][W] or NULL: 0 nothing, 1 mesh, 2 bone, 3 joint, 4 mesh hidden by the scene */
+  int *owner, *prim;                      /* [F][H][W] or NULL */
+  float* depth;                           /* [F][H][W] or NULL: the model depth in mm, 0 where no mesh */
+  int B, F, H, W, Fc, J, NB;
+  float occl_margin, alpha, joint_radius, bone_half_width;
+} kpf_overlay_draw_desc;
+int kpf_overlay_draw_u8(const kpf_overlay_draw_desc* d, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 33
+#define KPF_ABI_VERSION 34
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

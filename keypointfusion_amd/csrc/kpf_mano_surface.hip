@@ -5,6 +5,7 @@
 //   kpf_mano_raster_f32    the z-buffer render: depth, owning face, self-occluded vertices
 // Every operation is individually rounded and every sum has a fixed order: host restatements in tests/ give the same bits.
 #include "kpf_mano_dev.h"
+#include "kpf_raster_dev.h"
 
 namespace {
 
@@ -302,13 +303,11 @@ __global__ __launch_bounds__(256) void mano_assoc_vis_kernel(ManoAssocVisArgs a)
 // along their pixel's ray, and the comparison with an observed depth crop.  One workgroup per hand; the z-buffer is H * W 64-bit words of LDS holding
 // (bits(d) << 32) | face, and a face's candidate enters by an integer min: a positive float's bits order as the float does, so the smallest depth wins, among
 // equal depths the lowest face, whatever the order the faces arrive in.  A thread owns faces t, t + 256, ...: it walks a pixel box of up to
-// RASTER_SMALL pixels itself and queues a larger face, which a whole wave then walks, 8 x 8 pixels at a step (the queue's order does not matter either).
+// RASTER_SMALL pixels itself (kpf_raster_dev.h: the edge rule, shared with the overlay) and queues a larger face, which a whole wave then walks, 8 x 8 pixels at a step (the queue's order does not matter either).
 // The faces are read from global memory (at 128 x 128 the buffer alone is 131072 of the 163840 bytes).  There is no near-plane clipping: a face with a vertex at z <= 0 is
 // skipped whole.  Every operation individually rounded: tests/mano_raster_cases.py::raster_host gives the same bits.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int RASTER_MAXPIX = 16384;
-constexpr unsigned long long RASTER_EMPTY = ~0ull;
-constexpr int RASTER_SMALL = 64;
 
 struct ManoRasterArgs {
   const float* verts;      // [B][778][3]
@@ -324,68 +323,6 @@ struct ManoRasterArgs {
 
 // the launch's dynamic LDS: zb [HW] 64-bit | sx, sy, iz, z [778] float each | ok [778] int | count [4] int | queue [2048] 16-bit
 constexpr size_t raster_lds_bytes(int HW) { return (size_t)HW * 8 + (size_t)NV * 5 * 4 + 16 + (size_t)NORMALS_MAXF * 2; }
-
-// One directed edge a -> b, always evaluated from the lower vertex index: e = (sx[hi] - sx[lo]) (py - sy[lo]) - (sy[hi] - sy[lo]) (px - sx[lo]), negated
-// if a > b.  The two faces at an edge get the same number with opposite signs, so with an inclusive test a pixel centre on the edge belongs to one of them.
-struct RasterEdge {
-  float dx, dy, ox, oy;
-  bool neg;
-  __device__ __forceinline__ void set(const float* sx, const float* sy, int a, int b) {
-#pragma clang fp contract(off)
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    dx = __fsub_rn(sx[hi], sx[lo]);
-    dy = __fsub_rn(sy[hi], sy[lo]);
-    ox = sx[lo];
-    oy = sy[lo];
-    neg = a > b;
-  }
-  __device__ __forceinline__ float at(float px, float py) const {
-#pragma clang fp contract(off)
-    const float e = __fsub_rn(__fmul_rn(dx, __fsub_rn(py, oy)), __fmul_rn(dy, __fsub_rn(px, ox)));
-    return neg ? -e : e;
-  }
-};
-
-// One face ready to be walked: its three edges (w0, w1, w2 are the weights of v0, v1, v2), the vertices' 1 / z, the sign of its area and its pixel box
-struct RasterFace {
-  RasterEdge e0, e1, e2;
-  float iz0, iz1, iz2;
-  bool pos;
-  int x0, x1, y0, y1;
-  // false: the face is skipped (an index outside 0..777, a repeated one, a vertex that is not finite or has z <= 0, no area, no pixel)
-  __device__ __forceinline__ bool set(const int* faces, int k, const float* sx, const float* sy, const float* iz, const int* ok, int H, int W) {
-#pragma clang fp contract(off)
-    const int i0 = faces[k * 3 + 0], i1 = faces[k * 3 + 1], i2 = faces[k * 3 + 2];
-    if ((unsigned)i0 >= (unsigned)NV || (unsigned)i1 >= (unsigned)NV || (unsigned)i2 >= (unsigned)NV) return false;
-    if (i0 == i1 || i1 == i2 || i0 == i2) return false;
-    if (!(ok[i0] && ok[i1] && ok[i2])) return false;
-    e0.set(sx, sy, i1, i2);
-    e1.set(sx, sy, i2, i0);
-    e2.set(sx, sy, i0, i1);
-    const float area = e2.at(sx[i2], sy[i2]);
-    if (area == 0.0f || !isfinite(area)) return false;  // a finite area: every sx, sy of the face is finite
-    // the pixel box, clamped to the window in float: a vertex at z = 1e-3 mm projects to 1e9
-    const float x0f = fmaxf(ceilf(fminf(fminf(sx[i0], sx[i1]), sx[i2])), 0.0f), x1f = fminf(floorf(fmaxf(fmaxf(sx[i0], sx[i1]), sx[i2])), (float)(W - 1));
-    const float y0f = fmaxf(ceilf(fminf(fminf(sy[i0], sy[i1]), sy[i2])), 0.0f), y1f = fminf(floorf(fmaxf(fmaxf(sy[i0], sy[i1]), sy[i2])), (float)(H - 1));
-    if (!(x0f <= x1f && y0f <= y1f)) return false;
-    x0 = (int)x0f; x1 = (int)x1f; y0 = (int)y0f; y1 = (int)y1f;  // inside [0, W - 1] x [0, H - 1]
-    iz0 = iz[i0]; iz1 = iz[i1]; iz2 = iz[i2];
-    pos = area > 0.0f;
-    return true;
-  }
-  // pixel (c, r) of the box: the face's depth there enters the z-buffer if the pixel centre is inside
-  __device__ __forceinline__ void pixel(int c, int r, int k, unsigned long long* zb, int W) const {
-#pragma clang fp contract(off)
-    const float px = (float)c, py = (float)r;
-    const float w0 = e0.at(px, py), w1 = e1.at(px, py), w2 = e2.at(px, py);
-    const bool in = pos ? (w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f) : (w0 <= 0.0f && w1 <= 0.0f && w2 <= 0.0f);  // two-sided: MANO is open at the wrist
-    if (!in) return;
-    const float sum = __fadd_rn(__fadd_rn(w0, w1), w2);
-    const float izp = __fadd_rn(__fadd_rn(__fmul_rn(__fdiv_rn(w0, sum), iz0), __fmul_rn(__fdiv_rn(w1, sum), iz1)), __fmul_rn(__fdiv_rn(w2, sum), iz2));
-    const float d = __fdiv_rn(1.0f, izp);  // perspective-correct
-    if (isfinite(d) && d > 0.0f) atomicMin(&zb[r * W + c], ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)k);
-  }
-};
 
 __global__ __launch_bounds__(256) void mano_raster_kernel(ManoRasterArgs a) {
 #pragma clang fp contract(off)
@@ -417,21 +354,21 @@ __global__ __launch_bounds__(256) void mano_raster_kernel(ManoRasterArgs a) {
   __syncthreads();
   for (int k = t; k < F; k += 256) {  // a small face is walked by its thread, a large one is queued (at most F <= 2048 entries)
     RasterFace f;
-    if (!f.set(a.faces, k, sx, sy, iz, ok, H, W)) continue;
+    if (!f.set(a.faces, k, sx, sy, iz, ok, 0, W - 1, 0, H - 1)) continue;
     if ((f.x1 - f.x0 + 1) * (f.y1 - f.y0 + 1) > RASTER_SMALL) {
       queue[atomicAdd(&count[3], 1)] = (unsigned short)k;
       continue;
     }
     for (int r = f.y0; r <= f.y1; ++r)
-      for (int c = f.x0; c <= f.x1; ++c) f.pixel(c, r, k, zb, W);
+      for (int c = f.x0; c <= f.x1; ++c) raster_min(f, c, r, (unsigned)k, &zb[r * W + c]);
   }
   __syncthreads();
   for (int q = t >> 6; q < count[3]; q += 4) {  // a queued face is walked by one wave, 8 x 8 pixels at a step
     const int k = queue[q];
     RasterFace f;
-    f.set(a.faces, k, sx, sy, iz, ok, H, W);
+    f.set(a.faces, k, sx, sy, iz, ok, 0, W - 1, 0, H - 1);
     for (int r = f.y0 + ((t & 63) >> 3); r <= f.y1; r += 8)
-      for (int c = f.x0 + (t & 7); c <= f.x1; c += 8) f.pixel(c, r, k, zb, W);
+      for (int c = f.x0 + (t & 7); c <= f.x1; c += 8) raster_min(f, c, r, (unsigned)k, &zb[r * W + c]);
   }
   __syncthreads();
   for (int v = t; v < NV; v += 256) {  // behind the surface that owns its nearest pixel, by more than the margin

@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 33  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 34  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -88,6 +88,12 @@ class Dw7Plan(C.Structure):  # kpf_dw7_plan (include/kpf.h)
 
 KPF_DW7_OP = {"ln": 0, "fwd": 1, "wgrad": 2}  # KPF_DW7_OP_*
 KPF_DW7_FAMILY = ("tile", "wave", "wide", "two_launch", "tiny", "conv", "wgrad_lds", "wgrad_reg")  # KPF_DW7_FAMILY_* by value
+
+class OverlayDrawDesc(C.Structure):  # kpf_overlay_draw_desc (include/kpf.h); bones, bone_color and joint_color are HOST arrays
+    _fields_ = [(n, C.c_void_p) for n in ("sx sy iz shade ok rect faces mesh_color mesh_on frame_index rgb depth_frame joints_px skel_on bones bone_color "
+                                          "joint_color out label owner prim depth").split()] + [(n, C.c_int) for n in "B F H W Fc J NB".split()] + [
+        (n, C.c_float) for n in "occl_margin alpha joint_radius bone_half_width".split()]
+
 
 _P = C.c_void_p
 _SIGS = {
@@ -154,6 +160,8 @@ _SIGS = {
     "kpf_depth_silhouette_f32": [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P],
     "kpf_mano_free_space_f32": [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, C.c_float, C.c_float] + [_P] * 8 + [C.c_int, _P],
     "kpf_mano_fit_mesh_gn_plane_f32": [_P] * 11 + [C.POINTER(ManoFitMeshGnCfg)] + [_P] * 11 + [C.c_int, _P],
+    "kpf_overlay_project_f32": [_P, _P, _P, _P, C.c_float, C.c_float, C.c_int, C.c_int] + [_P] * 6 + [C.c_int, _P],
+    "kpf_overlay_draw_u8": [C.POINTER(OverlayDrawDesc), _P],
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],
     "kpf_xattn_weight_floats": [],
