@@ -1556,8 +1556,17 @@ int kpf_dwconv7_wgrad(const float* dy, const float* x, float* dw, float* db, flo
 // ---------------------------------------------------------------------------------------------------------------
 // BatchNorm (batch statistics) + optional ReLU on NHWC rows [M][C], forward and backward — the `BN -> ReLU` pairs of the
 // pre-activation Residual blocks (model/hourglass.py:84-119) when the reference trains.  Three launches each way: per-chunk partial
-// sums (thread = channel quad x row lane, coalesced float4 rows), a per-channel finalize that adds the partials in a fixed order,
-// and the elementwise pass.  Sums are taken about the first row's value (shifted data: no cancellation for |mean| >> std).
+// sums (thread = channel quad x row lane, coalesced float4 rows), a per-channel finalize that combines the partials in a fixed order,
+// and the elementwise pass.
+// The forward statistics travel as (mean, M2 = sum of squared deviations from that mean): every thread sums its own rows about ITS
+// first row and turns (n, sum, sum of squares) into (mean, M2); the lanes of a chunk, and then the chunks in the finalize, merge such
+// pairs as   mean = sum n_i mean_i / n   (taken about the first pair's mean),   M2 = sum M2_i + sum n_i (mean_i - mean)^2   — the
+// merged mean first, then the deviations from it, a sum of non-negative terms.  The means are carried as their distance from row 0
+// of the tensor, which the finalize adds back: a per-channel offset costs nothing (|mean| >> std: a mean carried at full size
+// would be rounded to 2^-24 |mean|, and the deviations between such means with it).  A row z standard deviations from its channel's
+// mean costs 2^-24 z^2 only in the M2 of the one thread that owns it, which is n_thread / M of the total, whichever row it is.
+// (Summing EVERY row's square about row 0 costs 2^-24 z^2 of the whole variance when row 0 is that row: 1e-4 of y at z = 30.)
+// The counts n_i are not stored: they follow from the geometry.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1570,7 +1579,7 @@ __host__ __device__ inline BnGeom bn_geom(int C) {
   return g;
 }
 
-// MODE 0: forward statistics  p0 = sum(x - K), p1 = sum((x - K)^2)          (K = x[0][c])
+// MODE 0: forward statistics  p0 = mean - x[0][c], p1 = M2 of the chunk's rows  (ws[chunk] = {p0, p1}; the chunk's row count follows from its index)
 // MODE 1: backward sums       p0 = sum(dz),    p1 = sum(dz * (x - mean))     (dz = dy masked by y > 0 when RELU)
 // TX: storage type of the layer's input side (x, dx); TY: of its output side (y, dy) — fp32 or the 16-bit type of the
 // mixed-precision step; the arithmetic is fp32 either way.
@@ -1587,7 +1596,9 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const TX* __restrict__ 
   if (active) {
     const long r0 = (long)blockIdx.x * rows_per_chunk;
     const long r1 = min(M, r0 + rows_per_chunk);
-    const f32x4 k = MODE == 0 ? kpf_ld4(x + 4 * q) : kpf_ld4(mean + 4 * q);
+    f32x4 k = {0.f, 0.f, 0.f, 0.f};
+    if (MODE != 0) k = kpf_ld4(mean + 4 * q);
+    else if (r0 + rl < r1) k = kpf_ld4(x + (r0 + rl) * C + 4 * q);  // the thread's own first row
     for (long r = r0 + rl; r < r1; r += g.RL) {
       const f32x4 xv = kpf_ld4(x + r * C + 4 * q) - k;
       if (MODE == 0) {
@@ -1604,15 +1615,42 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const TX* __restrict__ 
         p1 += d * xv;
       }
     }
+    if (MODE == 0 && r0 + rl < r1) {  // (n, sum, sum of squares about k) -> (mean, M2) of the thread's n rows
+      const float n = (float)((r1 - r0 - rl + g.RL - 1) / g.RL);
+      const f32x4 ms = p0 / n;
+      p1 -= p0 * ms;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) p1[e] = fmaxf(p1[e], 0.f);
+      // the mean as its distance from row 0 of the tensor (not rounded to the size of a far-off channel mean), from the SUM about row 0: one division, and
+      // exact sums where the rows differ by a few ulp
+      p0 = (n * (k - kpf_ld4(x + 4 * q)) + p0) / n;
+    }
   }
   red[0][threadIdx.x] = p0;
   red[1][threadIdx.x] = p1;
   __syncthreads();
   if (rl == 0 && q < g.Q) {
     f32x4 s0 = red[0][ql], s1 = red[1][ql];
-    for (int i = 1; i < g.RL; ++i) {
-      s0 += red[0][i * g.QL + ql];
-      s1 += red[1][i * g.QL + ql];
+    if (MODE == 0) {
+      // lane i owns n_i = base + (i < rem) of the chunk's rows: lane 0 at least one; a lane without rows left zeros and weighs nothing
+      const int rows = (int)(min(M, ((long)blockIdx.x + 1) * rows_per_chunk) - (long)blockIdx.x * rows_per_chunk);
+      const int base = rows / g.RL, rem = rows % g.RL;
+      const f32x4 m0 = s0;
+      f32x4 t = {0.f, 0.f, 0.f, 0.f};
+      for (int i = 1; i < g.RL; ++i) {
+        t += (float)(base + (i < rem)) * (red[0][i * g.QL + ql] - m0);
+        s1 += red[1][i * g.QL + ql];
+      }
+      s0 = m0 + t / (float)rows;
+      for (int i = 0; i < g.RL; ++i) {
+        const f32x4 dv = red[0][i * g.QL + ql] - s0;
+        s1 += (float)(base + (i < rem)) * (dv * dv);
+      }
+    } else {
+      for (int i = 1; i < g.RL; ++i) {
+        s0 += red[0][i * g.QL + ql];
+        s1 += red[1][i * g.QL + ql];
+      }
     }
     float* o = ws + (size_t)blockIdx.x * 2 * C;
     kpf_st4(o + 4 * q, s0);
@@ -1650,23 +1688,67 @@ __device__ __forceinline__ void bn_sum_partials(const float* __restrict__ ws, in
   r1 = s1;
 }
 
-// forward finalize: batch mean / 1/sqrt(biased var + eps), running statistics (unbiased variance); 64 channels per workgroup
+// one pass of the forward merge over the S per-chunk pairs ws[p][{mean, M2}][C] of channel c, in bn_sum_partials' order (wave g takes p = g, g+16, ... in four
+// chains); chunk p holds nfull rows, the last one nlast.  SQ false: a = sum n_p (mean_p - ref), b = sum M2_p;  SQ true: a = sum n_p (mean_p - ref)^2
+template <bool SQ>
+__device__ __forceinline__ void bn_merge_pass(const float* __restrict__ ws, int S, int C, int c, int g, float ref, float nfull, float nlast, float& a, float& b) {
+  float av[4] = {0.f, 0.f, 0.f, 0.f}, bv[4] = {0.f, 0.f, 0.f, 0.f};
+  int p = g;
+  for (; p + 3 * BN_FW < S; p += 4 * BN_FW) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float* w0 = ws + (size_t)(p + j * BN_FW) * 2 * C + c;
+      const float d = w0[0] - ref, n = p + j * BN_FW == S - 1 ? nlast : nfull;
+      av[j] += SQ ? n * (d * d) : n * d;
+      if (!SQ) bv[j] += w0[C];
+    }
+  }
+  for (; p < S; p += BN_FW) {
+    const float* w0 = ws + (size_t)p * 2 * C + c;
+    const float d = w0[0] - ref, n = p == S - 1 ? nlast : nfull;
+    av[0] += SQ ? n * (d * d) : n * d;
+    if (!SQ) bv[0] += w0[C];
+  }
+  a = (av[0] + av[1]) + (av[2] + av[3]);
+  b = (bv[0] + bv[1]) + (bv[2] + bv[3]);
+}
+
+// forward finalize: merges the chunks' (mean - x[0][c], M2) — the mean about chunk 0's, then the chunk means' deviations from it — into the batch mean and
+// 1/sqrt(biased var + eps), and updates the running statistics (unbiased variance); 64 channels per workgroup, the 16 wave sums combined through LDS
 template <typename TX>
-__global__ __launch_bounds__(64 * BN_FW) void bn_stats_finalize_kernel(const TX* __restrict__ x, const float* __restrict__ ws, int S, long M, int C,
+__global__ __launch_bounds__(64 * BN_FW) void bn_stats_finalize_kernel(const TX* __restrict__ x, const float* __restrict__ ws, int S, int rows_per_chunk, long M, int C,
                                                                 float* __restrict__ mean, float* __restrict__ invstd,
                                                                 float* __restrict__ rmean, float* __restrict__ rvar, float momentum, float eps) {
   __shared__ float red[BN_FW][2][64];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  float s, ss;
-  bn_sum_partials(ws, S, C, c, red, s, ss);
+  const int o = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + o;
+  const float n = (float)M, nfull = (float)rows_per_chunk, nlast = (float)(M - (long)(S - 1) * rows_per_chunk);
+  const float k = c < C ? ws[c] : 0.f;
+  float a = 0.f, b = 0.f;
+  if (c < C) bn_merge_pass<false>(ws, S, C, c, g, k, nfull, nlast, a, b);
+  red[g][0][o] = a;
+  red[g][1][o] = b;
+  __syncthreads();
+  float s = 0.f, m2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < BN_FW; ++i) {
+    s += red[i][0][o];
+    m2 += red[i][1][o];
+  }
+  const float m = k + s / n;
+  __syncthreads();  // red[.][0] is written again
+  a = 0.f;
+  if (c < C) bn_merge_pass<true>(ws, S, C, c, g, m, nfull, nlast, a, b);
+  red[g][0][o] = a;
+  __syncthreads();
   if (threadIdx.x >= 64 || c >= C) return;
-  const float n = (float)M;
-  const float ms = s / n;
-  const float var = fmaxf(ss / n - ms * ms, 0.f);
-  const float m = (float)x[c] + ms;
-  mean[c] = m;
+#pragma unroll
+  for (int i = 0; i < BN_FW; ++i) m2 += red[i][0][o];
+  const float var = m2 / n;
+  const float mu = ((float)x[c] + k) + s / n;  // (row 0 + chunk 0's mean) first: s / n is small whatever row 0 is
+  mean[c] = mu;
   invstd[c] = 1.0f / sqrtf(var + eps);
-  if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * m;
+  if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mu;
   if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * (M > 1 ? var * n / (n - 1.f) : var);
 }
 
@@ -2077,7 +2159,7 @@ int kpf_bn_ssr_forward(const float* x, const float* w, const float* b, float* ou
   const int cg = (nC / 4 + 63) / 64;
   hipLaunchKernelGGL((bn_partial_kernel<0, false, float, float>), dim3(S, cg), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ws, rows, nC,
                      rpc);
-  hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((nC + 63) / 64), dim3(64 * BN_FW), 0, st, x, ws, S, rows, nC, stats, stats + nC, rmean, rvar, momentum, eps);
+  hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((nC + 63) / 64), dim3(64 * BN_FW), 0, st, x, ws, S, rpc, rows, nC, stats, stats + nC, rmean, rvar, momentum, eps);
   const long n4 = rows * (C / 4);
   long nb = (n4 + 255) / 256;
   hipLaunchKernelGGL(bn_ssr_fwd_kernel, dim3((unsigned)(nb > 65535 ? 65535 : nb)), dim3(256), 0, st, x, stats, w, b, out, n4, C / 4, n1, n2);
@@ -2125,7 +2207,7 @@ int kpf_bn_relu_gmax_forward(const float* x, const float* w, const float* b, flo
   hipStream_t st = (hipStream_t)stream;
   const int cg = (C / 4 + 63) / 64;
   hipLaunchKernelGGL((bn_partial_kernel<0, false, float, float>), dim3(S, cg), dim3(256), 0, st, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ws, M, C, rpc);
-  hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((C + 63) / 64), dim3(64 * BN_FW), 0, st, x, ws, S, M, C, stats, stats + C, rmean, rvar, momentum, eps);
+  hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((C + 63) / 64), dim3(64 * BN_FW), 0, st, x, ws, S, rpc, M, C, stats, stats + C, rmean, rvar, momentum, eps);
   const long n4 = (M / group) * (C / 4);
   long nb = (n4 + 255) / 256;
   hipLaunchKernelGGL(bn_relu_gmax_fwd_kernel, dim3((unsigned)(nb > 65535 ? 65535 : nb)), dim3(256), 0, st, x, stats, w, b, y, arg, n4, group, C / 4);
@@ -2178,7 +2260,7 @@ int kpf_bn2_add_relu_forward(const float* xa, const float* xb, const float* wa, 
   for (int k = 0; k < 2; ++k) {  // (the two statistics passes reuse one workspace: same stream)
     hipLaunchKernelGGL((bn_partial_kernel<0, false, float, float>), dim3(S, cg), dim3(256), 0, st, xs[k], (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ws, M,
                        C, rpc);
-    hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((C + 63) / 64), dim3(64 * BN_FW), 0, st, xs[k], ws, S, M, C, stats + 2 * k * C, stats + (2 * k + 1) * C, rm[k],
+    hipLaunchKernelGGL(bn_stats_finalize_kernel<float>, dim3((C + 63) / 64), dim3(64 * BN_FW), 0, st, xs[k], ws, S, rpc, M, C, stats + 2 * k * C, stats + (2 * k + 1) * C, rm[k],
                        rv[k], momentum, eps);
   }
   hipLaunchKernelGGL(bn2_add_relu_fwd_kernel, dim3(S, cg), dim3(256), 0, st, xa, xb, stats, wa, ba, wb, bb, out, M, C, rpc);
@@ -2222,7 +2304,7 @@ static int bn_forward_impl(const void* xv, const float* w, const float* b, void*
   const int cg = (C / 4 + 63) / 64;
   hipLaunchKernelGGL((bn_partial_kernel<0, false, TX, TY>), dim3(S, cg), dim3(256), 0, st, x, (const TY*)nullptr, (const TY*)nullptr,
                      (const float*)nullptr, ws, M, C, rpc);
-  hipLaunchKernelGGL(bn_stats_finalize_kernel<TX>, dim3((C + 63) / 64), dim3(64 * BN_FW), 0, st, x, ws, S, M, C, mean, invstd, running_mean, running_var,
+  hipLaunchKernelGGL(bn_stats_finalize_kernel<TX>, dim3((C + 63) / 64), dim3(64 * BN_FW), 0, st, x, ws, S, rpc, M, C, mean, invstd, running_mean, running_var,
                      momentum, eps);
   if (relu)
     hipLaunchKernelGGL((bn_elem_kernel<0, true, TX, TY>), dim3(S, cg), dim3(256), 0, st, x, (const TY*)nullptr, (const TY*)nullptr, mean, invstd, w, b,
