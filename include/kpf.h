@@ -1254,12 +1254,41 @@ typedef struct {
 } kpf_overlay_draw_desc;
 int kpf_overlay_draw_u8(const kpf_overlay_draw_desc* d, void* stream);
 
+/* The depth stream registered to the colour camera (ABI 35; keypointfusion_amd/sensor.py, whose align_depth_host restates the rule in numpy fp32 and
+ * gives the same bits).  Three launches on the stream -- clear, scatter (one thread per raw pixel), finish (one thread per colour pixel)
+ * -- no synchronisation, no allocation; the launches communicate through integer atomics only and each reads what the launch before it completed.
+ *   depth_raw [F][Hd][Wd] uint16 raw counts, 0 = no measurement; calib HOST [F][21] float: fxd, fyd, u0d, v0d (the depth camera), fxc, fyc, u0c, v0c (the
+ * colour camera), R[9] row-major and t[3] in mm (X_c = R X_d + t), unit_mm (mm per raw count): read before the launch and passed with it; Hc, Wc: the
+ * colour grid; zbuf [F][Hc][Wc] uint32 scratch; depth_out [F][Hc][Wc] uint16 mm, 0 = nothing; stats [F][5] int32.
+ *   Pixel (c, r) is the point (c, r) and its footprint c +- 0.5, r +- 0.5 (kpf_prep_uncrop_f32's frame pixels, and camera calibrations).  Every
+ * floating-point step is one individually rounded fp32 operation (no fma).  Per raw pixel (c, r) of frame f with count q > 0 (stats[f][0] counts them):
+ *   1. z = (float)q * unit_mm.
+ *   2. carry(pu, pv): X = ((pu - u0d) / fxd) * z, Y = ((pv - v0d) / fyd) * z; Xc = ((R00*X + R01*Y) + R02*z) + t0, Yc and Zc alike from rows 1 and 2;
+ *      u = (Xc*fxc) / Zc + u0c, v = (Yc*fyc) / Zc + v0c.
+ *   3. a = carry(c - 0.5, r - 0.5), b = carry(c + 0.5, r + 0.5), m = carry(c, r); d = rintf(Zc of m), half to even.
+ *   4. The pixel is SKIPPED (stats[f][1]) unless the three Zc are > 0, the nine values u, v, Zc are finite and 1 <= d <= 65535.
+ *   5. x0 = ceil(fmin(ua, ub)), x1 = ceil(fmax(ua, ub)) - 1, y0 and y1 alike from v, in float: the colour pixels whose centres lie in [lo, hi) of the box
+ *      of the two carried corners.  (An identity calibration covers exactly pixel (c, r) whichever way the last bit of u rounds.)
+ *   6. If (x1 - x0) + 1 > max_span or (y1 - y0) + 1 > max_span, in float, the pixel is TOO LARGE (stats[f][2]) and writes nothing: the bound on the work
+ *      of a point close to the colour camera's plane.
+ *   7. X0 = fmax(x0, 0), X1 = fmin(x1, Wc - 1), Y0 = fmax(y0, 0), Y1 = fmin(y1, Hc - 1), in float; nothing is written unless X0 <= X1 and Y0 <= Y1, and
+ *      only then are the four converted to integers.
+ *   8. Every zbuf entry of [Y0, Y1] x [X0, X1] takes min(current, (uint32)d): an integer atomic min on a buffer cleared to 0xFFFFFFFF, so the result does
+ *      not depend on the order of arrival.
+ * Finish: u = (zbuf == 0xFFFFFFFF) ? 0 : zbuf is the unfilled map (stats[f][3] counts its non-zero pixels).  fill = 0: depth_out = u.  fill = 1: a pixel
+ * with u == 0 takes the smallest non-zero u of its 4-neighbours if at least two of them are non-zero (stats[f][4] counts these), the neighbours read from
+ * the UNFILLED map and counting as 0 outside the grid: the cracks of a resampling are one pixel wide and close, an occlusion shadow stays empty.
+ *   Refused before the launch, nothing written: a NULL pointer; F, Hd, Wd, Hc or Wc < 1; F > 32; Hd*Wd or Hc*Wc > 2^24; a calib entry that is not
+ * finite; fxd, fyd, fxc, fyc or unit_mm <= 0; max_span outside 1..16; fill not 0 or 1; depth_out overlapping depth_raw. */
+int kpf_align_depth_u16(const unsigned short* depth_raw, int Hd, int Wd, const float* calib /*HOST [F][21]*/, int F, int Hc, int Wc, int max_span, int fill,
+                        unsigned* zbuf /*[F][Hc][Wc] scratch*/, unsigned short* depth_out /*[F][Hc][Wc]*/, int* stats /*[F][5]*/, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 34
+#define KPF_ABI_VERSION 35
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 34  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 35  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -162,6 +162,7 @@ _SIGS = {
     "kpf_mano_fit_mesh_gn_plane_f32": [_P] * 11 + [C.POINTER(ManoFitMeshGnCfg)] + [_P] * 11 + [C.c_int, _P],
     "kpf_overlay_project_f32": [_P, _P, _P, _P, C.c_float, C.c_float, C.c_int, C.c_int] + [_P] * 6 + [C.c_int, _P],
     "kpf_overlay_draw_u8": [C.POINTER(OverlayDrawDesc), _P],
+    "kpf_align_depth_u16": [_P, C.c_int, C.c_int, _P] + [C.c_int] * 5 + [_P] * 4,
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],
     "kpf_xattn_weight_floats": [],

@@ -74,9 +74,13 @@ class TrackedStream:
     and an eager stream give identical bits from frame 0.  `graph_replays` counts the replays.
 
     State (device, updated in place by every step): bbox [B][4] float64, seed [B] int64 (+ B per frame, so that no two (track, frame) share a seed), lost [B]
-    int32 (frames since the last good box).  A frame with status != 0 keeps its box; reseed() writes detector boxes."""
+    int32 (frames since the last good box).  A frame with status != 0 keeps its box; reseed() writes detector boxes.
 
-    def __init__(self, model, pre, cam, frame_size, frames, frame_index=None, expansion=1.5, stage=5, seed=0, graph=True, forward=None):
+    aligner: a sensor.DepthAligner whose out_size is frame_size and which holds F frames -- step() then takes the RAW depth [F][Hd][Wd] of the depth sensor, and
+    the body registers it to the colour camera (cam is the colour camera's) in front of prepare, inside the captured step; the step's outputs gain
+    align_stats [F][5] int32.  None: depth arrives registered, and nothing of the aligner's runs."""
+
+    def __init__(self, model, pre, cam, frame_size, frames, frame_index=None, expansion=1.5, stage=5, seed=0, graph=True, forward=None, aligner=None):
         if not isinstance(cam, torch.Tensor) or cam.dim() != 2 or cam.shape[1] != 4 or cam.dtype != torch.float64:
             raise ValueError("TrackedStream: cam must be a float64 tensor [B][4] (fx, fy, u0, v0)")
         if cam.device.type != "cuda":
@@ -103,6 +107,12 @@ class TrackedStream:
         self._fi = make_frame_index(frame_index, self.F, dev)
         self._rgb = torch.zeros(self.F, self.H, self.W, 3, dtype=torch.uint8, device=dev)  # the static inputs of the captured step
         self._depth = torch.zeros(self.F, self.H, self.W, dtype=torch.int16, device=dev).view(torch.uint16)  # (torch's 16-bit unsigned type has copies but few kernels: zeros come from int16)
+        self.aligner, self._raw = aligner, None
+        if aligner is not None:
+            if (aligner.F, aligner.Hc, aligner.Wc) != (self.F, self.H, self.W) or aligner.device != dev:
+                raise ValueError("TrackedStream: the aligner registers %d frames to %d x %d on %s, the stream holds %d of %d x %d on %s"
+                                 % (aligner.F, aligner.Hc, aligner.Wc, aligner.device, self.F, self.H, self.W, dev))
+            self._raw = torch.zeros(self.F, aligner.Hd, aligner.Wd, dtype=torch.int16, device=dev).view(torch.uint16)  # the static raw depth of the captured step
         self.bbox = torch.zeros(B, 4, dtype=torch.float64, device=dev)
         self.seed = int(seed) + torch.arange(B, dtype=torch.int64, device=dev)
         self.lost = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -132,6 +142,9 @@ class TrackedStream:
     def _body(self):
         """One frame on the static buffers: what is captured.  Only launches on the current stream."""
         pre, B = self.pre, self.B
+        align_stats = None
+        if self.aligner is not None:  # the raw depth registered to the colour camera, into the static depth frame prepare reads
+            align_stats = self.aligner.align(self._raw, out=self._depth)["stats"]
         prep = pre.prepare(self._rgb, self._depth, self.bbox, self.cam, self.seed, frame_index=self._fi)
         if self._forward is not None:
             joints = self._forward(prep, self.frame_no)
@@ -157,16 +170,21 @@ class TrackedStream:
                                                     self.bbox.data_ptr(), self.seed.data_ptr(), self.lost.data_ptr(), crop_px.data_ptr(), frame_px.data_ptr(),
                                                     cam_mm.data_ptr(), self.bbox_used.data_ptr(), self.status.data_ptr(),
                                                     torch.cuda.current_stream(self.dev).cuda_stream), "kpf_track_step_f32")
-        return dict(frame_px=frame_px, crop_px=crop_px, cam_mm=cam_mm, bbox_used=self.bbox_used, bbox=self.bbox, status=self.status, lost=self.lost,
-                    com=prep["com"], bounds=prep["bounds"], pcl_count=prep["pcl_count"], joints=joints,
-                    pcl=prep["pcl"], cube=prep["cube"], center=prep["center"])  # what mano_fit.cloud_mm needs: the sampled depth points and their frame
+        out = dict(frame_px=frame_px, crop_px=crop_px, cam_mm=cam_mm, bbox_used=self.bbox_used, bbox=self.bbox, status=self.status, lost=self.lost,
+                   com=prep["com"], bounds=prep["bounds"], pcl_count=prep["pcl_count"], joints=joints,
+                   pcl=prep["pcl"], cube=prep["cube"], center=prep["center"])  # what mano_fit.cloud_mm needs: the sampled depth points and their frame
+        if align_stats is not None:
+            out["align_stats"] = align_stats
+        return out
 
     def step(self, rgb, depth):
         """rgb [F][H][W][3] uint8, depth [F][H][W] uint16 (mm) device tensors -> dict of STATIC device tensors, valid in stream order until the next step
         overwrites them: frame_px, crop_px [B][J][3] (u, v px, d mm), cam_mm [B][J][3], bbox_used [B][4] (this frame's box), bbox (the next frame's),
         status, lost [B] int32, and the prepare record com [B][3] float64, bounds [B][6], pcl_count [B] (+ joints, the forward's normalised output, and pcl
-        [B][n][3], cube, center [B][3]: the sampled depth points normalised to the cube, mano_fit.cloud_mm(out) puts them back in camera space)."""
-        for name, t, want in (("rgb", rgb, self._rgb), ("depth", depth, self._depth)):
+        [B][n][3], cube, center [B][3]: the sampled depth points normalised to the cube, mano_fit.cloud_mm(out) puts them back in camera space).
+        With an aligner, depth is the depth sensor's raw frame [F][Hd][Wd] uint16 and the outputs hold align_stats [F][5] int32 as well."""
+        depth_in = self._depth if self.aligner is None else self._raw
+        for name, t, want in (("rgb", rgb, self._rgb), ("depth", depth, depth_in)):
             if not isinstance(t, torch.Tensor) or t.dtype != want.dtype or tuple(t.shape) != tuple(want.shape):
                 raise ValueError("TrackedStream.step: %s must be %s %s (got %s)" % (name, want.dtype, tuple(want.shape),
                                                                                     (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
@@ -174,7 +192,7 @@ class TrackedStream:
                 raise RuntimeError("TrackedStream.step: %s is on %s, the stream on %s (no CPU fallback)" % (name, t.device, self.dev))
         with torch.no_grad(), torch.cuda.device(self.dev):
             self._rgb.copy_(rgb)
-            self._depth.copy_(depth)
+            depth_in.copy_(depth)
             if not self.graph or self.frames_done < 2:
                 self._result = self._body()
             else:
