@@ -1283,12 +1283,55 @@ int kpf_overlay_draw_u8(const kpf_overlay_draw_desc* d, void* stream);
 int kpf_align_depth_u16(const unsigned short* depth_raw, int Hd, int Wd, const float* calib /*HOST [F][21]*/, int F, int Hc, int Wc, int max_span, int fill,
                         unsigned* zbuf /*[F][Hc][Wc] scratch*/, unsigned short* depth_out /*[F][Hc][Wc]*/, int* stats /*[F][5]*/, void* stream);
 
+/* The hands found in the registered depth frame, and lost tracks seeded from them (ABI 36; keypointfusion_amd/detect.py, whose detect_hands_host and
+ * assign_host restate both rules in numpy and give the same words).  The classic depth-camera rule: the hand is the part of the nearest
+ * connected surface that reaches towards the camera.
+ *   kpf_detect_hands_u16: six launches on the stream for any content -- tiles (union-find in LDS), seams (unions in global memory), flatten + count and
+ * z_min, near-slab sums, candidates, selection -- no synchronisation, no readback, no allocation; each launch reads what the one before completed, and
+ * only integer atomics (32-bit min, max, add; 64-bit add) touch shared words, so every output is the same bits whatever the order of arrival.
+ *   depth [F][H][W] uint16 mm, registered to the camera of cam; cam HOST [F][4] float (fx, fy, u0, v0) of each stored frame's camera, read before the
+ * launch and passed with it; K = slots.  Per frame:
+ *   1. A pixel is VALID when near <= d <= far, both ends included (stats[f][0] counts them).
+ *   2. Two 4-neighbours are JOINED when both are valid and |d_a - d_b| <= step_mm.  Components are the classes of that relation (stats[f][1]); a
+ *      component's label is the smallest linear index r * W + c among its pixels: unique, and independent of any order.  Diagonal contact does not join.
+ *   3. Per component the pixel count n and z_min.  A component with n < min_pixels is dropped (stats[f][2] counts the others).
+ *   4. The NEAR SLAB is the component's pixels with d <= z_min + reach_mm.  In integers: the slab count, S2 = sum d^2, sum u, sum v, sum d (64-bit), and
+ *      the inclusive pixel bounds x0, y0, x1, y1.
+ *   5. area_mm2 = (double)S2 / ((double)fx * (double)fy): each slab pixel contributes its back-projected area.  A component is a CANDIDATE when
+ *      min_area_mm2 <= area_mm2 <= max_area_mm2 (stats[f][3]).
+ *   6. Candidates are ranked by (z_min, label) ascending; the first K fill the slots in that order (stats[f][4] = min(candidates, K)), the rest are counted
+ *      only.
+ *   7. A slot's box is kpf_track_step_f32's rule (tracking.next_bbox) on the two float points (x0, y0), (x1, y1) with frame W, H and `expansion`; where
+ *      the rule gives no box the slot is invalid.
+ *   boxes [F][K][4] double xywh (0 for an invalid or empty slot), valid [F][K] int, info [F][K][8] double: label, z_min, n, slab count, area_mm2, and the
+ * slab centroid u, v, d (the integer sums divided in double); an empty slot holds label -1 and zeros.  labels [F][H][W] int: the component's label, -1 for
+ * invalid pixels and for pixels of dropped components.  stats [F][5] int.  ws32: F * 8 * H * W ints of scratch, ws64: kpf_detect_ws64_words(F, H, W, K)
+ * 64-bit words (-1: refused).
+ *   Limitation: two hands joined through the body inside [near, far] are one component; only the nearer reaches the slots.  Set far to arm's length.
+ *   Refused before the launch, nothing written: a NULL pointer; F, H or W < 1; F > 32; H * W > 2^24; K outside 1..8; not 0 <= near <= far <= 65535;
+ * step_mm or reach_mm outside 0..65535; min_pixels < 1; an area bound that is not finite, or not 0 <= min <= max; expansion not in (0, 1e6); a cam entry
+ * that is not finite; fx or fy <= 0; a pointer not aligned to its element size. */
+long kpf_detect_ws64_words(int F, int H, int W, int K);
+int kpf_detect_hands_u16(const unsigned short* depth, int F, int H, int W, const float* cam /*HOST [F][4]*/, int near, int far, int step_mm, int reach_mm,
+                         int min_pixels, double min_area_mm2, double max_area_mm2, float expansion, int K, int* ws32, long long* ws64,
+                         double* boxes /*[F][K][4]*/, int* valid /*[F][K]*/, double* info /*[F][K][8]*/, int* labels /*[F][H][W]*/, int* stats /*[F][5]*/,
+                         void* stream);
+/* The slots handed to the tracks, one launch (detect.assign_host).  frame_index [B] int: each track's stored frame; the state bbox [B][4] double, lost [B],
+ * seeded [B] int is updated in place, reseeded [B] int is rewritten by every call.  A track is FREE when seeded == 0 or lost >= reseed_after, otherwise
+ * LIVE.  A valid slot is TAKEN when its slab centroid (u, v) lies inside the box of a live track on the same frame: x <= u < x + w and y <= v < y + h, in
+ * double.  The free tracks of a frame, in track order, take the frame's untaken slots in rank order: such a track gets the slot's box, lost = 0,
+ * seeded = 1, reseeded = 1.  A free track that gets nothing and has seeded == 0 holds the whole frame (0, 0, frame_w, frame_h), a defined input of the crop.
+ * Two live tracks that drift onto one hand are not resolved here.  Refused: a NULL pointer; F outside 1..32; K outside 1..8; B, frame_w, frame_h or
+ * reseed_after < 1. */
+int kpf_detect_assign_f64(const double* boxes, const int* valid, const double* info, int F, int K, int frame_w, int frame_h, const int* frame_index, int B,
+                          int reseed_after, double* bbox, int* lost, int* seeded, int* reseeded, void* stream);
+
 int kpf_conv_num_tile_cfgs(void);
 
 const char* kpf_last_error(void);
 /* Library/ABI version, bumped when a signature or the meaning of an argument changes (KPF_ABI_VERSION is what this header
  * describes; the Python binding refuses a library that reports another). */
-#define KPF_ABI_VERSION 35
+#define KPF_ABI_VERSION 36
 int kpf_abi_version(void);
 
 #ifdef __cplusplus

@@ -11,6 +11,8 @@
 // one by one).
 #include "kpf_common.h"
 
+#include "kpf_box_dev.h"
+
 #pragma clang fp contract(off)
 
 namespace {
@@ -26,20 +28,6 @@ __device__ __forceinline__ float track_wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-
-// get_bbox along one axis in float32: (corner, size) of the joints' extent [lo, hi] grown by e about its middle
-__device__ __forceinline__ void track_expand(float lo, float hi, float e, float& corner, float& size) {
-  const float c = (lo + hi) / 2.0f;
-  const float w = (hi - lo) * e;
-  const float a = c - 0.5f * w;
-  const float b = c + 0.5f * w;
-  corner = a;
-  size = b - a;
-}
-
-// numpy's reductions over a pair: np.max((a, b)) = a if a >= b else b, np.min((a, b)) = a if a <= b else b (no NaN reaches them here)
-__device__ __forceinline__ double track_max2(double a, double b) { return a >= b ? a : b; }
-__device__ __forceinline__ double track_min2(double a, double b) { return a <= b ? a : b; }
 
 __global__ __launch_bounds__(64) void track_step_kernel(const float* __restrict__ joints, const float* __restrict__ center, const float* __restrict__ M,
                                                         const float* __restrict__ cube, const float* __restrict__ cam, const int* __restrict__ pcl_count, int J,
@@ -81,27 +69,7 @@ __global__ __launch_bounds__(64) void track_step_kernel(const float* __restrict_
   if (any_bad) {
     st |= 4;
   } else {
-    float bx, bw, by, bh;
-    track_expand(ulo, uhi, expansion, bx, bw);
-    track_expand(vlo, vhi, expansion, by, bh);
-    // process_bbox(expansion 1, aspect ratio 1) in float64 on the four float32 values
-    const double X1 = track_max2(0.0, (double)bx), Y1 = track_max2(0.0, (double)by);
-    const double X2 = track_min2((double)(frame_w - 1), X1 + track_max2(0.0, (double)bw - 1.0));
-    const double Y2 = track_min2((double)(frame_h - 1), Y1 + track_max2(0.0, (double)bh - 1.0));
-    if ((double)bw * (double)bh > 0.0 && X2 >= X1 && Y2 >= Y1) {
-      double w = X2 - X1, h = Y2 - Y1;
-      const double cx = X1 + w / 2.0, cy = Y1 + h / 2.0;
-      if (w > h)
-        h = w;
-      else if (w < h)
-        w = h;
-      box[0] = cx - w / 2.0;
-      box[1] = cy - h / 2.0;
-      box[2] = w;
-      box[3] = h;
-    } else {
-      st |= 1;
-    }
+    if (!kpf_next_box(ulo, uhi, vlo, vhi, expansion, frame_w, frame_h, box)) st |= 1;  // (kpf_box_dev.h: the rule, shared with kpf_detect_hands_u16)
   }
   status[b] = st;
   if (st == 0) {

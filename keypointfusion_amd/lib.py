@@ -25,7 +25,7 @@ KPF_IN_SPLIT = 128
 KPF_OUT_SPLIT = 256
 KPF_W_SPLIT = 512
 KPF_DT_F32, KPF_DT_BF16, KPF_DT_F16 = 0, 1, 2
-ABI_VERSION = 35  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
+ABI_VERSION = 36  # KPF_ABI_VERSION of include/kpf.h: load() refuses a library built from another revision of the interface
 
 
 class ConvDesc(C.Structure):
@@ -163,6 +163,8 @@ _SIGS = {
     "kpf_overlay_project_f32": [_P, _P, _P, _P, C.c_float, C.c_float, C.c_int, C.c_int] + [_P] * 6 + [C.c_int, _P],
     "kpf_overlay_draw_u8": [C.POINTER(OverlayDrawDesc), _P],
     "kpf_align_depth_u16": [_P, C.c_int, C.c_int, _P] + [C.c_int] * 5 + [_P] * 4,
+    "kpf_detect_hands_u16": [_P] + [C.c_int] * 3 + [_P] + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_float, C.c_int] + [_P] * 8,
+    "kpf_detect_assign_f64": [_P] * 3 + [C.c_int] * 4 + [_P] + [C.c_int] * 2 + [_P] * 5,
     "kpf_tr_encoder_weight_floats": [C.c_int],
     "kpf_conv_num_tile_cfgs": [],
     "kpf_xattn_weight_floats": [],
@@ -270,6 +272,7 @@ _LONG_SIGS = {  # entries returning a long
     "kpf_tr_stack_dy_floats": [C.c_int],
     "kpf_tr_stack_part_floats": [C.c_int],
     "kpf_tr_stack_offset": [C.c_int, C.c_int, C.c_int],
+    "kpf_detect_ws64_words": [C.c_int] * 4,
 }
 EXPORTS = sorted(list(_SIGS) + list(_LONG_SIGS) + ["kpf_last_error", "kpf_abi_version"])
 

@@ -7,7 +7,8 @@ next box in device memory, so the steady state of a stream is one captured graph
 
     pre = DevicePreprocessor(img_size=128, sample_num=1024)
     ts = TrackedStream(model, pre, cam, frame_size=(480, 640), frames=1, frame_index=[0, 0])   # two hands in one camera frame
-    ts.reseed(detector_boxes)                    # [B][4] float64 (x, y, w, h) on the device
+    ts.reseed(boxes)                             # [B][4] float64 (x, y, w, h) on the device: the first boxes, from outside -- or none at all:
+    # TrackedStream(..., detector=detect.HandDetector(cam_frames, (480, 640), dev), reseed_after=3) finds the hands in the depth frame inside the step
     for rgb, depth in camera:                    # [F][H][W][3] uint8, [F][H][W] uint16 device tensors
         out = ts.step(rgb, depth)                # no host wait; out["frame_px"], out["cam_mm"], out["status"], out["lost"], ...
 
@@ -61,6 +62,15 @@ def next_bbox(joints_px, frame_w, frame_h, expansion=1.5):
         return np.array([cx - w / 2, cy - h / 2, w, h], np.float64)
 
 
+def check_detector(detector, frames, height, width, device, reseed_after):
+    """TrackedStream's refusal of a detect.HandDetector that does not read the stream's frames: their number, their size and the device must match"""
+    if (detector.F, detector.H, detector.W) != (frames, height, width) or detector.device != device:
+        raise ValueError("TrackedStream: the detector reads %d frames of %d x %d on %s, the stream holds %d of %d x %d on %s"
+                         % (detector.F, detector.H, detector.W, detector.device, frames, height, width, device))
+    if int(reseed_after) != reseed_after or int(reseed_after) < 1:
+        raise ValueError("TrackedStream: reseed_after = %r (an integer >= 1)" % (reseed_after,))
+
+
 class TrackedStream:
     """B tracks through a video of F stored frames per step: prepare (indexed) -> forward -> kpf_track_step_f32 on the current stream, no host wait.
 
@@ -78,9 +88,16 @@ class TrackedStream:
 
     aligner: a sensor.DepthAligner whose out_size is frame_size and which holds F frames -- step() then takes the RAW depth [F][Hd][Wd] of the depth sensor, and
     the body registers it to the colour camera (cam is the colour camera's) in front of prepare, inside the captured step; the step's outputs gain
-    align_stats [F][5] int32.  None: depth arrives registered, and nothing of the aligner's runs."""
+    align_stats [F][5] int32.  None: depth arrives registered, and nothing of the aligner's runs.
 
-    def __init__(self, model, pre, cam, frame_size, frames, frame_index=None, expansion=1.5, stage=5, seed=0, graph=True, forward=None, aligner=None):
+    detector: a detect.HandDetector that holds F frames of frame_size on this device -- the body then finds the hands in the (registered) depth frame and
+    hands the slots no live track stands on to the free tracks (never seeded, or lost >= reseed_after; detect.assign_host states the rule), behind the
+    aligner and in front of prepare, inside the captured step: a stream starts without a box from outside and a lost track finds its hand again.  The
+    state gains seeded [B] int32 (reseed() sets it for the tracks it writes), the outputs detections (the detector's dict), reseeded and seeded [B] int32.
+    None: no tensor, launch or output is added."""
+
+    def __init__(self, model, pre, cam, frame_size, frames, frame_index=None, expansion=1.5, stage=5, seed=0, graph=True, forward=None, aligner=None,
+                 detector=None, reseed_after=3):
         if not isinstance(cam, torch.Tensor) or cam.dim() != 2 or cam.shape[1] != 4 or cam.dtype != torch.float64:
             raise ValueError("TrackedStream: cam must be a float64 tensor [B][4] (fx, fy, u0, v0)")
         if cam.device.type != "cuda":
@@ -113,6 +130,11 @@ class TrackedStream:
                 raise ValueError("TrackedStream: the aligner registers %d frames to %d x %d on %s, the stream holds %d of %d x %d on %s"
                                  % (aligner.F, aligner.Hc, aligner.Wc, aligner.device, self.F, self.H, self.W, dev))
             self._raw = torch.zeros(self.F, aligner.Hd, aligner.Wd, dtype=torch.int16, device=dev).view(torch.uint16)  # the static raw depth of the captured step
+        self.detector, self.reseed_after, self.seeded, self.reseeded = detector, int(reseed_after), None, None
+        if detector is not None:
+            check_detector(detector, self.F, self.H, self.W, dev, reseed_after)
+            self.seeded = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.reseeded = torch.zeros(B, dtype=torch.int32, device=dev)
         self.bbox = torch.zeros(B, 4, dtype=torch.float64, device=dev)
         self.seed = int(seed) + torch.arange(B, dtype=torch.int64, device=dev)
         self.lost = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -133,11 +155,15 @@ class TrackedStream:
         if mask is None:
             self.bbox.copy_(bbox)
             self.lost.zero_()
+            if self.seeded is not None:
+                self.seeded.fill_(1)
             return
         if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (self.B,) or mask.dtype != torch.bool or mask.device != self.dev:
             raise ValueError("TrackedStream.reseed: mask must be a bool tensor [%d] on %s" % (self.B, self.dev))
         self.bbox.copy_(torch.where(mask.view(-1, 1), bbox, self.bbox))
         self.lost.copy_(torch.where(mask, torch.zeros_like(self.lost), self.lost))
+        if self.seeded is not None:
+            self.seeded.copy_(torch.where(mask, torch.ones_like(self.seeded), self.seeded))
 
     def _body(self):
         """One frame on the static buffers: what is captured.  Only launches on the current stream."""
@@ -145,6 +171,10 @@ class TrackedStream:
         align_stats = None
         if self.aligner is not None:  # the raw depth registered to the colour camera, into the static depth frame prepare reads
             align_stats = self.aligner.align(self._raw, out=self._depth)["stats"]
+        detections = None
+        if self.detector is not None:  # the hands of this frame, and the free tracks seeded from them: the boxes prepare is about to read
+            detections = self.detector.detect(self._depth)
+            self.detector.assign(self._fi, self.bbox, self.lost, self.seeded, self.reseeded, self.reseed_after)
         prep = pre.prepare(self._rgb, self._depth, self.bbox, self.cam, self.seed, frame_index=self._fi)
         if self._forward is not None:
             joints = self._forward(prep, self.frame_no)
@@ -175,6 +205,8 @@ class TrackedStream:
                    pcl=prep["pcl"], cube=prep["cube"], center=prep["center"])  # what mano_fit.cloud_mm needs: the sampled depth points and their frame
         if align_stats is not None:
             out["align_stats"] = align_stats
+        if detections is not None:
+            out["detections"], out["reseeded"], out["seeded"] = detections, self.reseeded, self.seeded
         return out
 
     def step(self, rgb, depth):
@@ -182,7 +214,8 @@ class TrackedStream:
         overwrites them: frame_px, crop_px [B][J][3] (u, v px, d mm), cam_mm [B][J][3], bbox_used [B][4] (this frame's box), bbox (the next frame's),
         status, lost [B] int32, and the prepare record com [B][3] float64, bounds [B][6], pcl_count [B] (+ joints, the forward's normalised output, and pcl
         [B][n][3], cube, center [B][3]: the sampled depth points normalised to the cube, mano_fit.cloud_mm(out) puts them back in camera space).
-        With an aligner, depth is the depth sensor's raw frame [F][Hd][Wd] uint16 and the outputs hold align_stats [F][5] int32 as well."""
+        With an aligner, depth is the depth sensor's raw frame [F][Hd][Wd] uint16 and the outputs hold align_stats [F][5] int32 as well; with a detector
+        they hold detections (HandDetector.detect's dict), reseeded and seeded [B] int32."""
         depth_in = self._depth if self.aligner is None else self._raw
         for name, t, want in (("rgb", rgb, self._rgb), ("depth", depth, depth_in)):
             if not isinstance(t, torch.Tensor) or t.dtype != want.dtype or tuple(t.shape) != tuple(want.shape):
